@@ -13,10 +13,13 @@ Multi-GPU: one process per GPU (torch.distributed, backend nccl = RCCL), every r
 generates its own batches (weak scaling, no data-path collective); the only exchange is one
 gather of the per-item status vector to rank 0 (the output manifest), inside the timed region.
 
-Output: ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant
-kernel = the implicit-GEMM MFMA kernel, measured with HIP events around each of its launches
-over one full UNet+ControlNet evaluation after the timed region) and `cpu_baseline` (the
-torch-CPU fp32 oracle on a bounded sample, rank 0 / N=1 only).
+Output: ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms
+up, times --steps steps and prints the line; `roofline`, `cpu_baseline` and `clock` are null.
+`--full` adds the secondary measurements: `clock` (shader clock sampled during the timed
+region), `roofline` (dominant kernel = the implicit-GEMM MFMA kernel, measured with HIP events
+around each of its launches over one full UNet+ControlNet evaluation after the timed region)
+and `cpu_baseline` (the torch-CPU fp32 oracle, rank 0 / N=1 only; see --baselines).
+`--dump-outputs DIR` writes what the last timed step returned as float32 .npy files.
 """
 import argparse
 import json
@@ -240,6 +243,29 @@ class ClockSampler:
                     how="one sleeping wave per sample on a side stream during the timed region: s_memtime / s_memrealtime (100 MHz)")
 
 
+DUMP_BUDGET_BYTES = 63 << 20          # data of --dump-outputs: under its 64 MB with the .npy headers
+
+
+def dump_outputs(path, images, nsfw):
+    """`--dump-outputs`: what a caller of the timed path received from its last step, as float32 .npy under `path`.
+    images.npy: the u8 images [B,H,W,3]; when they exceed the budget, the first items that fit, or (if not even one
+    does) a fixed seeded sample of the first item's values.  nsfw.npy: the safety checker's flags [B] (absent without it)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    flags = None if nsfw is None else nsfw.cpu().numpy().astype(np.float32)
+    img = images.cpu().numpy()
+    budget = DUMP_BUDGET_BYTES - (0 if flags is None else flags.nbytes)
+    n = min(img.shape[0], budget // (img[0].size * 4))
+    if n > 0:
+        img = img[:n].astype(np.float32)
+    else:
+        idx = np.sort(np.random.RandomState(0).choice(img[0].size, budget // 4, replace=False))
+        img = img[0].reshape(-1)[idx].astype(np.float32)
+    np.save(os.path.join(path, "images.npy"), img)
+    if flags is not None:
+        np.save(os.path.join(path, "nsfw.npy"), flags)
+
+
 def effective_cpus():
     """Host cores this process may actually use: min(affinity mask, cgroup CPU quota)."""
     n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
@@ -459,10 +485,15 @@ def main():
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--res", type=int, default=512)
     ap.add_argument("--ddim-steps", type=int, default=50)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements: shader clock during the timed region, the roofline pass after it, "
+                         "the CPU baseline (--baselines / --no-cpu-baseline); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0) to DIR/<name>.npy, float32, at most 64 MB in all")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--baselines", choices=["config0", "quick", "full"], default="config0",
-                    help="config0 (default): cpu_baseline = BASELINE configs[0] timed directly on the host cores (~70 s); quick: only "
-                         "the 15 s evaluation sample, extrapolated; full: config0 + the PyTorch-ROCm eager port")
+                    help="with --full. config0 (default): cpu_baseline = BASELINE configs[0] timed directly on the host cores "
+                         "(~70 s); quick: only the 15 s evaluation sample, extrapolated; full: config0 + the PyTorch-ROCm eager port")
     ap.add_argument("--no-safety-checker", action="store_true",
                     help="A/B only: the reference never disables the SD-1.5 safety checker, so the default step runs it")
     ap.add_argument("--tiny", action="store_true", help="reduced-width family (plumbing check only; INVALID as a result)")
@@ -617,6 +648,8 @@ def roofline_pass(pipe, ops, batches, neg, dev, value, n_gpus, f_img, s, dt, arg
 
 
 def run(args):
+    from concurrent.futures import ThreadPoolExecutor
+
     import numpy as np
     import torch
 
@@ -664,9 +697,9 @@ def run(args):
     vocab = cfgs["text"]["vocab"]
     neg = negative_prompt_ids(vocab)
 
-    def make_batch(step_idx):
+    def make_batch(step_idx, pool):
         base = (rank * 100000 + step_idx) * b
-        imgs = np.stack([synthetic_image(res, res, base + i) for i in range(b)])
+        imgs = np.stack(list(pool.map(lambda i: synthetic_image(res, res, base + i), range(b))))
         ids = synthetic_prompt_ids(b, seed=1 + base, vocab=vocab)
         g = torch.Generator().manual_seed(1 + base)
         lat = torch.randn((b, 4, res // 8, res // 8), generator=g, dtype=torch.float16)
@@ -677,7 +710,9 @@ def run(args):
         ctrl = ops.canny(imgs, 120, 200)
         return pipe.generate_batch(ids, neg, ctrl, lat_dev, s, 7.5, 0.75, latents_on_device=True)
 
-    batches = [make_batch(i) for i in range(args.warmup + args.steps)]   # resident in HBM before timing
+    # resident in HBM before timing; the images are drawn on a thread pool (numpy releases the GIL, each has its own seed)
+    with ThreadPoolExecutor(effective_cpus()) as pool:
+        batches = [make_batch(i, pool) for i in range(args.warmup + args.steps)]
     for i in range(args.warmup):
         hot_path(batches[i])
 
@@ -687,7 +722,7 @@ def run(args):
         torch.cuda.synchronize()
 
     barrier()
-    sampler = ClockSampler(dev).start() if rank == 0 else None
+    sampler = ClockSampler(dev).start() if rank == 0 and args.full else None
     t0 = time.time()
     status = []
     for i in range(args.steps):
@@ -708,6 +743,8 @@ def run(args):
     assert out.shape == (b, res, res, 3) and out.dtype == torch.uint8
     if gathered is not None:
         assert all(int(g.sum()) == b * args.steps for g in gathered), "the status gather did not deliver every rank's vector"
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, pipe.last_nsfw)
 
     images = n_gpus * b * args.steps
     value = images / dt
@@ -715,7 +752,7 @@ def run(args):
 
     # ---- roofline of the dominant kernel family (HIP events around every launch, one evaluation) ----
     roof = None
-    if rank == 0:
+    if rank == 0 and args.full:
         # the roofline pass runs AFTER the timed region and must never take the bench line down with it
         try:
             roof = roofline_pass(pipe, ops, batches, neg, dev, value, n_gpus, f_img, s, dt, args)
@@ -727,7 +764,7 @@ def run(args):
 
     cpu = None
     extra = None
-    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline and not args.tiny:
+    if rank == 0 and args.full and n_gpus == 1 and not args.no_cpu_baseline and not args.tiny:
         cpu = cpu_baseline(sample_only=(args.baselines == "quick"))
         if args.baselines == "full":
             extra = baselines_full(dev)

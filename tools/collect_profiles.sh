@@ -8,7 +8,7 @@ ROOT=${GRAFT_REPO_ROOT:-$PWD}
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-echo "== kernel trace" && rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_under_trace.json 2> $OUT/trace.err || exit 1
+echo "== kernel trace" && rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline > $OUT/bench_under_trace.json 2> $OUT/trace.err || exit 1
 echo "== pmc mfma" && rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $OUT/pmc_mfma -- python3 $ROOT/tools/pmc_step.py > /dev/null 2> $OUT/pmc_mfma.err || exit 1
 echo "== pmc fetch" && rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- python3 $ROOT/tools/pmc_step.py > /dev/null 2> $OUT/pmc_fetch.err || exit 1
 echo "== pmc write" && rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -- python3 $ROOT/tools/pmc_step.py > /dev/null 2> $OUT/pmc_write.err || exit 1

@@ -11,7 +11,8 @@ OUT=gpurun_out/r6_ab
 mkdir -p $OUT
 run() {   # tag, tree, env...
   tag=$1; tree=$2; shift 2
-  ( cd $tree && env "$@" python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline ) > $OUT/$tag.json 2> $OUT/$tag.err
+  full=$([ "$tree" = . ] && echo --full)      # this tree's `clock` needs --full; the round-4 tree measures it unasked
+  ( cd $tree && env "$@" python3 bench.py --gpus 1 --steps 20 --warmup 5 $full --no-cpu-baseline ) > $OUT/$tag.json 2> $OUT/$tag.err
   python3 - "$tag" $OUT/$tag.json <<'EOF' | tee -a gpurun_out/r6_ab/summary.txt
 import json, sys
 try:

@@ -1,0 +1,170 @@
+"""Rounding-error budgets for kernel parity (tests only).
+
+A bf16 kernel that is right differs from a float64 reference of the same operation (computed from the bf16-rounded operands, with
+the kernel's documented intermediate rounding points applied) by rounding only: the RNE output rounding (at most 2^-8 of |out|),
+bf16 intermediates (at most 2^-8 of the magnitude that was rounded) and fp32 accumulation in some order (far smaller).  All of
+these are bounded by 2^-8 times the per-output magnitude s_i of the terms that formed output i, so the error in units of
+`unit * s_i` stays O(1) and has no sign preference.  check_budget measures four statistics of that error:
+
+- max    max_i |e_i|,  e_i = (got_i - ref_i) / (unit * s_i)
+- rms    sqrt(mean e_i^2)
+- bias   mean(e_i * sign(ref_i)): negative = pulled toward zero (truncation instead of RNE, a denominator too large)
+- slope  sum (got_i - ref_i) ref_i / (unit * sum ref_i^2): a relative scale error of the whole output in units (a wrong eps, an
+         unmasked pad key, a wrong softmax scale)
+
+and asserts each against a per-family limit table.  bias and slope are means over the outputs, so even the correctly rounded
+result carries sampling noise in them (a few 1e-3 units at a few thousand outputs): their allowance is the table's systematic limit
+PLUS Z_NOISE standard errors of the statistic measured on the same outputs (se_bias = std(e sign(ref)) / sqrt(N), se_slope =
+sqrt(sum (err ref)^2) / (unit sum ref^2)).  A systematic slip grows with N; the noise allowance shrinks with it.  tests/test_errbudget.py proves on the CPU that every limit sits at least 2x
+above what legitimate emulations of the kernels produce and at least 2x below what a catalogue of subtly wrong results produces.
+"""
+import math
+
+import torch
+import torch.nn.functional as F
+
+UNIT_BF16 = 2.0 ** -8
+# SASPA_F32X3: a = hi + lo with hi = bf16(a), lo = bf16(a - hi), products hi*hi + hi*lo + lo*hi in fp32.  |a - hi - lo| <=
+# 2^-9 |a - hi| <= 2^-18 |a| and the dropped lo*lo <= 2^-18 |a b|: 2^-17 |a b| per product at most, fp32 accumulation below that.
+UNIT_F32X3 = 2.0 ** -17
+
+# Per family: max / rms / |bias| / |slope| in units.  Each value is checked against both margins in tests/test_errbudget.py.
+LIMITS = {
+    "gemm": dict(max=2.2, rms=0.3, bias=0.002, slope=0.032),
+    "attn": dict(max=3.2, rms=0.62, bias=0.024, slope=0.1),
+    "norm": dict(max=2.2, rms=0.9, bias=0.0145, slope=0.0095),
+    "elem": dict(max=2.2, rms=1.0, bias=0.025, slope=0.09),
+    "f32x3": dict(max=0.9, rms=0.2, bias=0.006, slope=0.036),
+}
+STATS = ("max", "rms", "bias", "slope")
+Z_NOISE = 8.0           # standard errors of bias / slope granted on top of the systematic limit (8 sigma: never by chance)
+
+
+def budget_stats(got, ref64, scale, unit):
+    """The four statistics (a dict, plus 'worst': the flat index of the largest |e|) of got against ref64."""
+    got = got.detach().to("cpu", torch.float64).reshape(-1)
+    ref = ref64.detach().to("cpu", torch.float64).reshape(-1)
+    s = scale.detach().to("cpu", torch.float64).expand_as(ref64).reshape(-1) if torch.is_tensor(scale) else \
+        torch.full_like(ref, float(scale))
+    if got.shape != ref.shape:
+        raise ValueError(f"shape mismatch: got {tuple(got.shape)} vs reference {tuple(ref.shape)}")
+    if not torch.isfinite(ref).all() or not (s > 0).all():
+        raise ValueError("reference must be finite and scale strictly positive (floor it)")
+    if not torch.isfinite(got).all():
+        bad = int((~torch.isfinite(got)).nonzero()[0])
+        return dict(max=math.inf, rms=math.inf, bias=math.inf, slope=math.inf, se_bias=0.0, se_slope=0.0, worst=bad)
+    err = got - ref
+    e = err / (unit * s)
+    worst = int(e.abs().argmax())
+    den = (ref * ref).sum().item()
+    n = e.numel()
+    es = e * torch.sign(ref)
+    return dict(max=e.abs().max().item(), rms=e.pow(2).mean().sqrt().item(), bias=es.mean().item(),
+                slope=(err * ref).sum().item() / (unit * den) if den > 0 else 0.0,
+                se_bias=es.std().item() / math.sqrt(n) if n > 1 else 0.0,
+                se_slope=(err * ref).pow(2).sum().sqrt().item() / (unit * den) if den > 0 else 0.0, worst=worst)
+
+
+def allowance(st, limits):
+    """The allowance of each statistic: the table's limit, plus Z_NOISE standard errors for bias and slope."""
+    return dict(max=limits["max"], rms=limits["rms"], bias=limits["bias"] + Z_NOISE * st["se_bias"],
+                slope=limits["slope"] + Z_NOISE * st["se_slope"])
+
+
+def ratio(st, limits):
+    """max over the four statistics of |stat| / allowance (<= 1: within budget)."""
+    a = allowance(st, limits)
+    return max(abs(st[k]) / a[k] for k in STATS)
+
+
+def fmt(st):
+    return " ".join(f"{k} {st[k]:+.3e}" for k in STATS)
+
+
+def check_budget(got, ref64, scale, unit, *, limits, what=""):
+    """Assert that got (kernel output, any dtype / device) is within the rounding budget of ref64 (float64 reference); scale is the
+    per-output magnitude s_i (broadcastable to ref64, floored > 0).  Returns the statistics (for printing)."""
+    st = budget_stats(got, ref64, scale, unit)
+    if ratio(st, limits) > 1.0:
+        w = st["worst"]
+        shape = tuple(ref64.shape)
+        idx = tuple(int(i) for i in torch.unravel_index(torch.tensor(w), shape))
+        g = got.detach().to("cpu", torch.float64).reshape(-1)[w].item()
+        r = ref64.detach().to("cpu", torch.float64).reshape(-1)[w].item()
+        a = allowance(st, limits)
+        raise AssertionError(f"{what}: error budget exceeded: {fmt(st)}; allowance " + " ".join(f"{k} {a[k]:.3e}" for k in STATS)
+                             + f" (limits {limits}, se_bias {st['se_bias']:.2e}, se_slope {st['se_slope']:.2e}); worst element "
+                             f"{idx}: got {g:.6g} ref {r:.6g}")
+    return st
+
+
+def rejects(got, ref64, scale, unit, *, limits):
+    """True when check_budget would fail (negative controls)."""
+    return ratio(budget_stats(got, ref64, scale, unit), limits) > 1.0
+
+
+# ------------------------------------------------------------------ magnitudes s_i (float64)
+def _abs64(t):
+    return t.detach().to("cpu", torch.float64).abs()
+
+
+def _floor(s, rel=2.0 ** -10, absolute=1e-30):
+    """Zero magnitudes (all-zero rows, a constant group) must not divide by zero: floor at rel * mean(s)."""
+    return s.clamp_min(max(rel * s.mean().item(), absolute))
+
+
+def gemm_scale(a, b, bias=None, *, alpha=1.0, residual=None, rowvec=None):
+    """|alpha| (|A| @ |B|^T + |bias| + |rowvec|) + |residual| for out = alpha (A B^T + bias + rowvec) + residual (act after the
+    sum: SiLU / GELU have |f'| <= 1.13, inside the factor-of-2 margin)."""
+    s = _abs64(a) @ _abs64(b).t()
+    if bias is not None:
+        s = s + _abs64(bias)
+    if rowvec is not None:
+        s = s + _abs64(rowvec)
+    s = abs(alpha) * s
+    if residual is not None:
+        s = s + _abs64(residual)
+    return _floor(s)
+
+
+def conv_scale(x, w, bias=None, *, stride=1, pad=1, residual=None, alpha=1.0):
+    """The GEMM magnitude of an NCHW convolution: conv2d(|x|, |w|) + |bias| (+ |residual|)."""
+    s = F.conv2d(_abs64(x), _abs64(w), None if bias is None else _abs64(bias), stride=stride, padding=pad)
+    s = abs(alpha) * s
+    if residual is not None:
+        s = s + _abs64(residual)
+    return _floor(s)
+
+
+def geglu_gemm_scale(hv, hg, mv, mg):
+    """out = hv * gelu(hg) with hv, hg GEMM outputs of magnitudes mv, mg: the error of each factor propagated through the product
+    (|gelu(hg)| mv + |hv gelu'(hg)| mg) plus |out| for the output rounding."""
+    hv, hg = hv.double(), hg.double()
+    phi = torch.exp(-0.5 * hg * hg) / math.sqrt(2 * math.pi)
+    gel = F.gelu(hg)
+    dgel = 0.5 * (1 + torch.erf(hg / math.sqrt(2))) + hg * phi
+    return _floor(gel.abs() * mv + (hv * dgel).abs() * mg + (hv * gel).abs())
+
+
+def attn_scale(p, v):
+    """sum_j p_ij |v_j| / l_i with p the float64 softmax weights [..., nq, nk] (already divided by l) and v [..., nk, d]."""
+    return _floor(p.double() @ _abs64(v))
+
+
+def norm_scale(xhat, gamma, beta, mu_rstd=None):
+    """|gamma * xhat| + |beta| for a normalised xhat [..., C] (channels last) and per-channel gamma, beta.  mu_rstd (mean * rstd,
+    broadcastable): the kernels apply y = x sc + (beta - mean sc) with sc = gamma rstd in fp32 (saspa_norm.hip, gn_apply_kernel and
+    the one-pass / fused forms that restate it), two fp32 terms of magnitude |mean sc| that cancel: 2^-24 of each, i.e. 2^-15 |mean sc|
+    in bf16 units, joins the budget (it dominates for a constant group, where rstd = eps^-1/2)."""
+    s = (xhat.double() * gamma.double()).abs() + beta.double().abs()
+    if mu_rstd is not None:
+        s = s + 2.0 ** -15 * (mu_rstd.double() * gamma.double()).abs()
+    return _floor(s)
+
+
+def elem_scale(*factors, floor=2.0 ** -8):
+    """|product of the factors| with an absolute floor near zero (GEGLU: hv * gelu(hg); SiLU: x * sigmoid(x))."""
+    s = torch.ones_like(factors[0], dtype=torch.float64)
+    for f in factors:
+        s = s * f.double().abs()
+    return s.clamp_min(floor)

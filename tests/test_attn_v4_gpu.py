@@ -6,7 +6,7 @@ import torch
 
 import saspa_aug_amd  # noqa: F401
 from saspa_aug_amd import ops
-from tests.test_kernels_gpu import _prescaled_q, _rand, _ref_attn, assert_close, q
+from tests.test_kernels_gpu import _poison_keys, _prescaled_q, _rand, _ref_attn, assert_close, q
 
 pytestmark = pytest.mark.gpu
 
@@ -24,6 +24,7 @@ def _run(dev, qs, kk, vv, heads, d, nq, nk):
     vt[:, :, :nk] = vv.transpose(1, 2).to(dev, dtype)
     qkbuf = torch.zeros(bsz, max(nq, nk), 2 * c, device=dev, dtype=dtype)           # q and k interleaved like a fused projection output
     qkbuf[:, :nq, :c] = qs.to(dev, dtype)
+    qkbuf[:, nk:, c:] = _poison_keys(qs.float(), max(nq, nk) - nk).to(dev, dtype)  # K rows past nk must be masked
     qkbuf[:, :nk, c:] = kk.to(dev, dtype)
     out = torch.zeros(bsz, nq, c, device=dev, dtype=dtype)
     ops.flash_attn(qkbuf[:, :nq, :c], qkbuf[:, :nk, c:], vt, out, heads, d, nq, nk, 123.0, False, prescaled=True)

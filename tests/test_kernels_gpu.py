@@ -221,6 +221,13 @@ def _ref_attn(qq, kk, vv, heads, causal=False):
     return (torch.softmax(s, -1) @ v2).transpose(1, 2).reshape(b, nq, c)
 
 
+def _poison_keys(qq, rows):
+    """Key rows that sit past nk in a buffer: pad row r is 4 x query r mod nq (every head), so each of those queries meets one
+    unmasked key that would dominate its softmax, instead of a harmless zero key."""
+    idx = torch.arange(rows) % qq.shape[1]
+    return 4.0 * qq[:, idx]
+
+
 @pytest.mark.parametrize("d,heads,nq,nk,causal", [
     (40, 8, 200, 200, False), (80, 4, 300, 300, False), (160, 2, 256, 256, False), (64, 3, 77, 77, True),
     (40, 8, 130, 77, False), (8, 4, 64, 64, False), (16, 2, 33, 200, False), (32, 4, 128, 64, False),
@@ -238,6 +245,7 @@ def test_flash_attn(dev, d, heads, nq, nk, causal):
     # q and k live interleaved in one buffer like a fused projection output
     qkbuf = torch.zeros(bsz, max(nq, nk), 2 * c, device=dev, dtype=dtype)
     qkbuf[:, :nq, :c] = qq.to(dev, dtype)
+    qkbuf[:, nk:, c:] = _poison_keys(qq, max(nq, nk) - nk).to(dev, dtype)   # K rows past nk (nq > nk) must be masked
     qkbuf[:, :nk, c:] = kk.to(dev, dtype)
     out = torch.zeros(bsz, nq, c, device=dev, dtype=dtype)
     ops.flash_attn(qkbuf[:, :nq, :c], qkbuf[:, :nk, c:], vt, out, heads, d, nq, nk, d ** -0.5, causal)

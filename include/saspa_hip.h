@@ -169,15 +169,15 @@ typedef struct SaspaGemmParams {
 } SaspaGemmParams;
 /* Non-zero if the A-stationary kernel can run the problem (bf16 pointwise layer, K = c0 = 320, N % 64 == 0, at least 192
  * blocks of 256 rows, no row vector / split-K / GroupNorm statistics / batching, alpha = 1, activation none or fused GEGLU,
- * 16-byte aligned operands, ldo % 8 == 0): the only kernel that takes ln_gamma / out_t.  2 = the row blocks also fill whole
- * rounds of the 256 CUs (the sizes where it beats the other kernels on every layer shape), 1 = they do not. */
+ * 16-byte aligned operands, ldo % 8 == 0): the only kernel that takes ln_gamma / out_t.  Returns 2 or 0 (the kernel deals its
+ * work evenly over the CUs at every eligible size; 1, "ragged last round", is no longer returned). */
 int saspa_gemm_as_eligible(const SaspaGemmParams* p);
 /* ABI 20: 1 if saspa_gemm with variant AUTO will run THIS problem on the A-stationary kernel (the predicate dispatch itself uses):
  * what a caller must ask before it plans around that choice -- e.g. dropping SaspaGemmParams.gn_stats, which that kernel's
  * epilogue does not produce.  (saspa_gemm_as_eligible says whether the kernel CAN run it.) */
 int saspa_gemm_as_auto(const SaspaGemmParams* p);
-/* ABI 20: which kernel family saspa_gemm would run `p` on and on how many K slices: the dispatch executed DRY (same validation, nothing
- * launched, `stream` not needed).  Returns family | (ksplit << 8), family = SASPA_GEMM_TILED / WIDE / WS / AS, or the SASPA_E* code
+/* ABI 20: which kernel family saspa_gemm would run `p` on and on how many K slices: saspa_gemm's validation and dispatch plan, nothing
+ * launched, `stream` not needed.  Returns family | (ksplit << 8), family = SASPA_GEMM_TILED / WIDE / WS / AS, or the SASPA_E* code
  * saspa_gemm would return.  Measurement aid: bench.py attributes every recorded launch to its kernel (roofline.dominant). */
 int saspa_gemm_which(const SaspaGemmParams* p);
 int saspa_gemm(const SaspaGemmParams* p, void* stream);

@@ -28,17 +28,6 @@
 #include "common.h"
 #include "gemm_internal.h"
 
-#ifdef SASPA_NO_KORDER
-constexpr bool KORDER_ON = false;   // A/B build: the K walk exactly as before ABI v4
-#else
-constexpr bool KORDER_ON = true;
-#endif
-
-SaspaDryRun* saspa_dry_state() {      // dry dispatch state of the calling thread (gemm_internal.h)
-  static thread_local SaspaDryRun st = {false, 0, 0};
-  return &st;
-}
-
 namespace {
 
 template <typename T> struct Mma;
@@ -628,7 +617,7 @@ __global__ __launch_bounds__(64 * NWM * NWN, (NWM * NWN == 4 && NSTAGE > 2) ? 1 
   const int kcs = (tid & 7) ^ (r0 & 7);           // logical 16-byte chunk fetched by this lane
   const int hw = p.hout * p.wout;
   const int ctot = p.c0 + p.c1;
-  const int chunk_major = (KORDER_ON && p.korder == SASPA_KORDER_CHUNK) ? 1 : 0;   // wave-uniform
+  const int chunk_major = p.korder == SASPA_KORDER_CHUNK ? 1 : 0;   // wave-uniform
   const rsrc_t rs0 = make_rsrc(a0);
   const rsrc_t rs1 = make_rsrc(p.c1 > 0 ? (const void*)a1 : (const void*)a0);
   const rsrc_t rsw = make_rsrc(w);
@@ -750,25 +739,17 @@ __global__ __launch_bounds__(64 * NWM * NWN, (NWM * NWN == 4 && NSTAGE > 2) ? 1 
       if (RPI * (i + 1) <= BN || RPI * i + 8 * wave < BN)
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (lds_void_t*)(lb + (RPI * i + 8 * wave) * 8), 16, (int)offb[i], soffw, 0, 0);
     ku += BK;
-    if (KORDER_ON) {
-      // branch-free mixed-radix step (a scalar branch in this path costs the DMA kernels ~25 %, measured): tap-major
-      // counts (c, x, y) with the channel offset fastest, chunk-major (x, y, c) with the tap fastest
-      const int cu_t = cu + BK;
-      const int wc = (cu_t >= ctot) ? 1 : 0;                        // tap-major: channel wrap carries into x
-      const int dx1 = dxu + (chunk_major ? 1 : wc);
-      const int wx = (dx1 == p.kw) ? 1 : 0;
-      const int dy1 = dyu + wx;
-      const int wy = (chunk_major && dy1 == p.kh) ? 1 : 0;          // chunk-major: tap wrap carries into the chunk
-      cu = chunk_major ? cu + (wy ? BK : 0) : (wc ? cu_t - ctot : cu_t);
-      dxu = wx ? 0 : dx1;
-      dyu = wy ? 0 : dy1;
-    } else {
-      cu += BK;
-      if (cu >= ctot) {
-        cu -= ctot;
-        if (++dxu == p.kw) { dxu = 0; ++dyu; }
-      }
-    }
+    // branch-free mixed-radix step (a scalar branch in this path costs the DMA kernels ~25 %, measured): tap-major
+    // counts (c, x, y) with the channel offset fastest, chunk-major (x, y, c) with the tap fastest
+    const int cu_t = cu + BK;
+    const int wc = (cu_t >= ctot) ? 1 : 0;                        // tap-major: channel wrap carries into x
+    const int dx1 = dxu + (chunk_major ? 1 : wc);
+    const int wx = (dx1 == p.kw) ? 1 : 0;
+    const int dy1 = dyu + wx;
+    const int wy = (chunk_major && dy1 == p.kh) ? 1 : 0;          // chunk-major: tap wrap carries into the chunk
+    cu = chunk_major ? cu + (wy ? BK : 0) : (wc ? cu_t - ctot : cu_t);
+    dxu = wx ? 0 : dx1;
+    dyu = wy ? 0 : dy1;
   };
 
   f32x4 acc[WM][WN];
@@ -985,10 +966,17 @@ __global__ __launch_bounds__(256) void splitk_reduce_stats_kernel(const SaspaGem
                      p.gn_stats + ((long long)rb * (p.N / p.gn_unit) + (cs * BC) / p.gn_unit) * 2);
 }
 
+// The DMA loaders (LDS-DMA kernels of both tile widths) need a K-tile inside one tap of one source; a nearest-x2 input also needs
+// pad <= 1 and the packed 16-bit window corner of gemm_dma_kernel
+bool dma_loader_ok(const SaspaGemmParams& p) {
+  const int bk = p.dtype == SASPA_BF16 ? 64 : 32;
+  const int ctot = p.c0 + p.c1;
+  return (ctot % bk) == 0 && (p.c1 == 0 || (p.c0 % bk) == 0) && (!p.upsample || (p.pad <= 1 && p.hin < 16000 && p.win < 16000));
+}
+
 template <typename T, int WM, int WN, int NWM = 2, int NWN = 2>
 int launch(const SaspaGemmParams& p, hipStream_t s, int ksplit) {
   constexpr int BM = 16 * WM * NWM, BN = 16 * WN * NWN, NT = 64 * NWM * NWN;
-  SASPA_DRY_RETURN(SASPA_GEMM_TILED, ksplit);
   const int tiles = ((p.N + BN - 1) / BN) * ((p.M + BM - 1) / BM);
   // persistent grid: as many workgroups as the chip keeps resident (256 CUs x blocks/CU by LDS / VGPR budget)
   constexpr int kResident = 256 * (NT > 256 ? 1 : ((BM + BN) * 256 > 48 * 1024 ? 2 : 4));
@@ -997,28 +985,19 @@ int launch(const SaspaGemmParams& p, hipStream_t s, int ksplit) {
   if ((long long)tiles * zy > kResident) gx = max(1, min(tiles, kResident / zy));
   dim3 grid(gx, ksplit, p.nb1 * p.nb2);
   const bool pw = p.kh == 1 && p.kw == 1 && p.stride == 1 && p.pad == 0 && !p.upsample;
-  constexpr int BK = 128 / (int)sizeof(T);
-  const int ctot = p.c0 + p.c1;
-  static const bool dma_off = getenv("SASPA_GEMM_DMA") && atoi(getenv("SASPA_GEMM_DMA")) == 0;   // A/B knob
   static const int abl = getenv("SASPA_GEMM_ABLATE") ? (atoi(getenv("SASPA_GEMM_ABLATE")) & 15) : 0;       // diagnostics only
   const int tiles_abl = tiles | (abl << 28);
   const int npart8 = saspa_gemm_npart8(p, BM, BN, gx, tiles);
-  const bool fast = (ctot % BK) == 0 && (p.c1 == 0 || (p.c0 % BK) == 0) && !dma_off &&
-                    (!p.upsample || (p.pad <= 1 && p.hin < 16000 && p.win < 16000));
-  if (p.korder == SASPA_KORDER_CHUNK && !fast) return SASPA_ERANGE;   // only the DMA kernels walk K chunk-major
-  if (p.w_split && (!fast || !is_x3<T>::value)) return SASPA_ERANGE;  // pre-split weights: only the SASPA_F32X3 DMA loop reads them
   if constexpr (NT != 256) {
-    // 8-wave tiles exist only as DMA kernels; dispatch() guarantees `fast`
-    if (!fast) return SASPA_ERANGE;
+    // 8-wave tiles exist only as DMA kernels (the plan checked dma_loader_ok)
     if (pw) hipLaunchKernelGGL((gemm_dma_kernel<T, WM, WN, NWM, NWN, true, 3>), grid, dim3(NT), 0, s, p, tiles_abl, npart8);
     else if (p.upsample) hipLaunchKernelGGL((gemm_dma_kernel<T, WM, WN, NWM, NWN, false, 3, true>), grid, dim3(NT), 0, s, p, tiles_abl, npart8);
     else hipLaunchKernelGGL((gemm_dma_kernel<T, WM, WN, NWM, NWN, false, 3>), grid, dim3(NT), 0, s, p, tiles_abl, npart8);
-  } else if (fast) {
+  } else if (dma_loader_ok(p)) {
     // few tiles (<= ~1 workgroup per CU): spend the idle LDS on a 4-deep DMA ring (latency-bound
     // K loops); otherwise 2 stages and 2 workgroups per CU
-    static const int force_st = getenv("SASPA_GEMM_STAGES") ? atoi(getenv("SASPA_GEMM_STAGES")) : 0;
     constexpr bool can4 = (BM + BN) * 128 * 4 <= 160 * 1024;
-    const bool deep = can4 && (force_st ? force_st == 4 : (long long)tiles * zy <= 320);
+    const bool deep = can4 && (long long)tiles * zy <= 320;
     if (deep) {
       if (pw) hipLaunchKernelGGL((gemm_dma_kernel<T, WM, WN, 2, 2, true, can4 ? 4 : 2>), grid, dim3(256), 0, s, p, tiles_abl, npart8);
       else if (p.upsample) hipLaunchKernelGGL((gemm_dma_kernel<T, WM, WN, 2, 2, false, can4 ? 4 : 2, true>), grid, dim3(256), 0, s, p, tiles_abl, npart8);
@@ -1037,28 +1016,74 @@ int launch(const SaspaGemmParams& p, hipStream_t s, int ksplit) {
   return 0;
 }
 
-// K-split of the 8-wave kernel from a cost model instead of "about one workgroup per CU" (round 3): with t tiles and ks slices
-// the launch takes ceil(t * ks / 256) ROUNDS of workgroups, each c0 + (K-tiles per slice) * c1 long, plus a reduce pass
-// over ks fp32 slabs.  The old rule rounded 256 / t to the nearest integer, which at the tile counts of non-square images
-// (88 / 96 / 176 tiles at 512x704 / 512x768) lands just ABOVE a whole number of rounds -- 264 workgroups = two rounds at
-// half occupancy.  Constants fitted on tools/conv_variant_sweep.py (profiles/r3_conv_sweep_704.txt): c0 = 20 us per workgroup
-// (prologue, epilogue, launch), c1 = 1.34 us per 64-deep K-tile of a 256 x 320 tile (x 0.8 for 256 x 256), reduce at 4 TB/s.
-// The wave-specialised kernel runs one workgroup per CU: t tiles take ceil(t / 256) rounds.  352 tiles (the 16x22 level of a
-// 512x704 image) would be two rounds at 69 %; the 4-wave tiles (two workgroups per CU) take those in one.  SASPA_GEMM_KSPLIT_MODEL=0
-// restores the round-2 rule (any 256 <= t < 512).
-static bool ws_round_ok(long long t) {
-  static const bool model = !(getenv("SASPA_GEMM_KSPLIT_MODEL") && atoi(getenv("SASPA_GEMM_KSPLIT_MODEL")) == 0);
-  if (!model) return true;
-  const long long rounds = (t + 255) / 256;
-  return t * 100 >= rounds * 256 * 85;
+// ---- the dispatch policy of the GEMM family ---------------------------------------------------------------------------------
+// plan_gemm() decides, for a validated problem, the kernel family, its tile and the K split -- or refuses the problem; saspa_gemm
+// runs the plan, saspa_gemm_which reports it, saspa_gemm_suggest_ksplit and saspa_gemm_as_auto answer from the same rules.  Every
+// threshold is written once, here; the measurements behind them are in DESIGN.md (kernel table, K-split and round rules).
+constexpr int kCUs = 256;
+// a round of one-workgroup-per-CU launches counts as full from 85 % of its slots; a wide launch just over a whole number of rounds
+// with its last round below 65 % (264 / 288 tiles of the fused Q|K|V projection of the 16x22 / 16x24 level: 99 us against 81 on
+// the 4-wave tiles) takes the finer tiles
+constexpr int kRoundFull = 85, kRoundRagged = 65;
+// 8-wave wide kernel (256 x 320 / 256 tiles):
+constexpr int kWideKMin = 640;                // K below this never goes wide
+constexpr int kWideKFull = 960;               // 640 <= K < 960 (the level-1 pointwise layers) only un-split, from kWideAlone tiles
+                                              // (a twin beside it: kTwinWholeRound)
+constexpr int kLongK = 4096;                  // from here on one slice at half the chip, or K slices on the wide kernel
+constexpr long long kTwinWholeRound = 96;     // with a twin launch beside it (sharing): un-split, whatever K
+constexpr long long kWideAlone = 144;         // alone: un-split from 144 tiles (the 32x44 / 32x48 levels: 176 / 192 workgroups in one
+                                              // round against 704 / 768 4-wave tiles in two, 74 vs 124 us; 128, the 512x512 case, ties)
+constexpr long long kWideSplitMinTiles = 24;  // fewer tiles than CUs but long K: the wide kernel on K slices (1.17 - 1.45x the 4-wave
+                                              // tiles on the 3x3 convs of the 32x32 / 16x16 levels)
+constexpr long long kWideGegluTiles = 384;    // fused GEGLU projection: at least 1.5 rounds of wide tiles
+// wave-specialised kernel: short-K GEGLU projections (level 0: 199 vs 214 us) and one full round of 128-row tiles
+constexpr int kWsGegluKMax = 384;
+// A-stationary kernel on a ragged last round of row blocks: the layers with a residual or at least this many columns
+constexpr int kAsRaggedMinN = 640;
+
+// t work items in rounds of kCUs: is the last round at least pct % full?
+bool fills_rounds(long long t, int pct) { return t * 100 >= (t + kCUs - 1) / kCUs * kCUs * pct; }
+
+// exactly one round of 128-row tiles, full: the wave-specialised kernel without K slices (19 vs 24 us at (4096, 1280, 1280), 52 vs
+// 72 at (4096, 1280, 5120)); with more tiles it only ties the 4-wave kernel and, owning the CU's whole LDS, keeps the other graph
+// branch's kernels off the CU.  352 tiles (the 16x22 level of a 512x704 image) would be two rounds at 69 %.
+bool ws_one_round(long long t128) { return t128 >= kCUs && t128 < 2 * kCUs && fills_rounds(t128, kRoundFull); }
+
+long long tiles128(const SaspaGemmParams& p) {
+  const int bn = (p.N % 160 == 0) ? 160 : 128;
+  return (long long)((p.M + 127) / 128) * ((p.N + bn - 1) / bn);
+}
+// the wide kernel's tile width in 64-column units (5: 320, 4: 256), 0 if N fits neither
+int wide_fn(const SaspaGemmParams& p) { return (p.N % 320 == 0) ? 5 : (p.N % 256 == 0) ? 4 : 0; }
+long long wide_tiles(const SaspaGemmParams& p, int fn) { return (long long)((p.M + 255) / 256) * (p.N / (64 * fn)); }
+
+// The wide kernel under AUTO for t tiles and the caller's K split: the split it runs on, or 0 = not taken.  With GroupNorm statistics
+// (gn) neither the short-K admission nor the ragged-round exception applies.
+int wide_auto(const SaspaGemmParams& p, long long t, int ksplit, bool must_split, bool gn) {
+  if (p.K < kWideKMin) return 0;
+  if (p.K < kWideKFull && (gn || ksplit != 1 || must_split || t < (p.sharing ? kTwinWholeRound : kWideAlone))) return 0;
+  if (ksplit == 1 && p.sharing && t >= kTwinWholeRound) return 1;
+  if (ksplit == 1 && p.K >= kLongK && t >= kCUs / 2) return 1;        // one slice chosen by the cost model, half the CUs busy
+  const bool ragged = !gn && t > kCUs && !fills_rounds(t, kRoundRagged);
+  if (ksplit == 1 && !must_split && !ragged && t >= kWideAlone) return 1;
+  if (ksplit > 1 && p.K >= kLongK && t >= kWideSplitMinTiles && t * ksplit >= kCUs / 2) return ksplit;
+  return 0;
 }
 
-// wide (256-row) tiles from which a launch with a twin beside it (SaspaGemmParams.sharing) runs un-split on the 8-wave kernel:
-// one constant for dispatch() and saspa_gemm_suggest_ksplit
-constexpr long long kTwinWholeRound = 96;
+// A-stationary kernel under AUTO: whole rounds of 256-row blocks, or -- with a ragged last round (352 blocks at 512x704) -- the
+// layers with a residual or >= kAsRaggedMinN columns, not the GEGLU projection (tools/as_bench.py); the only kernel with a fused
+// LayerNorm / transposed tail
+bool as_auto(const SaspaGemmParams& p) {
+  if (p.variant != SASPA_GEMM_AUTO || p.defer_reduce || !saspa_gemm_as_ok(p)) return false;
+  const long long blocks = (p.M + 255) / 256;
+  return p.ln_gamma || p.out_t || fills_rounds(blocks, kRoundFull) || (p.act != SASPA_ACT_GEGLU && (p.residual || p.N >= kAsRaggedMinN));
+}
 
-// ncu: CUs the launch may count on -- 256, or 128 when a twin launch shares the chip (SaspaGemmParams.sharing)
-static int pp_choose_ksplit(long long t, int ktiles, long long mn, int fn, int ncu = 256) {
+// K-split of the wide kernel from a cost model (round 3): with t tiles and ks slices the launch takes ceil(t * ks / ncu) ROUNDS
+// of workgroups, each c0 + (K-tiles per slice) * c1 long, plus a reduce pass over ks fp32 slabs.  Constants fitted on
+// tools/conv_variant_sweep.py (profiles/r3_conv_sweep_704.txt): c0 = 20 us per workgroup (prologue, epilogue, launch), c1 = 1.34 us
+// per 64-deep K-tile of a 256 x 320 tile (x 0.8 for 256 x 256), reduce at 4 TB/s.  ncu: 256, or 128 beside a twin launch.
+int pp_choose_ksplit(long long t, int ktiles, long long mn, int fn, int ncu) {
   const double c0 = 20.0, c1 = fn == 5 ? 1.34 : 1.07;
   int best = 1;
   double best_cost = 1e30;
@@ -1072,258 +1097,107 @@ static int pp_choose_ksplit(long long t, int ktiles, long long mn, int fn, int n
   return best;
 }
 
-template <typename T>
-int dispatch(const SaspaGemmParams& p, hipStream_t s) {
-  const long long nb = (long long)p.nb1 * p.nb2;
-  // A-stationary kernel (saspa_gemm_as.hip): pointwise bf16 layers with K = 320 and enough rows to fill the chip; the only
-  // kernel that takes a fused LayerNorm / a transposed second output
-  if constexpr (sizeof(T) == 2) {
-    if (p.variant == SASPA_GEMM_AS) return p.defer_reduce ? SASPA_ERANGE : saspa_gemm_as_launch(p, s);      // (no slabs on this kernel)
-    // AUTO: one predicate with the callers that plan around this choice (saspa_gemm_as_auto, saspa_gemm_as.hip)
-    if (saspa_gemm_as_auto(&p)) return saspa_gemm_as_launch(p, s);
-  }
-  if (p.ln_gamma || p.out_t || p.variant == SASPA_GEMM_AS) return SASPA_ERANGE;
-  int ksplit = (p.workspace && p.ksplit > 1 && nb == 1 && p.N % 4 == 0) ? p.ksplit : 1;
-  // ABI 18 deferred reduce: the caller will hand `workspace` to saspa_splitk_groupnorm, which sums exactly p.ksplit slabs.  A
-  // launch that ends up on ONE slice (or on a kernel that writes no slabs) would leave the workspace uninitialised and the
-  // consumer would normalise garbage without any error: every branch below that drops the K split is closed to such a call,
-  // and a call that cannot be split at all fails here (round-4 advisor finding).
-  const bool must_split = p.defer_reduce != 0;
-  if (must_split && (ksplit <= 1 || p.act == SASPA_ACT_GEGLU || p.N <= 32 || p.variant == SASPA_GEMM_WS)) return SASPA_ERANGE;
-  const bool n160 = (p.N % 160) == 0;
-  if (p.gn_stats) {
-    // statistics need the LDS-staged bf16 epilogue on 160 / 320-column tiles of 128 / 256 rows (saspa_gemm checked the
-    // shape): the 8-wave kernel where AUTO would take it, the 4-wave 128x160 tiles otherwise -- never the wave-specialised
-    // kernel (its epilogue waves have no statistics pass) or the 64x64 tiles
-    if constexpr (sizeof(T) == 2) {
-      if (p.variant == SASPA_GEMM_WS) return SASPA_ERANGE;
-      static const int pp_mode_g = getenv("SASPA_GEMM_PP") ? atoi(getenv("SASPA_GEMM_PP")) : 1;
-      const bool can = nb == 1 && (p.N % 320) == 0 && saspa_gemm_pp_eligible(p);
-      if (p.variant == SASPA_GEMM_WIDE) return can ? saspa_gemm_pp_launch(p, s, ksplit, 5) : SASPA_ERANGE;
-      if (can && pp_mode_g != 0 && p.variant == SASPA_GEMM_AUTO && p.K >= 960) {
-        const long long t = (long long)((p.M + 255) / 256) * (p.N / 320);
-        static const bool model_g = !(getenv("SASPA_GEMM_KSPLIT_MODEL") && atoi(getenv("SASPA_GEMM_KSPLIT_MODEL")) == 0);
-        // a twin launch beside this one (sharing): a whole round of the HALF chip is 128 tiles, whatever K (tools/twin_sweep.py)
-        if (model_g && p.sharing && ksplit == 1 && t >= kTwinWholeRound) return saspa_gemm_pp_launch(p, s, 1, 5);
-        if (model_g && ksplit == 1 && p.K >= 4096 && t >= 128) return saspa_gemm_pp_launch(p, s, 1, 5);
-        if (!must_split && t >= (model_g ? 144 : 192) && (!model_g || ksplit == 1)) return saspa_gemm_pp_launch(p, s, 1, 5);
-        static const bool wide_ks_g = !(getenv("SASPA_GEMM_WIDE_SPLITK") && atoi(getenv("SASPA_GEMM_WIDE_SPLITK")) == 0);
-        if (wide_ks_g && ksplit > 1 && p.K >= 4096 && t >= 24 && t * ksplit >= 128) return saspa_gemm_pp_launch(p, s, ksplit, 5);
-      }
-      return launch<T, 4, 5>(p, s, ksplit);
-    } else {
-      return SASPA_ERANGE;
-    }
-  }
-  if constexpr (sizeof(T) == 2) {
-    if (p.variant == SASPA_GEMM_WS) return saspa_gemm_ws_launch(p, s);
-  } else {
-    if (p.variant == SASPA_GEMM_WS) return SASPA_ERANGE;
-  }
-  if (p.act == SASPA_ACT_GEGLU) {
-    if constexpr (sizeof(T) == 2) {
-      // level-0 projection (K = 320): 199 vs 214 us on the wave-specialised kernel; K >= 640 is faster on the 4-wave tiles
-      static const bool ws_on_g = !(getenv("SASPA_GEMM_WS") && atoi(getenv("SASPA_GEMM_WS")) == 0);
-      const long long t = (long long)((p.M + 127) / 128) * (p.N / (n160 ? 160 : 128));
-      if (ws_on_g && p.variant == SASPA_GEMM_AUTO && nb == 1 && t >= 256 && p.K <= 384 && saspa_gemm_ws_eligible(p)) return saspa_gemm_ws_launch(p, s);
-    }
-    if constexpr (sizeof(T) == 2) {
-      // long K and at least two waves of 256 x 320 tiles: the wide kernel (116 vs 142 us at (4096, 10240, 1280))
-      static const bool wide_g = !(getenv("SASPA_GEMM_WIDE_GEGLU") && atoi(getenv("SASPA_GEMM_WIDE_GEGLU")) == 0);   // A/B knob
-      // round 6: K >= 640 (was 1 024).  With the long-interval loop the level-1 projection (16384, 5120, 640) runs 117 us on the wide
-      // kernel against 137-139 on the 4-wave tiles (175 vs 198-201 at the 512x704 bucket's 22 528 rows), alone and beside a twin
-      // (pair 238 vs 270-275): tools/pointwise_dispatch_sweep.py, tools/twin_sweep.py -> profiles/r6_pointwise_sweep.txt
-      static const int wide_g_k = getenv("SASPA_GEMM_WIDE_GEGLU_K") ? atoi(getenv("SASPA_GEMM_WIDE_GEGLU_K")) : 640;
-      const bool want = p.variant == SASPA_GEMM_WIDE || (wide_g && p.variant == SASPA_GEMM_AUTO && p.K >= wide_g_k &&
-                                                         (long long)((p.M + 255) / 256) * (p.N / 320) >= 384);
-      if (want && nb == 1 && saspa_gemm_pp_eligible(p)) return saspa_gemm_pp_launch(p, s, 1, 5);
-      if (p.variant == SASPA_GEMM_WIDE) return SASPA_ERANGE;
-    }
-    return n160 ? launch<T, 4, 5>(p, s, 1) : launch<T, 4, 4>(p, s, 1);
-  }
-  static const int force_tile = getenv("SASPA_GEMM_TILE") ? atoi(getenv("SASPA_GEMM_TILE")) : 0;   // tuning knob
-  if (force_tile == 845) return launch<T, 4, 5, 4, 2>(p, s, ksplit);   // 256x160, 8 waves
-  if (force_tile == 45) return launch<T, 4, 5>(p, s, ksplit);
-  if (force_tile == 44) return launch<T, 4, 4>(p, s, ksplit);
-  if (force_tile == 25) return launch<T, 2, 5>(p, s, ksplit);
-  if (force_tile == 24) return launch<T, 2, 4>(p, s, ksplit);
-  if (force_tile == 22) return launch<T, 2, 2>(p, s, ksplit);
-  if (force_tile == 41) return launch<T, 4, 1>(p, s, ksplit);
-  if (p.N <= 32) return launch<T, 4, 1>(p, s, 1);
-  if constexpr (sizeof(T) == 2) {
-    // long-K layers with enough 256-row tiles to fill the chip: 8-wave 256 x 320/256 kernel (saspa_gemm_pp.hip).
-    // SASPA_GEMM_PP: 0 = never (A/B knob), 4 / 5 / 14 / 15 = force a tile / loop flavour (tools/pp_check.py)
-    static const int pp_mode = getenv("SASPA_GEMM_PP") ? atoi(getenv("SASPA_GEMM_PP")) : 1;
-    const bool can = nb == 1 && saspa_gemm_pp_eligible(p);
-    if (p.variant == SASPA_GEMM_WIDE) {
-      if (!can) return SASPA_ERANGE;
-      return saspa_gemm_pp_launch(p, s, ksplit, (p.N % 320 == 0 || p.N % 256 != 0) ? 5 : 4);
-    }
-    if (can && pp_mode >= 4) return saspa_gemm_pp_launch(p, s, ksplit, pp_mode);
-    // round 6: short K (640 <= K < 960: the level-1 pointwise layers) is admitted where the sweeps of the long-interval loop show
-    // the wide kernel ahead -- beside a twin from a whole round of the half chip on (pairs: (16384, 640, 640) + residual 38 vs 50 us,
-    // (16384, 1920, 640) 84 vs 100), alone from 144 tiles on ((16384, 1920, 640): 50.6 vs 53.9; at 128 tiles the 4-wave kernel keeps
-    // (16384, 640, 640): 25.4 vs 29.7).  SASPA_GEMM_WIDE_KMIN=960 restores the round-5 gate.
-    static const int wide_kmin = getenv("SASPA_GEMM_WIDE_KMIN") ? atoi(getenv("SASPA_GEMM_WIDE_KMIN")) : 640;
-    if (can && pp_mode == 1 && p.variant == SASPA_GEMM_AUTO && p.K >= wide_kmin) {
-      const int fn = (p.N % 320 == 0) ? 5 : (p.N % 256 == 0) ? 4 : 0;
-      const long long t0 = fn ? (long long)((p.M + 255) / 256) * (p.N / (64 * fn)) : 0;
-      // (alone: from 144 tiles, the un-split threshold below -- (22528, 640, 640) + residual, 176 tiles: 31.9 vs 44.6 us; 128 tiles, the
-      // 512x512 case, stay on the 4-wave kernel: 25.4 vs 29.7)
-      const bool short_ok = p.K >= 960 || (ksplit == 1 && !must_split && (p.sharing ? t0 >= kTwinWholeRound : t0 >= 144));
-      if (fn && short_ok) {
-        const long long t = t0;
-        static const bool model = !(getenv("SASPA_GEMM_KSPLIT_MODEL") && atoi(getenv("SASPA_GEMM_KSPLIT_MODEL")) == 0);   // A/B knob
-        // a twin launch of the same shape shares the chip (SaspaGemmParams.sharing): 96+ wide tiles are a whole round of this
-        // launch's half, for every K the wide kernel takes -- pair times of tools/twin_sweep.py (profiles/r4_twin_sweep.txt):
-        // (16384, 640, 2560) + residual 112 vs 152 us, conv (16384, 640, 2880) 106 vs 139, conv (16384, 640, 5760) 183 vs 270
-        if (model && p.sharing && ksplit == 1 && t >= kTwinWholeRound) return saspa_gemm_pp_launch(p, s, 1, fn);
-        // long K, one slice chosen by the cost model (suggest_ksplit) and at least half the CUs busy: still the wide kernel
-        if (model && ksplit == 1 && p.K >= 4096 && t >= 128) return saspa_gemm_pp_launch(p, s, 1, fn);
-        // 3/4 of a wave of tiles or more: no split-K.  (144 <= t < 192 is the 512x704 / 512x768 buckets' 32x44 / 32x48 level:
-        // 176 / 192 workgroups in one round against 704 / 768 4-wave tiles in two rounds of 512 slots -- 74 vs 124 us at
-        // (22528, 640, 2560); t = 128, the 512x512 case, ties and stays on the 4-wave tiles)
-        // ... unless the tiles are just over a whole number of rounds (264 / 288 tiles of the fused Q|K|V projection of the 16x22 /
-        // 16x24 level: two rounds at 52-56 %, 99 us against 81 on the 4-wave tiles): then the finer tiles below
-        const bool ragged = model && t > 256 && t * 100 < ((t + 255) / 256) * 256 * 65;
-        if (!must_split && !ragged && t >= (model ? 144 : 192) && (!model || ksplit == 1)) return saspa_gemm_pp_launch(p, s, 1, fn);
-        // fewer wide tiles than CUs but a long K (the 3x3 convs of the 32x32 / 16x16 levels): the wide kernel on K
-        // slices -- measured 1.17-1.45x the 128x160 kernel at M = 16 384 / 4 096 (tools/conv_variant_sweep.py)
-        static const bool wide_ks = !(getenv("SASPA_GEMM_WIDE_SPLITK") && atoi(getenv("SASPA_GEMM_WIDE_SPLITK")) == 0);   // A/B knob
-        if (wide_ks && ksplit > 1 && p.K >= 4096 && t >= 24 && t * ksplit >= 128) return saspa_gemm_pp_launch(p, s, ksplit, fn);
-      }
-    }
-  } else {
-    if (p.variant == SASPA_GEMM_WIDE) return SASPA_ERANGE;
-  }
-  const int bn = n160 ? 160 : 128;
-  if constexpr (sizeof(T) == 2) {
-    // exactly one wave of 128-row tiles (256 <= tiles < 512: the 16x16-level linears, where the 2-workgroups-per-CU kernel
-    // runs half empty) and no K slices: the wave-specialised kernel (saspa_gemm_ws.hip) -- 19 vs 24 us at (4096, 1280,
-    // 1280), 52 vs 72 us at (4096, 1280, 5120); with more tiles it only ties the 4-wave kernel (both sit at the L2 -> LDS
-    // fill rate of a 128x160 tile, tools/ws_stamps.py) and, owning the CU's whole LDS, it keeps the other graph branch's
-    // kernels off the CU (bench 6.07 vs 6.14 images/s when used everywhere).  SASPA_GEMM_WS=0 turns it off (A/B knob).
-    static const bool ws_on = !(getenv("SASPA_GEMM_WS") && atoi(getenv("SASPA_GEMM_WS")) == 0);
-    static const int ws_max = getenv("SASPA_GEMM_WS_MAXTILES") ? atoi(getenv("SASPA_GEMM_WS_MAXTILES")) : 512;
-    if (ws_on && p.variant == SASPA_GEMM_AUTO && ksplit == 1 && nb == 1 && saspa_gemm_ws_eligible(p)) {
-      const long long t = (long long)((p.M + 127) / 128) * ((p.N + bn - 1) / bn);
-      if (t >= 256 && t < ws_max && ws_round_ok(t)) return saspa_gemm_ws_launch(p, s);
-    }
-  }
-  const long long tiles = (long long)((p.M + 127) / 128) * ((p.N + bn - 1) / bn) * nb * ksplit;
-  if (tiles >= 160 && p.N > 64) return n160 ? launch<T, 4, 5>(p, s, ksplit) : launch<T, 4, 4>(p, s, ksplit);
-  return launch<T, 2, 2>(p, s, ksplit);
+int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+// Measurement pins (tools/tile_sweep.py, tools/pp_check.py ...), read once.  SASPA_GEMM_TILE = WM WN of a 4-wave tile (45 44 25 24
+// 22 41) or 845 = the 8-wave 256x160 tile; SASPA_GEMM_PP = 0: never the wide kernel, 4 / 5 / 14 / 15 / 24 / 25: force its tile and
+// loop flavour, 1: AUTO
+struct Pins { int tile, pp; };
+const Pins& pins() {
+  static const Pins v = [] {
+    const int t = env_int("SASPA_GEMM_TILE", 0);
+    const bool tile = t == 845 || t == 45 || t == 44 || t == 25 || t == 24 || t == 22 || t == 41;
+    return Pins{tile ? t : 0, env_int("SASPA_GEMM_PP", 1)};
+  }();
+  return v;
 }
 
-}  // namespace
+struct GemmPlan {
+  int family;   // SASPA_GEMM_TILED / WIDE / WS / AS
+  int tile;     // TILED: WM * 10 + WN of the 4-wave tile, or 845; WIDE: fn (4, 5, or a SASPA_GEMM_PP flavour)
+  int ksplit;
+};
 
-// Recommended K-split of a problem (1 = none): the caller sizes the fp32 workspace (ksplit*M*N floats) from it.
-extern "C" int saspa_gemm_suggest_ksplit(const SaspaGemmParams* pp) {
-  if (!pp) return 1;
-  const SaspaGemmParams& p = *pp;
-  if (p.M <= 0 || p.N <= 0 || p.K <= 0 || (long long)p.nb1 * p.nb2 > 1 || p.N % 4 || p.act == SASPA_ACT_GEGLU) return 1;
-  const int bk = p.dtype == SASPA_BF16 ? 64 : 32;
-  const int ktiles = (p.K + bk - 1) / bk;
-  static const bool wide_ks = !(getenv("SASPA_GEMM_WIDE_SPLITK") && atoi(getenv("SASPA_GEMM_WIDE_SPLITK")) == 0);       // A/B knob
-  {
-    // exactly one wave of 128-row tiles on a pointwise layer: the wave-specialised kernel without K slices beats the 8-wave
-    // kernel on K slices (feed-forward output projection of the 16x16 level, (4096, 1280, 5120): 52 vs 76 us, and no slabs)
-    static const bool ws_on = !(getenv("SASPA_GEMM_WS") && atoi(getenv("SASPA_GEMM_WS")) == 0) &&
-                              !(getenv("SASPA_GEMM_WS_NOSPLIT") && atoi(getenv("SASPA_GEMM_WS_NOSPLIT")) == 0);   // A/B knobs
-    static const int ws_max = getenv("SASPA_GEMM_WS_MAXTILES") ? atoi(getenv("SASPA_GEMM_WS_MAXTILES")) : 512;
-    const int bn_t = (p.N % 160 == 0) ? 160 : 128;
-    const long long t128 = (long long)((p.M + 127) / 128) * ((p.N + bn_t - 1) / bn_t);
-    // (not with a twin launch beside a long-K layer: there two K slices on the 8-wave kernel win, pair times 124 vs 146 us at
-    // (4096, 1280, 5120) + residual, tools/twin_sweep.py)
-    if (ws_on && !(p.sharing && p.K >= 4096) && !p.gn_stats && p.dtype == SASPA_BF16 && p.variant == SASPA_GEMM_AUTO && p.kh == 1 && p.kw == 1 &&
-        t128 >= 256 && t128 < ws_max && ws_round_ok(t128) && saspa_gemm_ws_eligible(p))
-      return 1;
-  }
-  if (wide_ks && p.dtype == SASPA_BF16 && p.K >= 4096 && saspa_gemm_pp_eligible(p)) {
-    const int fn = (p.N % 320 == 0) ? 5 : (p.N % 256 == 0) ? 4 : 0;
-    if (fn) {
-      const long long t = (long long)((p.M + 255) / 256) * (p.N / (64 * fn));
-      static const bool model = !(getenv("SASPA_GEMM_KSPLIT_MODEL") && atoi(getenv("SASPA_GEMM_KSPLIT_MODEL")) == 0);   // A/B knob
-      if (!model) {
-        if (t >= 192) return 1;                     // the wide kernel fills the chip without slicing K
-        if (t >= 24) {
-          int ks = (int)((256 + t / 2) / t);        // about one workgroup per CU
-          ks = ks < 2 ? 2 : (ks > 8 ? 8 : ks);
-          while (ks > 1 && ktiles / ks < 8) --ks;
-          if (ks > 1) return ks;
-        }
-      } else if (t >= 24) {
-        // rounds x slice length + reduce: pp_choose_ksplit; a single slice is taken on the wide kernel too when it leaves at
-        // least half the CUs busy (dispatch() applies the same rule).  With a twin launch beside it (sharing) the launch
-        // counts on half the chip: 128 tiles need no slices, 64 tiles two instead of four
-        const int ks = pp_choose_ksplit(t, ktiles, (long long)p.M * p.N, fn, p.sharing ? 128 : 256);
-        // one slice only where dispatch() really takes the wide kernel un-split (kTwinWholeRound tiles with a twin, 128 alone);
-        // below that a one-slice answer would land on the 4-wave tiles un-split (round-4 advisor finding): fall through
-        if (ks > 1 || t >= (p.sharing ? kTwinWholeRound : 128)) return ks;
-      }
-    }
-  }
-  // 4-wave tiles: enough K slices to give the 256 CUs about two workgroups each, for the deep levels only
-  const int bn = (p.N % 160 == 0) ? 160 : 128;
-  const long long tiles = (long long)((p.M + 127) / 128) * ((p.N + bn - 1) / bn);
-  if (p.N <= 64 || tiles >= 512 || ktiles < 32) return 1;
-  long long ks = (512 + tiles - 1) / tiles;
-  if (ks > 8) ks = 8;
-  if (ks > ktiles / 8) ks = ktiles / 8;
-  return ks < 1 ? 1 : (int)ks;
-}
-
-// Tile order of a launch: 0 = M-partitioned (an XCD walks whole rows of N tiles: its activations stay in L2, the weights
-// stream through once per row block) or n = nbn / 8 > 0 = N-partitioned (an XCD owns an eighth of the N tiles for every row
-// block: its weight slice stays in L2, the activations stream through once per XCD).  Estimated beyond-L2 bytes decide;
-// profiles/r2_pmc_per_shape.txt has the measured ones (GEGLU projection at M = 16 384: 684 MB fetched for 28 MB of operands
-// with the M-partitioned order).  SASPA_GEMM_NPART=0 turns it off (A/B knob).
-int saspa_gemm_npart8(const SaspaGemmParams& p, int BM, int BN, int G, int tiles) {
-  static const bool off = getenv("SASPA_GEMM_NPART") && atoi(getenv("SASPA_GEMM_NPART")) == 0;
-  const int nbn = (p.N + BN - 1) / BN, nbm = (p.M + BM - 1) / BM;
-  if (off || (long long)p.nb1 * p.nb2 != 1 || (nbn & 7) || (G & 7) || G <= 0 || tiles % G || p.N % BN) return 0;
-  const double esz = p.dtype == SASPA_BF16 ? 2.0 : 4.0;
-  const double a = (double)p.batch * p.hin * p.win * (p.c0 + p.c1) * esz;     // the input tensor (taps re-read from L2)
-  const double w = (double)p.N * p.K * esz;
-  static const double l2mb = getenv("SASPA_GEMM_NPART_L2MB") ? atof(getenv("SASPA_GEMM_NPART_L2MB")) : 3.8;   // of the 4 MiB per XCD
-  const double l2 = l2mb * (1 << 20);
-  const double g8 = G / 8.0;
-  const double mpart = a * (nbn > g8 ? nbn / g8 : 1.0) + w * (w <= l2 ? 8.0 : (double)nbm);
-  const double npart = 8.0 * a + w * (w / 8.0 <= l2 ? 1.0 : (double)nbm);
-  return npart < 0.75 * mpart ? nbn / 8 : 0;
-}
-
-int saspa_gemm_splitk_reduce(const SaspaGemmParams& p, hipStream_t s, int ksplit) {
-  if (p.defer_reduce) return 0;      // ABI 18: the slabs go to saspa_splitk_groupnorm
-  if (p.gn_stats) {        // saspa_gemm checked: bf16, N % 160 == 0, 160 % gn_unit == 0
-    hipLaunchKernelGGL(splitk_reduce_stats_kernel, dim3((p.M + 127) / 128, p.N / 80), dim3(256), 0, s, p, ksplit);
-    SASPA_CHECK_LAUNCH();
-    return 0;
-  }
-  long long blocks = ((long long)p.M * (p.N / 4) + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  if (p.dtype == SASPA_BF16) hipLaunchKernelGGL((splitk_reduce_kernel<bf16_t>), dim3((unsigned)blocks), dim3(256), 0, s, p, ksplit);
-  else hipLaunchKernelGGL((splitk_reduce_kernel<float>), dim3((unsigned)blocks), dim3(256), 0, s, p, ksplit);
-  SASPA_CHECK_LAUNCH();
+// the 4-wave tiles (and the 8-wave 256x160 one): chunk-major K, pre-split weights and the 8-wave tile need the DMA loaders
+int plan_tiled(const SaspaGemmParams& p, int tile, int ksplit, GemmPlan& g) {
+  const bool dma = dma_loader_ok(p);
+  if ((p.korder == SASPA_KORDER_CHUNK || p.w_split || tile == 845) && !dma) return SASPA_ERANGE;
+  g = {SASPA_GEMM_TILED, tile, ksplit};
   return 0;
 }
 
-/* ABI 20: which kernel family saspa_gemm would run `p` on, and on how many K slices -- the dispatch itself, executed dry (nothing is
- * launched).  Returns family | (ksplit << 8) with family = SASPA_GEMM_TILED / WIDE / WS / AS, or the SASPA_E* code saspa_gemm would
- * return.  bench.py attributes every recorded launch to its kernel with this (roofline.by_kernel / roofline.dominant). */
-extern "C" int saspa_gemm_which(const SaspaGemmParams* pp) {
-  SaspaDryRun* st = saspa_dry_state();
-  *st = {true, 0, 1};
-  const int rc = saspa_gemm(pp, nullptr);
-  const SaspaDryRun d = *st;
-  *st = {false, 0, 0};
-  if (rc != 0) return rc;
-  return d.family | (d.ksplit << 8);
+// p: validated by check_gemm
+int plan_gemm(const SaspaGemmParams& p, GemmPlan& g) {
+  const bool bf16 = p.dtype == SASPA_BF16;
+  const long long nb = (long long)p.nb1 * p.nb2;
+  const bool pp_ok = nb == 1 && saspa_gemm_pp_eligible(p);     // bf16 only
+  const bool ws_ok = saspa_gemm_ws_eligible(p);                // bf16, unbatched only
+  const bool n160 = (p.N % 160) == 0;
+  auto pick = [&](int family, int tile, int ksplit) { g = {family, tile, ksplit}; return 0; };
+  // the A-stationary kernel writes no K slices
+  if (bf16 && p.variant == SASPA_GEMM_AS) return !p.defer_reduce && saspa_gemm_as_ok(p) ? pick(SASPA_GEMM_AS, 0, 1) : SASPA_ERANGE;
+  if (bf16 && as_auto(p)) return pick(SASPA_GEMM_AS, 0, 1);
+  if (p.ln_gamma || p.out_t || p.variant == SASPA_GEMM_AS) return SASPA_ERANGE;
+  const int ksplit = (p.workspace && p.ksplit > 1 && nb == 1 && p.N % 4 == 0) ? p.ksplit : 1;
+  // ABI 18 deferred reduce: the caller's saspa_splitk_groupnorm sums exactly p.ksplit slabs.  A launch that ended on ONE slice (or
+  // on a kernel that writes no slabs) would leave the workspace uninitialised: every rule below that drops the K split is closed
+  // to such a call, and a call that cannot be split at all is refused here.
+  const bool must_split = p.defer_reduce != 0;
+  if (must_split && (ksplit <= 1 || p.act == SASPA_ACT_GEGLU || p.N <= 32 || p.variant == SASPA_GEMM_WS)) return SASPA_ERANGE;
+  if (p.gn_stats) {
+    // statistics need the LDS-staged bf16 epilogue on 160 / 320-column tiles of 128 / 256 rows (check_gemm checked the shape):
+    // the wide kernel where AUTO would take it, the 4-wave 128x160 tiles otherwise -- never the wave-specialised kernel (its
+    // epilogue waves have no statistics pass) or the 64x64 tiles
+    if (p.variant == SASPA_GEMM_WS) return SASPA_ERANGE;
+    const bool can = pp_ok && (p.N % 320) == 0;
+    if (p.variant == SASPA_GEMM_WIDE) return can ? pick(SASPA_GEMM_WIDE, 5, ksplit) : SASPA_ERANGE;
+    if (can && pins().pp != 0 && p.variant == SASPA_GEMM_AUTO)
+      if (const int ks = wide_auto(p, wide_tiles(p, 5), ksplit, must_split, true)) return pick(SASPA_GEMM_WIDE, 5, ks);
+    return plan_tiled(p, 45, ksplit, g);
+  }
+  if (p.variant == SASPA_GEMM_WS) return ws_ok ? pick(SASPA_GEMM_WS, 0, 1) : SASPA_ERANGE;
+  if (p.act == SASPA_ACT_GEGLU) {
+    // (check_gemm: bf16, whole tiles)
+    if (p.variant == SASPA_GEMM_AUTO && nb == 1 && tiles128(p) >= kCUs && p.K <= kWsGegluKMax && ws_ok) return pick(SASPA_GEMM_WS, 0, 1);
+    // long K and enough wide tiles (116 vs 142 us at (4096, 10240, 1280); the level-1 projection (16384, 5120, 640) 117 vs 137-139)
+    const bool wide = p.variant == SASPA_GEMM_WIDE ||
+                      (p.variant == SASPA_GEMM_AUTO && p.K >= kWideKMin && (long long)((p.M + 255) / 256) * (p.N / 320) >= kWideGegluTiles);
+    if (wide && pp_ok) return pick(SASPA_GEMM_WIDE, 5, 1);
+    if (p.variant == SASPA_GEMM_WIDE) return SASPA_ERANGE;
+    return plan_tiled(p, n160 ? 45 : 44, 1, g);
+  }
+  if (pins().tile) return plan_tiled(p, pins().tile, ksplit, g);
+  if (p.N <= 32) return plan_tiled(p, 41, 1, g);
+  if (p.variant == SASPA_GEMM_WIDE) {
+    if (!pp_ok) return SASPA_ERANGE;
+    return pick(SASPA_GEMM_WIDE, (p.N % 320 == 0 || p.N % 256 != 0) ? 5 : 4, ksplit);
+  }
+  if (pp_ok && pins().pp >= 4) return pick(SASPA_GEMM_WIDE, pins().pp, ksplit);
+  const int fn = wide_fn(p);
+  if (pp_ok && fn && pins().pp == 1 && p.variant == SASPA_GEMM_AUTO)
+    if (const int ks = wide_auto(p, wide_tiles(p, fn), ksplit, must_split, false)) return pick(SASPA_GEMM_WIDE, fn, ks);
+  if (p.variant == SASPA_GEMM_AUTO && ksplit == 1 && ws_ok && ws_one_round(tiles128(p))) return pick(SASPA_GEMM_WS, 0, 1);
+  if (tiles128(p) * nb * ksplit >= 160 && p.N > 64) return plan_tiled(p, n160 ? 45 : 44, ksplit, g);
+  return plan_tiled(p, 22, ksplit, g);
 }
 
-extern "C" int saspa_gemm(const SaspaGemmParams* pp, void* stream) {
+template <typename T>
+int launch_tiled(const SaspaGemmParams& p, hipStream_t s, const GemmPlan& g) {
+  switch (g.tile) {
+    case 845: return launch<T, 4, 5, 4, 2>(p, s, g.ksplit);   // 256x160, 8 waves
+    case 45: return launch<T, 4, 5>(p, s, g.ksplit);
+    case 44: return launch<T, 4, 4>(p, s, g.ksplit);
+    case 25: return launch<T, 2, 5>(p, s, g.ksplit);
+    case 24: return launch<T, 2, 4>(p, s, g.ksplit);
+    case 22: return launch<T, 2, 2>(p, s, g.ksplit);
+    case 41: return launch<T, 4, 1>(p, s, g.ksplit);
+  }
+  return SASPA_ERANGE;
+}
+
+// Argument validation shared by saspa_gemm and saspa_gemm_which: p = *pp with the defaults filled in (nb1 / nb2, ksplit of GEGLU)
+int check_gemm(const SaspaGemmParams* pp, SaspaGemmParams& p) {
   if (!pp) return SASPA_EINVAL;
-  SaspaGemmParams p = *pp;
+  p = *pp;
   if (p.nb1 <= 0) p.nb1 = 1;
   if (p.nb2 <= 0) p.nb2 = 1;
   if (!p.a0 || !p.w || !p.out) return SASPA_EINVAL;
@@ -1345,7 +1219,7 @@ extern "C" int saspa_gemm(const SaspaGemmParams* pp, void* stream) {
   if (p.lda0 < p.c0 || (p.c1 > 0 && p.lda1 < p.c1) || p.ldw < p.K) return SASPA_ERANGE;
   if (p.act != SASPA_ACT_GEGLU && p.ldo < (p.out_t ? p.n_split : p.N)) return SASPA_ERANGE;
   if (p.ln_gamma && !p.ln_beta) return SASPA_EINVAL;
-  if (p.out_t) {      // transposed tail columns (ABI 13): geometry is checked here, eligibility of the kernel in dispatch()
+  if (p.out_t) {      // transposed tail columns (ABI 13): geometry is checked here, eligibility of the kernel in plan_gemm()
     if (p.n_split < 0 || p.n_split > p.N || p.rows_per_batch <= 0 || p.M % p.rows_per_batch || p.ldt < p.rows_per_batch) return SASPA_ERANGE;
     if (p.M / p.rows_per_batch > 1 && p.st < (long long)(p.N - p.n_split) * p.ldt) return SASPA_ERANGE;
     if ((reinterpret_cast<uintptr_t>(p.out_t) & 1u)) return SASPA_EALIGN;
@@ -1356,6 +1230,7 @@ extern "C" int saspa_gemm(const SaspaGemmParams* pp, void* stream) {
     if ((p.hout - 1) * p.stride - p.pad >= hv || (p.wout - 1) * p.stride - p.pad >= wv) return SASPA_ERANGE;
   }
   if ((long long)p.batch * p.hin * p.win >= (1ll << 31)) return SASPA_ERANGE;
+  const int bk = p.dtype == SASPA_BF16 ? 64 : 32;
   {
     // buffer loads address every operand with 32-bit byte offsets below 2 GiB
     const long long esz = p.dtype == SASPA_BF16 ? 2 : 4;
@@ -1365,16 +1240,12 @@ extern "C" int saspa_gemm(const SaspaGemmParams* pp, void* stream) {
     if (a0b >= (1ll << 31) || a1b >= (1ll << 31) || wb >= (1ll << 31)) return SASPA_ERANGE;
     // the tap-validity bitmask of the fast loaders (a K-tile inside one tap) holds 31 taps; larger windows (the 7x7 stem of
     // the filter stage's ResNet, 3 -> 8 padded channels) run on the generic per-lane loader, which has no mask
-    const int bk = p.dtype == SASPA_BF16 ? 64 : 32;
     const bool fastpath = ((p.c0 + p.c1) % bk) == 0 && (p.c1 == 0 || (p.c0 % bk) == 0);
     if (p.kh * p.kw > 31 && fastpath) return SASPA_ERANGE;
   }
   if (p.ksplit < 0 || p.ksplit > 64) return SASPA_ERANGE;
   if (p.korder != SASPA_KORDER_TAP && p.korder != SASPA_KORDER_CHUNK) return SASPA_EINVAL;
-  if (KORDER_ON && p.korder == SASPA_KORDER_CHUNK) {
-    const int bk = p.dtype == SASPA_BF16 ? 64 : 32;
-    if (p.c0 % bk || p.c1 % bk) return SASPA_ERANGE;
-  }
+  if (p.korder == SASPA_KORDER_CHUNK && (p.c0 % bk || p.c1 % bk)) return SASPA_ERANGE;
   if (p.variant < SASPA_GEMM_AUTO || p.variant > SASPA_GEMM_AS) return SASPA_EINVAL;
   if (p.act == SASPA_ACT_GEGLU) {
     // fused GEGLU: bf16 only, whole tiles, weights pre-interleaved per tile (see header)
@@ -1391,8 +1262,104 @@ extern "C" int saspa_gemm(const SaspaGemmParams* pp, void* stream) {
     if (p.gn_unit < 2 || p.gn_unit > 16 || (p.gn_unit & 1) || (80 % p.gn_unit) != 0 || (p.N % 160) != 0) return SASPA_ERANGE;
     if ((p.ldo % 8) != 0 || (p.residual && (p.ldr % 8) != 0)) return SASPA_ERANGE;
   }
+  // pre-split weights (ABI 20): only the SASPA_F32X3 DMA loop reads them
+  if (p.w_split && p.dtype != SASPA_F32X3) return SASPA_ERANGE;
+  return 0;
+}
+
+}  // namespace
+
+// Recommended K-split of a problem (1 = none): the caller sizes the fp32 workspace (ksplit*M*N floats) from it.
+extern "C" int saspa_gemm_suggest_ksplit(const SaspaGemmParams* pp) {
+  if (!pp) return 1;
+  const SaspaGemmParams& p = *pp;
+  if (p.M <= 0 || p.N <= 0 || p.K <= 0 || (long long)p.nb1 * p.nb2 > 1 || p.N % 4 || p.act == SASPA_ACT_GEGLU) return 1;
+  const int bk = p.dtype == SASPA_BF16 ? 64 : 32;
+  const int ktiles = (p.K + bk - 1) / bk;
+  // one round of 128-row tiles on a pointwise layer: the wave-specialised kernel without K slices beats the wide kernel on K slices
+  // ((4096, 1280, 5120): 52 vs 76 us, and no slabs) -- not beside a twin launch with long K, where two slices on the wide kernel
+  // win (pair times 124 vs 146 us at (4096, 1280, 5120) + residual, tools/twin_sweep.py)
+  if (!(p.sharing && p.K >= kLongK) && !p.gn_stats && p.dtype == SASPA_BF16 && p.variant == SASPA_GEMM_AUTO && p.kh == 1 && p.kw == 1 &&
+      ws_one_round(tiles128(p)) && saspa_gemm_ws_eligible(p))
+    return 1;
+  const int fn = wide_fn(p);
+  if (p.dtype == SASPA_BF16 && p.K >= kLongK && fn && saspa_gemm_pp_eligible(p)) {
+    const long long t = wide_tiles(p, fn);
+    if (t >= kWideSplitMinTiles) {
+      // a twin launch beside it (sharing) counts on half the chip; one slice only where plan_gemm really takes the wide kernel
+      // un-split -- below that a one-slice answer would land on the 4-wave tiles un-split: fall through
+      const int ks = pp_choose_ksplit(t, ktiles, (long long)p.M * p.N, fn, p.sharing ? kCUs / 2 : kCUs);
+      if (ks > 1 || wide_auto(p, t, 1, false, false)) return ks;
+    }
+  }
+  // 4-wave tiles: enough K slices to give the CUs about two workgroups each, for the deep levels only
+  const long long tiles = tiles128(p);
+  if (p.N <= 64 || tiles >= 2 * kCUs || ktiles < 32) return 1;
+  long long ks = (2 * kCUs + tiles - 1) / tiles;
+  if (ks > 8) ks = 8;
+  if (ks > ktiles / 8) ks = ktiles / 8;
+  return ks < 1 ? 1 : (int)ks;
+}
+
+extern "C" int saspa_gemm_as_auto(const SaspaGemmParams* pp) { return pp && as_auto(*pp) ? 1 : 0; }
+
+// Tile order of a launch: 0 = M-partitioned (an XCD walks whole rows of N tiles: its activations stay in L2, the weights
+// stream through once per row block) or n = nbn / 8 > 0 = N-partitioned (an XCD owns an eighth of the N tiles for every row
+// block: its weight slice stays in L2, the activations stream through once per XCD).  Estimated beyond-L2 bytes decide;
+// profiles/r2_pmc_per_shape.txt has the measured ones (GEGLU projection at M = 16 384: 684 MB fetched for 28 MB of operands
+// with the M-partitioned order).
+int saspa_gemm_npart8(const SaspaGemmParams& p, int BM, int BN, int G, int tiles) {
+  const int nbn = (p.N + BN - 1) / BN, nbm = (p.M + BM - 1) / BM;
+  if ((long long)p.nb1 * p.nb2 != 1 || (nbn & 7) || (G & 7) || G <= 0 || tiles % G || p.N % BN) return 0;
+  const double esz = p.dtype == SASPA_BF16 ? 2.0 : 4.0;
+  const double a = (double)p.batch * p.hin * p.win * (p.c0 + p.c1) * esz;     // the input tensor (taps re-read from L2)
+  const double w = (double)p.N * p.K * esz;
+  const double l2 = 3.8 * (1 << 20);                                            // of the 4 MiB per XCD
+  const double g8 = G / 8.0;
+  const double mpart = a * (nbn > g8 ? nbn / g8 : 1.0) + w * (w <= l2 ? 8.0 : (double)nbm);
+  const double npart = 8.0 * a + w * (w / 8.0 <= l2 ? 1.0 : (double)nbm);
+  return npart < 0.75 * mpart ? nbn / 8 : 0;
+}
+
+int saspa_gemm_splitk_reduce(const SaspaGemmParams& p, hipStream_t s, int ksplit) {
+  if (p.defer_reduce) return 0;      // ABI 18: the slabs go to saspa_splitk_groupnorm
+  if (p.gn_stats) {        // saspa_gemm checked: bf16, N % 160 == 0, 160 % gn_unit == 0
+    hipLaunchKernelGGL(splitk_reduce_stats_kernel, dim3((p.M + 127) / 128, p.N / 80), dim3(256), 0, s, p, ksplit);
+    SASPA_CHECK_LAUNCH();
+    return 0;
+  }
+  long long blocks = ((long long)p.M * (p.N / 4) + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  if (p.dtype == SASPA_BF16) hipLaunchKernelGGL((splitk_reduce_kernel<bf16_t>), dim3((unsigned)blocks), dim3(256), 0, s, p, ksplit);
+  else hipLaunchKernelGGL((splitk_reduce_kernel<float>), dim3((unsigned)blocks), dim3(256), 0, s, p, ksplit);
+  SASPA_CHECK_LAUNCH();
+  return 0;
+}
+
+/* ABI 20: which kernel family saspa_gemm would run `p` on, and on how many K slices: the validation and the plan, nothing launched.
+ * Returns family | (ksplit << 8) with family = SASPA_GEMM_TILED / WIDE / WS / AS, or the SASPA_E* code saspa_gemm would return.
+ * bench.py attributes every recorded launch to its kernel with this (roofline.by_kernel / roofline.dominant). */
+extern "C" int saspa_gemm_which(const SaspaGemmParams* pp) {
+  SaspaGemmParams p;
+  GemmPlan g{};
+  int rc = check_gemm(pp, p);
+  if (rc == 0) rc = plan_gemm(p, g);
+  return rc != 0 ? rc : g.family | (g.ksplit << 8);
+}
+
+extern "C" int saspa_gemm(const SaspaGemmParams* pp, void* stream) {
+  SaspaGemmParams p;
+  GemmPlan g{};
+  int rc = check_gemm(pp, p);
+  if (rc == 0) rc = plan_gemm(p, g);
+  if (rc != 0) return rc;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (p.dtype == SASPA_BF16) return dispatch<bf16_t>(p, s);
-  if (p.dtype == SASPA_F32X3) return dispatch<f32x3_t>(p, s);
-  return dispatch<float>(p, s);
+  switch (g.family) {
+    case SASPA_GEMM_AS: return saspa_gemm_as_launch(p, s);
+    case SASPA_GEMM_WS: return saspa_gemm_ws_launch(p, s);
+    case SASPA_GEMM_WIDE: return saspa_gemm_pp_launch(p, s, g.ksplit, g.tile);
+  }
+  if (p.dtype == SASPA_BF16) return launch_tiled<bf16_t>(p, s, g);
+  if (p.dtype == SASPA_F32X3) return launch_tiled<f32x3_t>(p, s, g);
+  return launch_tiled<float>(p, s, g);
 }

@@ -20,7 +20,6 @@
 // previous slice's epilogue and the next-but-one slice's DMA pieces dealt between them take 4 200-4 500 (each vector-memory
 // instruction costs the wave 100-200 issue cycles, ten of them per step), the DMA wait 300-400, the barrier skew the rest:
 // 40-50 % of the matrix-pipe bound, i.e. the level of the 8-wave conv kernel, on layers where the tiled kernels reach 20-25 %.
-#include <cstdlib>
 
 #include "common.h"
 #include "gemm_internal.h"
@@ -31,6 +30,7 @@ constexpr int AS_K = 320;
 constexpr int AS_KS = AS_K / 16;          // MFMA K-steps
 constexpr int AS_BM = 256;                // rows per workgroup: 8 waves x 32
 constexpr int AS_BN = 64;                 // W rows (output columns) per ring slot
+constexpr int AS_MIN_BLOCKS = 192;        // fewer row blocks than this cannot fill the chip
 constexpr int AS_PITCH = 40;              // 16-byte chunks per W row in LDS; chunk kc of row n sits at kc ^ ((n >> 1) & 7): conflict-free
                                           // ds_read_b128 (rows 2 i and 2 i + 1 differ by 8 chunks = half the banks, the XOR spreads
                                           // the pairs) AND every aligned lane quad of the DMA reads one aligned 64-byte segment
@@ -459,14 +459,12 @@ __global__ __launch_bounds__(512, 1) void gemm_as_kernel(const SaspaGemmParams p
 }  // namespace
 
 bool saspa_gemm_as_ok(const SaspaGemmParams& p) {
-  static const bool on = !(getenv("SASPA_GEMM_AS") && atoi(getenv("SASPA_GEMM_AS")) == 0);      // A/B knob
-  static const int min_blocks = getenv("SASPA_GEMM_AS_MINBLOCKS") ? atoi(getenv("SASPA_GEMM_AS_MINBLOCKS")) : 192;
-  if (!on || p.dtype != SASPA_BF16) return false;
+  if (p.dtype != SASPA_BF16) return false;
   if (p.kh != 1 || p.kw != 1 || p.stride != 1 || p.pad != 0 || p.upsample || p.c1 != 0 || p.a1) return false;
   if (p.c0 != AS_K || p.K != AS_K || p.lda0 % 8 || p.ldw % 8 || p.ldw < AS_K) return false;
   if ((long long)p.nb1 * p.nb2 > 1 || (p.ksplit > 1 && p.workspace) || p.gn_stats || p.rowvec || p.alpha != 1.0f) return false;
   if (p.act != SASPA_ACT_NONE && p.act != SASPA_ACT_GEGLU) return false;
-  if (p.N % AS_BN || p.N <= 0 || (p.M + AS_BM - 1) / AS_BM < min_blocks) return false;
+  if (p.N % AS_BN || p.N <= 0 || (p.M + AS_BM - 1) / AS_BM < AS_MIN_BLOCKS) return false;
   if ((long long)p.M * (p.lda0 > p.ldo ? p.lda0 : p.ldo) * 2 >= 0x7fffffffLL) return false;   // 32-bit buffer offsets
   if (p.act == SASPA_ACT_GEGLU) {
     const int gb = (p.N % 160 == 0) ? 160 : 128;
@@ -485,14 +483,11 @@ bool saspa_gemm_as_ok(const SaspaGemmParams& p) {
 }
 
 int saspa_gemm_as_launch(const SaspaGemmParams& p, hipStream_t s) {
-  if (!saspa_gemm_as_ok(p)) return SASPA_ERANGE;
-  SASPA_DRY_RETURN(SASPA_GEMM_AS, 1);
-  // one workgroup per CU, the steps dealt evenly (see the kernel); SASPA_GEMM_BALANCE=0: one workgroup per row block as before
+  // one workgroup per CU, the steps dealt evenly (see the kernel)
   const long long nblk = (p.M + AS_BM - 1) / AS_BM, steps = nblk * (p.N / AS_BN);
-  static const bool balance_off = getenv("SASPA_GEMM_BALANCE") && atoi(getenv("SASPA_GEMM_BALANCE")) == 0;
   // few slices per block (N = 320: five): a share of 6.9 steps would reload and re-normalise its rows twice for seven slices
   // -- measured slower than letting the hardware deal whole blocks (LayerNorm + N = 320 at 352 blocks: 60 us against 53.5)
-  const bool whole_blocks = balance_off || p.N / AS_BN < 8 || nblk % 256 == 0;
+  const bool whole_blocks = p.N / AS_BN < 8 || nblk % 256 == 0;
   const dim3 grid((unsigned)(whole_blocks ? nblk : (steps < 256 ? steps : 256)));
   const int abl = 0;
   if (p.act == SASPA_ACT_GEGLU) {
@@ -507,28 +502,6 @@ int saspa_gemm_as_launch(const SaspaGemmParams& p, hipStream_t s) {
   return 0;
 }
 
-// 0: cannot run; 1: can; 2: can, and the work fills the chip evenly -- the sizes where the kernel beats the wave-specialised one
-// on the GEGLU projection too (tools/as_bench.py).  Until round 5 that meant row blocks filling whole rounds of the 256 CUs
-// (>= 85 % of the last round: 352 blocks at 512x704 did not); with the steps dealt evenly every eligible size does.
-// SASPA_GEMM_BALANCE=0 restores the old launch and the old answer.
-// THE predicate "variant AUTO runs this problem on the A-stationary kernel" (round 6: shared by dispatch() in saspa_gemm.hip and
-// by callers that decide on it before the launch -- ops.conv drops the epilogue GroupNorm statistics only where this says yes;
-// saspa_gemm_as_eligible() alone said 2 for every size since the balanced launch, while dispatch() kept its measured rule).
-// A fused LayerNorm / transposed tail exists on this kernel only; otherwise it is taken where it measured faster than the tiled /
-// wave-specialised kernels (tools/as_bench.py): whole rounds of 256-row blocks, or -- with a ragged last round (352 blocks at
-// 512x704) -- the layers with a residual or >= 640 columns, not the GEGLU projection.
-extern "C" int saspa_gemm_as_auto(const SaspaGemmParams* pp) {
-  if (!pp || pp->variant != SASPA_GEMM_AUTO || pp->defer_reduce || !saspa_gemm_as_ok(*pp)) return 0;
-  const SaspaGemmParams& p = *pp;
-  const long long blocks = (p.M + 255) / 256;
-  const bool whole = blocks * 100 >= ((blocks + 255) / 256) * 256 * 85;
-  return (p.ln_gamma || p.out_t || whole || (p.act != SASPA_ACT_GEGLU && (p.residual || p.N >= 640))) ? 1 : 0;
-}
-
-extern "C" int saspa_gemm_as_eligible(const SaspaGemmParams* p) {
-  if (!p || !saspa_gemm_as_ok(*p)) return 0;
-  static const bool balance_off = getenv("SASPA_GEMM_BALANCE") && atoi(getenv("SASPA_GEMM_BALANCE")) == 0;
-  if (!balance_off) return 2;
-  const long long blocks = (p->M + AS_BM - 1) / AS_BM;
-  return blocks * 100 >= ((blocks + 255) / 256) * 256 * 85 ? 2 : 1;
-}
+// 0: cannot run; 2: can -- with the steps dealt evenly every eligible size fills the chip (until round 5 the answer was 1 for row
+// blocks that did not fill whole rounds of the 256 CUs).  Whether AUTO takes the kernel is saspa_gemm_as_auto (saspa_gemm.hip).
+extern "C" int saspa_gemm_as_eligible(const SaspaGemmParams* p) { return p && saspa_gemm_as_ok(*p) ? 2 : 0; }

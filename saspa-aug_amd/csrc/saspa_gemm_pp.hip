@@ -39,12 +39,6 @@
 #include "common.h"
 #include "gemm_internal.h"
 
-#ifdef SASPA_NO_KORDER
-constexpr bool KORDER_ON = false;   // A/B build: the K walk exactly as before ABI v4
-#else
-constexpr bool KORDER_ON = true;
-#endif
-
 #ifndef SASPA_PP_CT_ABL
 #define SASPA_PP_CT_ABL 0
 #endif
@@ -126,7 +120,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const SaspaGemmParams p, c
 
   const int hw = p.hout * p.wout;
   const int ctot = p.c0 + p.c1;
-  const int chunk_major = (KORDER_ON && p.korder == SASPA_KORDER_CHUNK) ? 1 : 0;   // wave-uniform
+  const int chunk_major = p.korder == SASPA_KORDER_CHUNK ? 1 : 0;   // wave-uniform
   const int hv = UP ? 2 * p.hin : p.hin, wv = UP ? 2 * p.win : p.win;
   // A descriptors: for the 3x3 / pad 1 window the base is moved back by one row + one pixel so that the
   // tap offset (dy*win + dx) * pitch is a non-negative SCALAR offset (no per-lane arithmetic per tap)
@@ -264,25 +258,17 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const SaspaGemmParams p, c
     // advance to the following tile
     ++staged;
     ku += BK;
-    if (KORDER_ON) {
-      // branch-free mixed-radix step (a scalar branch in this path costs the DMA kernels ~25 %, measured): tap-major
-      // counts (c, x, y) with the channel offset fastest, chunk-major (x, y, c) with the tap fastest
-      const int cu_t = cu + BK;
-      const int wc = (cu_t >= ctot) ? 1 : 0;                        // tap-major: channel wrap carries into x
-      const int dx1 = dxu + (chunk_major ? 1 : wc);
-      const int wx = (dx1 == p.kw) ? 1 : 0;
-      const int dy1 = dyu + wx;
-      const int wy = (chunk_major && dy1 == p.kh) ? 1 : 0;          // chunk-major: tap wrap carries into the chunk
-      cu = chunk_major ? cu + (wy ? BK : 0) : (wc ? cu_t - ctot : cu_t);
-      dxu = wx ? 0 : dx1;
-      dyu = wy ? 0 : dy1;
-    } else {
-      cu += BK;
-      if (cu >= ctot) {
-        cu -= ctot;
-        if (++dxu == p.kw) { dxu = 0; ++dyu; }
-      }
-    }
+    // branch-free mixed-radix step (a scalar branch in this path costs the DMA kernels ~25 %, measured): tap-major
+    // counts (c, x, y) with the channel offset fastest, chunk-major (x, y, c) with the tap fastest
+    const int cu_t = cu + BK;
+    const int wc = (cu_t >= ctot) ? 1 : 0;                        // tap-major: channel wrap carries into x
+    const int dx1 = dxu + (chunk_major ? 1 : wc);
+    const int wx = (dx1 == p.kw) ? 1 : 0;
+    const int dy1 = dyu + wx;
+    const int wy = (chunk_major && dy1 == p.kh) ? 1 : 0;          // chunk-major: tap wrap carries into the chunk
+    cu = chunk_major ? cu + (wy ? BK : 0) : (wc ? cu_t - ctot : cu_t);
+    dxu = wx ? 0 : dx1;
+    dyu = wy ? 0 : dy1;
   };
   // LDS element (u32x4) index of the READ buffer (cur) and of the other one; swapped every K-tile
   int cur = 0, oth = STAGE;
@@ -1042,8 +1028,6 @@ bool saspa_gemm_pp_eligible(const SaspaGemmParams& p) {
 }
 
 int saspa_gemm_pp_launch(const SaspaGemmParams& p, hipStream_t s, int ksplit, int fn) {
-  if (!saspa_gemm_pp_eligible(p)) return SASPA_ERANGE;
-  SASPA_DRY_RETURN(SASPA_GEMM_WIDE, ksplit);
   // K loop flavour (read per launch; all are bit-identical: same MFMA order per accumulator):
   //   SASPA_GEMM_PP_LOOP=2 (default since round 5)  two-barrier ping-pong, TWO 40-MFMA intervals per K-tile: +2 ... +8 % on every
   //                         shape against =0 (tools/pp_ab.py, profiles/r5_pp_long_ab.txt)

@@ -567,9 +567,8 @@ def _linear_params(x2, w, bias, r2, o2, alpha, act, rowvec, variant, m, n, k):
 
 
 def linear_ln_fusable(x, w, *, act=ACT_NONE, n_out=None):
-    """Non-zero if `linear(x, w, ..., ln=...)` / `out_t=` can run: the A-stationary kernel takes the problem
-    (saspa_gemm_as_eligible: bf16, K = 320, N % 64 == 0, >= 192 blocks of 256 rows; SASPA_GEMM_AS=0 turns it off).
-    2 = whole rounds of row blocks (the kernel wins on every layer shape), 1 = a ragged last round."""
+    """Non-zero (2) if `linear(x, w, ..., ln=...)` / `out_t=` can run: the A-stationary kernel takes the problem
+    (saspa_gemm_as_eligible: bf16, K = 320, N % 64 == 0, >= 192 blocks of 256 rows).  Use it as a boolean."""
     if not x.is_cuda or x.dtype != torch.bfloat16:
         return 0
     k = x.shape[-1]

@@ -134,7 +134,7 @@ def test_qkv_one_launch(dev, b, ntok):
 
 def test_eligibility_levels(dev):
     """saspa_gemm_as_eligible: 0 = cannot, 2 = can and fills the chip (since round 5 the steps are dealt evenly, so every
-    eligible size does; 1 = "can, ragged last round" is only returned with SASPA_GEMM_BALANCE=0)."""
+    eligible size does; the value 1, "can, ragged last round", is no longer returned)."""
     w = torch.zeros(320, K, device=dev, dtype=BF)
     mk = lambda m: torch.zeros(m, K, device=dev, dtype=BF)
     assert ops.linear_ln_fusable(mk(65536), w) == 2            # 256 blocks: one whole round

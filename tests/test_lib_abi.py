@@ -2,6 +2,7 @@
 declares (no compute calls without a GPU); argument validation happens on the host before
 any launch."""
 import ctypes as C
+import json
 import os
 import re
 
@@ -139,6 +140,156 @@ def test_gemm_which_is_a_dry_dispatch():
     bad.K = 99
     assert lib.saspa_gemm_which(C.byref(bad)) == -3
     assert lib.saspa_gemm_which(None) == -1
+
+
+# ---- the GEMM dispatch table ------------------------------------------------------------------------------------------------
+# A deterministic corpus of SaspaGemmParams (the latent levels of every shipped bucket, SD-1.5 / SDXL widths, the operand options
+# the dispatch looks at) and, per row, (saspa_gemm_which, saspa_gemm_suggest_ksplit, saspa_gemm_as_auto, saspa_gemm_as_eligible),
+# compared with tests/golden/gemm_dispatch.json.  Any change of a threshold or an eligibility rule shows up as a changed row; a
+# deliberate one rewrites the golden:  PYTHONPATH=. python tests/test_lib_abi.py --write-dispatch-golden
+DISPATCH_GOLDEN = os.path.join(ROOT, "tests", "golden", "gemm_dispatch.json")
+_A0, _A1, _W, _OUT, _AUX = (1 << 20) * 1, (1 << 20) * 2, (1 << 20) * 3, (1 << 20) * 4, (1 << 20) * 5   # never dereferenced
+_LEVELS = [(64, 64), (64, 88), (64, 96), (32, 32), (32, 44), (32, 48), (16, 16), (16, 22), (16, 24), (8, 8), (8, 11), (8, 12),
+           (128, 128)]
+_SILU, _GEGLU = 1, 3
+
+
+def _gemm(b, h, w, c0, n, kh=1, c1=0, up=False, dtype=0, res=False, act=0, variant=0, sharing=0, korder=0, ks=0, defer=False,
+          gn=False, nb=(1, 1), w_split=0, ln=False, out_t=False, pad=None):
+    p = _lib.GemmParams()
+    p.dtype, p.batch, p.hout, p.wout, p.hin, p.win = dtype, b, h, w, (h // 2 if up else h), (w // 2 if up else w)
+    p.kh = p.kw = kh
+    p.stride, p.pad, p.upsample = 1, kh // 2 if pad is None else pad, int(up)
+    p.a0, p.c0, p.lda0 = _A0, c0, c0
+    if c1:
+        p.a1, p.c1, p.lda1 = _A1, c1, c1
+    p.w, p.K = _W, kh * kh * (c0 + c1)
+    p.ldw, p.N, p.M = p.K, n, b * h * w
+    p.out, p.ldo = _OUT, (n // 2 if act == _GEGLU else n)
+    p.alpha, p.act, p.variant, p.sharing, p.korder, p.w_split = 1.0, act, variant, sharing, korder, w_split
+    p.nb1, p.nb2 = nb
+    if res:
+        p.residual, p.ldr = _AUX, n
+    if gn:
+        p.gn_stats, p.gn_unit = _AUX, 10
+    if ln:
+        p.ln_gamma = p.ln_beta = _AUX
+        p.ln_eps = 1e-5
+    if out_t:
+        p.out_t, p.n_split, p.rows_per_batch = _AUX, n - 64, h * w
+        p.ldt, p.st = h * w, 64 * h * w
+    if ks:
+        p.ksplit = _lib.load().saspa_gemm_suggest_ksplit(C.byref(p)) if ks == "suggest" else ks
+        p.workspace = _AUX
+    p.defer_reduce = int(defer)
+    return p
+
+
+# the options the dispatch reads, one dict of _gemm keywords each
+_MODS = [{}, {"res": True}, {"act": _SILU}, {"act": _GEGLU}, {"act": _SILU, "res": True}, {"dtype": 1}, {"dtype": 2},
+         {"dtype": 2, "w_split": 1}, {"dtype": 1, "w_split": 1}, {"w_split": 1}, {"sharing": 1}, {"sharing": 1, "res": True},
+         {"variant": 1}, {"variant": 2}, {"variant": 3}, {"variant": 4}, {"gn": True}, {"gn": True, "ks": "suggest"},
+         {"gn": True, "ks": "suggest", "defer": True}, {"ks": "suggest"}, {"ks": 2}, {"ks": 4}, {"ks": "suggest", "defer": True},
+         {"ks": 1, "defer": True}, {"sharing": 1, "ks": "suggest"}, {"sharing": 1, "gn": True, "ks": "suggest"}, {"nb": (2, 3)},
+         {"korder": 1}, {"korder": 1, "dtype": 2, "w_split": 1}, {"ln": True}, {"out_t": True}, {"ln": True, "act": _GEGLU},
+         {"variant": 2, "gn": True}, {"variant": 3, "gn": True}, {"variant": 4, "ks": 2, "defer": True}, {"variant": 3, "act": _GEGLU},
+         {"variant": 2, "act": _GEGLU}, {"variant": 3, "ks": 2, "defer": True}, {"dtype": 1, "variant": 2}, {"dtype": 1, "variant": 3},
+         {"act": _GEGLU, "sharing": 1}, {"res": True, "ks": "suggest", "sharing": 1}, {"pad": 2}, {"pad": 2, "korder": 1}]
+
+
+def _geometries(c):
+    """(kh, c0, c1, upsample, N) of the layers of a level of width c, plus the odd shapes the dispatch special-cases."""
+    return [(1, c, 0, False, c), (1, c, 0, False, 3 * c), (1, c, 0, False, 8 * c), (1, 4 * c, 0, False, c), (1, c, 0, False, 32),
+            (1, c, 0, False, 64), (3, c, 0, False, c), (3, c, 0, False, 2 * c), (3, c, c, False, c), (3, c, c // 2, False, c),
+            (3, c, 0, True, c), (3, 8, 0, False, c), (1, c // 2, c // 2, False, c), (3, c, 0, False, 32)]
+
+
+def _boundary_rows():
+    """Linears (one image of M x 1 pixels) on both sides of every tile-count, K and row-block threshold of the policy."""
+    rows = []
+
+    def add(m, k, n, **kw):
+        rows.append(((1, m, 1, 1, k, 0, False, n, kw), _gemm(1, m, 1, k, n, **kw)))
+    for t in (23, 24, 63, 64, 95, 96, 127, 128, 143, 144, 256, 257, 332, 333):      # 256 x 320 wide tiles
+        for k in (576, 640, 896, 960, 4032, 4096):
+            for sharing in (0, 1):
+                for ks in (0, 2, "suggest"):
+                    add(256 * t, k, 320, sharing=sharing, ks=ks)
+    for t in (383, 384):                                                             # GEGLU on wide tiles
+        for k in (576, 640):
+            add(256 * t, k, 320, act=_GEGLU)
+    for m in (16256, 16384):                                                         # GEGLU: 254 / 256 tiles of 128 x 160
+        for k in (384, 448):
+            add(m, k, 320, act=_GEGLU)
+    for t in (159, 160, 255, 256, 435, 436, 511, 512):                               # 128 x 160 / 128 x 128 tiles
+        for k in (320, 1280, 1984, 2048):
+            for n in (160, 128):
+                add(128 * t, k, n)
+                add(128 * t, k, n, sharing=1)
+    for blocks in (191, 192, 217, 218, 255, 256, 435, 436):                          # A-stationary: 256-row blocks
+        for n, act, res in ((320, 0, False), (320, _GEGLU, False), (320, 0, True), (576, 0, False), (640, 0, False)):
+            add(256 * blocks, 320, n, act=act, res=res)
+    for n in (32, 40, 64, 72):                                                       # skinny N
+        add(16384, 2048, n)
+    return rows
+
+
+def dispatch_corpus():
+    """[(description, SaspaGemmParams)] in a fixed order: every (level, batch, width, geometry) plain and under one of the
+    options (cycled), every option on a core of levels at batch 16, then the thresholds' boundaries."""
+    rows = [("null", None)]
+    i = 0
+    for (h, w) in _LEVELS:
+        for b in (2, 8, 16):
+            for c in (320, 640, 1280):
+                for g in _geometries(c):
+                    for j in (0, 1 + (7 * i) % (len(_MODS) - 1)):
+                        kh, c0, c1, up, n = g
+                        rows.append(((b, h, w, kh, c0, c1, up, n, _MODS[j]), _gemm(b, h, w, c0, n, kh, c1, up, **_MODS[j])))
+                    i += 1
+    for (h, w), c in [((64, 88), 320), ((32, 44), 640), ((8, 12), 1280)]:
+        for kh, c0, c1, up, n in _geometries(c):
+            for j in range(1, len(_MODS)):
+                rows.append(((16, h, w, kh, c0, c1, up, n, _MODS[j]), _gemm(16, h, w, c0, n, kh, c1, up, **_MODS[j])))
+    return rows + _boundary_rows()
+
+
+def dispatch_table(lib):
+    table = []
+    for _, p in dispatch_corpus():
+        q = None if p is None else C.byref(p)
+        table.append([lib.saspa_gemm_which(q), lib.saspa_gemm_suggest_ksplit(q), lib.saspa_gemm_as_auto(q), lib.saspa_gemm_as_eligible(q)])
+    return table
+
+
+def _decode(row):
+    fam = {1: "TILED", 2: "WIDE", 3: "WS", 4: "AS"}
+    w = row[0]
+    which = _lib.ERRORS.get(w, str(w)).split()[0] if w < 0 else f"{fam.get(w & 0xff, w & 0xff)} x{w >> 8}"
+    return f"which {which}, suggest_ksplit {row[1]}, as_auto {row[2]}, as_eligible {row[3]}"
+
+
+def test_gemm_dispatch_table():
+    """The dispatch of the GEMM family, decision for decision, against the recorded table (no GPU: the dry dispatch)."""
+    lib = _lib.load()
+    got = dispatch_table(lib)
+    with open(DISPATCH_GOLDEN) as f:
+        want = json.load(f)
+    assert len(got) == len(want), (len(got), len(want))
+    keys = [k for k, _ in dispatch_corpus()]
+    bad = [i for i in range(len(want)) if got[i] != want[i]]
+    msg = "\n".join(f"row {i} (b, h, w, kh, c0, c1, up, N, options) = {keys[i]}:\n  got  {_decode(got[i])}\n  want {_decode(want[i])}"
+                    for i in bad[:8])
+    assert not bad, f"{len(bad)} of {len(want)} dispatch decisions changed:\n{msg}"
+
+
+if __name__ == "__main__":
+    import sys
+    if sys.argv[1:] == ["--write-dispatch-golden"]:
+        rows = dispatch_table(_lib.load())
+        with open(DISPATCH_GOLDEN, "w") as f:
+            f.write("[\n" + ",\n".join(json.dumps(r, separators=(",", ":")) for r in rows) + "\n]\n")
+        print(f"{DISPATCH_GOLDEN}: {len(rows)} rows")
 
 
 def test_ff_block_host_side_validation():

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Same-box A/B at the DRIVER's bench command (`bench.py --gpus 1 --steps 20 --warmup 5`): the round-4 final tree
 # (`git archive 0da8daf` extracted to _ab/r4 and built there) against this tree, alternating, then this tree with the
-# round-5 defaults switched back one at a time (SASPA_GEMM_PP_LOOP=0, SASPA_GEMM_BALANCE=0).  `--no-cpu-baseline`: the
+# round-5 K loop of the 8-wave kernel switched back (SASPA_GEMM_PP_LOOP=0).  `--no-cpu-baseline`: the
 # CPU leg is outside the timed region and only costs box time.
 # usage: tools/driver_cmd_ab.sh [alternations = 3] [knobs = 1]   -> gpurun_out/r6_ab/*.json + summary.txt
 set -u
@@ -29,7 +29,6 @@ for i in $(seq 1 $N); do
 done
 if [ "$KNOBS" = "1" ]; then
   run r5_pploop0 . SASPA_GEMM_PP_LOOP=0
-  run r5_balance0 . SASPA_GEMM_BALANCE=0
   run r5_again . X=1
 fi
 cat $OUT/summary.txt

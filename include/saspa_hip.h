@@ -461,6 +461,41 @@ int saspa_gemm_fp8(const SaspaGemmF8Params* p, void* stream);
 int saspa_layernorm_quant_fp8(const void* x, int ldx, void* q, int ldq, float* scale, long long rows, int C,
                               const float* gamma, const float* beta, float eps, void* stream);
 
+/* ---- MX-fp8 3x3 convolutions (block-scaled e4m3; opt-in fp8 conv path of ResnetBlock2D conv1 / conv2) --
+ * saspa_groupnorm_quant_mxfp8: GroupNorm(+SiLU) exactly as saspa_groupnorm_apply takes it (one or two bf16 sources, statistics from
+ *   the producers' epilogues or from saspa_groupnorm_stats, act NONE / SILU; p->y is not read), quantised instead of stored:
+ *   y = act((x - mean) * rstd * gamma + beta) in fp32 (the apply pass's arithmetic); for every pixel and block of 32 consecutive
+ *   channels, e = the smallest integer with max|y| <= 448 * 2^e, clamped to [-127, 127] (0 for an all-zero block);
+ *   qs[pixel][block] = e + 127 (E8M0), q[pixel][c] = e4m3fn(y * 2^-e) rounded to nearest even (cannot saturate).
+ *   q: uint8 [batch * hw][C] at pitch ldq bytes (% 16), qs: uint8 [batch * hw][C / 32] at pitch ldqs.  bf16, C = c0 + c1,
+ *   C % 32 == 0, C <= 4096; SASPA_ERANGE / SASPA_EALIGN otherwise.  Deterministic, no atomics; an image's bytes depend on it alone.
+ * saspa_conv3x3_mxfp8: 3x3 / stride 1 / pad 1 conv of ONE such (q, qs) source with e4m3 weights w8 [N][ldw] (K = tap * C + c as
+ *   weights.pack_conv orders it, zero padded to Kp = 9 C rounded up to a multiple of 128) and per-output-channel fp32 scales sw [N]:
+ *   out[m][n] = bf16(sw[n] * sum_k 2^(qs - 127) q[m][k] w8[n][k] + bias[n] + rowvec[b(m)][n]) + residual[m][n]   (bf16 out /
+ *   residual, the exponent of the (pixel, tap, block) a k belongs to applied inside v_mfma_scale_f32_16x16x128_f8f6f4; taps
+ *   outside the image contribute zero).  gn_stats / gn_unit: exactly SaspaGemmParams.gn_stats (160-column tiles).
+ *   C % 32 == 0, N % 160 == 0, any M (row tail masked), kh = kw = 3, stride 1, pad 1, no upsampling -- SASPA_ERANGE otherwise;
+ *   16-byte aligned operands, ldq / ldw % 16, ldo / ldr % 8 -- SASPA_EALIGN otherwise.  No split-K.
+ * saspa_conv3x3_mxfp8_eligible: non-zero if the shapes, pitches and the alignment of the pointers given are accepted. */
+typedef struct SaspaConvMxParams {
+  const void* q; int ldq;        /* e4m3 activations [batch * h * w][C], pitch in bytes */
+  const void* qs; int ldqs;      /* E8M0 block exponents [batch * h * w][C / 32], pitch in bytes */
+  int batch, h, w, C;            /* input extent = output extent */
+  int kh, kw, stride, pad;       /* must be 3, 3, 1, 1 */
+  int upsample;                  /* must be 0 */
+  const void* w8; int ldw;       /* e4m3 weights [N][ldw] */
+  int N, Kp;
+  const float* sw;               /* [N] */
+  const float* bias;             /* [N] or NULL */
+  const float* rowvec; int ldrv; /* [batch or 1][N] or NULL (time-embedding projection) */
+  const void* residual; int ldr; /* bf16 [M][ldr] or NULL */
+  void* out; int ldo;            /* bf16 [M][ldo] */
+  float* gn_stats; int gn_unit;
+} SaspaConvMxParams;
+int saspa_groupnorm_quant_mxfp8(const SaspaGroupNormParams* p, void* q, int ldq, void* qs, int ldqs, void* stream);
+int saspa_conv3x3_mxfp8_eligible(const SaspaConvMxParams* p);
+int saspa_conv3x3_mxfp8(const SaspaConvMxParams* p, void* stream);
+
 /* ---- HED annotator head (run_aug/run_aug.py:311-312, :438-439 -> controlnet_aux HEDdetector.__call__) -------
  * The network's conv stack runs as saspa_gemm / saspa_pool2d launches; this is what follows it: side output k
  * ([n][mh][mw] fp32 samples at element pitch ld -- channel 0 of a channel-padded NHWC tensor) is resized to H x W like

@@ -76,6 +76,18 @@ class GemmF8Params(C.Structure):
     ]
 
 
+class ConvMxParams(C.Structure):
+    _fields_ = [
+        ("q", C.c_void_p), ("ldq", C.c_int), ("qs", C.c_void_p), ("ldqs", C.c_int),
+        ("batch", C.c_int), ("h", C.c_int), ("w", C.c_int), ("C", C.c_int),
+        ("kh", C.c_int), ("kw", C.c_int), ("stride", C.c_int), ("pad", C.c_int), ("upsample", C.c_int),
+        ("w8", C.c_void_p), ("ldw", C.c_int), ("N", C.c_int), ("Kp", C.c_int),
+        ("sw", C.c_void_p), ("bias", C.c_void_p), ("rowvec", C.c_void_p), ("ldrv", C.c_int),
+        ("residual", C.c_void_p), ("ldr", C.c_int), ("out", C.c_void_p), ("ldo", C.c_int),
+        ("gn_stats", C.c_void_p), ("gn_unit", C.c_int),
+    ]
+
+
 class FfBlockParams(C.Structure):
     _fields_ = [
         ("x", C.c_void_p), ("ldx", C.c_int), ("residual", C.c_void_p), ("ldr", C.c_int), ("M", C.c_longlong), ("F", C.c_int),
@@ -145,6 +157,9 @@ SYMBOLS = {
     "saspa_conv3x3_halo_eligible": (_I, [C.POINTER(GemmParams), C.POINTER(ConvGnParams)]),
     "saspa_conv3x3_halo_ksplit": (_I, [C.POINTER(GemmParams), _I]),
     "saspa_conv3x3_halo": (_I, [C.POINTER(GemmParams), C.POINTER(ConvGnParams), _P]),
+    "saspa_groupnorm_quant_mxfp8": (_I, [C.POINTER(GroupNormParams), _P, _I, _P, _I, _P]),
+    "saspa_conv3x3_mxfp8_eligible": (_I, [C.POINTER(ConvMxParams)]),
+    "saspa_conv3x3_mxfp8": (_I, [C.POINTER(ConvMxParams), _P]),
     "saspa_abi_version": (_I, []),
     "saspa_build_arch": (C.c_char_p, []),
 }

@@ -103,17 +103,11 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const SaspaGroupNormPar
   }
 }
 
-// ---- stage 2: y = act(x * scale[b][c] + shift[b][c]) -----------------------------------------
-// grid = (nblk, batch, slabs), the block's pixels are [blockIdx.x * ppb, +ppb).  Prologue: the 32 (groups) x nsplit x slabs
-// partial sums of image b -> mean / rstd per group (fp64 combine, 8 threads per group), then each thread derives
-// scale / shift of its own 8 channels once; the main loop is a pure stream.
-template <typename T>
-__global__ __launch_bounds__(256) void gn_apply_kernel(const SaspaGroupNormParams p, int cxw, int slabs, int ppb) {
-  __shared__ float2 stat[256];
+// The prologue: mean / rstd of every group of image b -> stat[group] (shared with the MX-fp8 quantiser below, so both form the
+// same statistics).  Ends with a workgroup barrier.
+__device__ __forceinline__ void gn_image_stats(const SaspaGroupNormParams& p, int slabs, int b, float2* stat) {
   const int tid = threadIdx.x;
-  const int b = blockIdx.y;
   const int C = p.c0 + p.c1;
-  const int C8 = C >> 3;
   const int cpg = C / p.groups;
   {
     const int sub = tid & 7;
@@ -187,6 +181,21 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const SaspaGroupNormParam
     }
   }
   __syncthreads();
+}
+
+// ---- stage 2: y = act(x * scale[b][c] + shift[b][c]) -----------------------------------------
+// grid = (nblk, batch, slabs), the block's pixels are [blockIdx.x * ppb, +ppb).  Prologue: the 32 (groups) x nsplit x slabs
+// partial sums of image b -> mean / rstd per group (fp64 combine, 8 threads per group), then each thread derives
+// scale / shift of its own 8 channels once; the main loop is a pure stream.
+template <typename T>
+__global__ __launch_bounds__(256) void gn_apply_kernel(const SaspaGroupNormParams p, int cxw, int slabs, int ppb) {
+  __shared__ float2 stat[256];
+  const int tid = threadIdx.x;
+  const int b = blockIdx.y;
+  const int C = p.c0 + p.c1;
+  const int C8 = C >> 3;
+  const int cpg = C / p.groups;
+  gn_image_stats(p, slabs, b, stat);
   const int rows = 256 / cxw;
   if (tid >= rows * cxw) return;
   const int cx = tid % cxw, py = tid / cxw;
@@ -263,6 +272,102 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const SaspaGroupNormParam
     }
   }
   for (; px < pend; px += rows) one(px);
+}
+
+// ---- GroupNorm(+SiLU) quantised to MX-fp8 (saspa_groupnorm_quant_mxfp8) ---------------------------------------------------
+// grid = (nblk, batch), the block's items are [blockIdx.x * ipb, +ipb) of image b's hw x C/8 chunks in pixel-major order.  The
+// apply pass's prologue (the same mean / rstd per group), then scale / shift of every channel into LDS; one chunk of 8 channels
+// per lane and item, so 4 consecutive lanes hold one 32-channel block of one pixel (C % 32 == 0, ipb % 4 == 0) and the block
+// maximum is two lane exchanges.  y is quantised from fp32, never rounded to bf16.
+constexpr int kQuantMaxC = 4096;
+
+// smallest e with amax <= 448 * 2^e, read off the fp32 bits (448 = 1.75 * 2^8: mantissa above 0.75 needs one binade more),
+// clamped to the E8M0 range; 0 for an all-zero block
+__device__ __forceinline__ int mx_block_exponent(float amax) {
+  const unsigned bits = __float_as_uint(amax);
+  if (bits == 0u) return 0;
+  const int e = (int)(bits >> 23) - 135 + ((bits & 0x7fffffu) > 0x600000u ? 1 : 0);
+  return max(-127, min(127, e));
+}
+
+__global__ __launch_bounds__(256) void gn_quant_mx_kernel(const SaspaGroupNormParams p, int slabs, int ipb, uint8_t* q, int ldq,
+                                                          uint8_t* qs, int ldqs) {
+  __shared__ float2 stat[256];
+  __shared__ float scs[kQuantMaxC], shs[kQuantMaxC];
+  const int tid = threadIdx.x;
+  const int b = blockIdx.y;
+  const int C = p.c0 + p.c1;
+  const int C8 = C >> 3;
+  const int cpg = C / p.groups;
+  gn_image_stats(p, slabs, b, stat);
+  for (int c = tid; c < C; c += 256) {
+    const float2 st = stat[c / cpg];
+    const float sc = p.gamma[c] * st.y;                 // the arithmetic of gn_apply_kernel
+    scs[c] = sc;
+    shs[c] = p.beta[c] - st.x * sc;
+  }
+  __syncthreads();
+  const int total = p.hw * C8;
+  const int beg = blockIdx.x * ipb;
+  const int end = min(total, beg + ipb);
+  const bool silu = p.act == SASPA_ACT_SILU;
+  // (pixel, chunk) of the thread's first item, advanced by 256 items per step without a division
+  const int step_p = 256 / C8, step_c = 256 - step_p * C8;
+  int px = (beg + tid) / C8, ck = (beg + tid) - px * C8;
+  constexpr int U = 4;
+  for (int i0 = beg + tid; i0 < end; i0 += U * 256) {
+    float v[U][8];
+    int pxu[U], cku[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      pxu[u] = px;
+      cku[u] = ck;
+      ck += step_c;
+      px += step_p;
+      if (ck >= C8) { ck -= C8; ++px; }
+      if (i0 + u * 256 < end) {
+        const int ch = cku[u] * 8;
+        const long long pix = (long long)b * p.hw + pxu[u];
+        const bf16_t* src = ch < p.c0 ? reinterpret_cast<const bf16_t*>(p.x0) + pix * p.ldx0 + ch
+                                       : reinterpret_cast<const bf16_t*>(p.x1) + pix * p.ldx1 + (ch - p.c0);
+        Elem<bf16_t>::load_chunk(src, v[u]);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[u][j] = 0.f;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (i0 + u * 256 >= end) break;                  // uniform over each 4-lane block: the exchanges below see whole blocks
+      const int ch = cku[u] * 8;
+      const float4 s0 = *reinterpret_cast<const float4*>(scs + ch), s1 = *reinterpret_cast<const float4*>(scs + ch + 4);
+      const float4 h0 = *reinterpret_cast<const float4*>(shs + ch), h1 = *reinterpret_cast<const float4*>(shs + ch + 4);
+      const float scv[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
+      const float shv[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
+      float amax = 0.f;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        float y = v[u][j] * scv[j] + shv[j];
+        if (silu) y = silu_fast(y);
+        v[u][j] = y;
+        amax = fmaxf(amax, fabsf(y));
+      }
+      amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
+      amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
+      const int e = mx_block_exponent(amax);
+      float t[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) t[j] = ldexpf(v[u][j], -e);   // exact; |t| <= 448 by the choice of e
+      int w0 = 0, w1 = 0;
+      w0 = __builtin_amdgcn_cvt_pk_fp8_f32(t[0], t[1], w0, false);
+      w0 = __builtin_amdgcn_cvt_pk_fp8_f32(t[2], t[3], w0, true);
+      w1 = __builtin_amdgcn_cvt_pk_fp8_f32(t[4], t[5], w1, false);
+      w1 = __builtin_amdgcn_cvt_pk_fp8_f32(t[6], t[7], w1, true);
+      const long long pix = (long long)b * p.hw + pxu[u];
+      *reinterpret_cast<int2*>(q + pix * ldq + ch) = make_int2(w0, w1);
+      if ((cku[u] & 3) == 0) qs[pix * ldqs + (cku[u] >> 2)] = (uint8_t)(e + 127);
+    }
+  }
 }
 
 // ---- LayerNorm: LPR lanes per row (64 / LPR rows per wave), NCH chunks of 8 channels per lane, two-pass in registers.
@@ -649,6 +754,30 @@ extern "C" int saspa_groupnorm_apply(const SaspaGroupNormParams* pp, void* strea
   dim3 grid(nblk, p.batch, ge.slabs);
   if (p.dtype == SASPA_BF16) hipLaunchKernelGGL(gn_apply_kernel<bf16_t>, grid, dim3(256), 0, s, p, ge.cxw, ge.slabs, ppb);
   else hipLaunchKernelGGL(gn_apply_kernel<float>, grid, dim3(256), 0, s, p, ge.cxw, ge.slabs, ppb);
+  SASPA_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int saspa_groupnorm_quant_mxfp8(const SaspaGroupNormParams* pp, void* q, int ldq, void* qs, int ldqs, void* stream) {
+  if (!pp || !q || !qs) return SASPA_EINVAL;
+  const SaspaGroupNormParams& p = *pp;
+  if (int e = check_gn(p)) return e;
+  if (p.act != SASPA_ACT_NONE && p.act != SASPA_ACT_SILU) return SASPA_EINVAL;
+  const int C = p.c0 + p.c1;
+  if (p.dtype != SASPA_BF16 || C % 32 || C > kQuantMaxC) return SASPA_ERANGE;
+  if (ldq % 16 || ldq < C || !aligned16(q) || ldqs < C / 32) return SASPA_EALIGN;
+  const int C8 = C / 8;
+  if ((long long)p.hw * C8 >= (1ll << 30)) return SASPA_ERANGE;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const GnGeom ge = gn_geometry(C8);          // layout of the statistics pass's partial sums (unused with epilogue statistics)
+  // about 1024 workgroups in all, each at least 8 trips of 256 items long (amortises the statistics prologue)
+  const int items = p.hw * C8;
+  int nblk = 1024 / p.batch;
+  if (nblk > items / 2048) nblk = items / 2048;
+  if (nblk < 1) nblk = 1;
+  const int ipb = ((items + nblk - 1) / nblk + 3) & ~3;
+  nblk = (items + ipb - 1) / ipb;
+  hipLaunchKernelGGL(gn_quant_mx_kernel, dim3(nblk, p.batch), dim3(256), 0, s, p, ge.slabs, ipb, (uint8_t*)q, ldq, (uint8_t*)qs, ldqs);
   SASPA_CHECK_LAUNCH();
   return 0;
 }

@@ -178,12 +178,31 @@ def attention_core(q, k, vt, heads, nq, nk, causal=False, prescaled=False, v_row
 # ------------------------------------------------------------------------------------------
 # UNet / ControlNet building blocks
 # ------------------------------------------------------------------------------------------
+# MX-fp8 resnet convs (fp8_conv): the routing rule, set from tools/mxfp8_conv_bench.py (profiles/mxfp8_conv_bench_b8.txt, batch 8).
+# The MX conv has no split-K: with fewer 128 x 160 output tiles than two per CU (2 x 256) it leaves CUs idle where the bf16 path
+# slices K.  Every shape with >= 512 tiles measured faster (x1.028 .. x1.441); at one tile per CU (256) only short K won (C <= 640:
+# x1.094 .. x1.293; C = 960 / 1280 / 1920 measured x0.98-0.99 / x0.94 / x0.85-0.86); below 256 tiles every shape lost (x0.262 .. x0.878).
+MXFP8_CONV_FULL_TILES = 512
+MXFP8_CONV_MIN_TILES = 256
+MXFP8_CONV_SHORT_C = 640
+
+
+def mxfp8_conv_takes(m, n, c):
+    """Routing rule of the fp8 conv path: does an eligible resnet conv (m output pixels, c input and n output channels) run MX-fp8?"""
+    tiles = ((m + 127) // 128) * (n // 160)
+    return tiles >= MXFP8_CONV_FULL_TILES or (tiles >= MXFP8_CONV_MIN_TILES and c <= MXFP8_CONV_SHORT_C)
+
+
 class _Net:
-    def __init__(self, sd, cfg, dev, dtype, fp8=False):
+    def __init__(self, sd, cfg, dev, dtype, fp8=False, fp8_conv=False):
         self.cfg, self.dev, self.dtype = cfg, dev, dtype
         # fp8: the LayerNorm-fed projections of the transformer blocks (attn2.to_q, ff.net.0.proj) run W8A8 on
         # saspa_gemm_fp8 (bf16 networks only; blocks whose width is not a multiple of 128 stay bf16)
         self.fp8 = bool(fp8) and dtype == torch.bfloat16
+        # fp8_conv (needs fp8): ResnetBlock2D conv1 / conv2 as quantising GroupNorm -> MX-fp8 conv (saspa_groupnorm_quant_mxfp8 +
+        # saspa_conv3x3_mxfp8) where the library accepts the shape and mxfp8_conv_takes(M, N); weights quantised at pack time
+        self.fp8_conv = self.fp8 and bool(fp8_conv)
+        self.fp8_convs = set()            # "<resnet>.conv1" / ".conv2" that have run on the MX-fp8 conv
         self.fp8_blocks = set()
         self.fp8_qkv = set()              # blocks whose fused self-attention projection runs on fp8 tiles (round 6)
         self.fp8_ffout = {}               # block -> calibrated?  (feed-forward output projection on fp8 tiles, round 6)
@@ -203,6 +222,12 @@ class _Net:
         pk.conv(pfx + ".conv1")
         pk.norm(pfx + ".norm2")
         pk.conv(pfx + ".conv2")
+        if self.fp8_conv:
+            for name in (pfx + ".conv1", pfx + ".conv2"):
+                w = pk.sd[name + ".weight"]
+                if ops.conv3x3_mxfp8_eligible(w.shape[1], w.shape[0]):
+                    w8, sw = W.pack_conv_mxfp8(w)
+                    self.p[name + ".w8"], self.p[name + ".sw"] = w8.to(self.dev), sw.to(self.dev)
         if pfx + ".conv_shortcut.weight" in pk.sd:
             pk.conv(pfx + ".conv_shortcut", split)
         if pfx + ".time_emb_proj.weight" in pk.sd:
@@ -379,10 +404,22 @@ class _Net:
         # (round 6: the halo-tiled conv with the GroupNorm applied in LDS -- saspa_conv3x3_halo, SASPA_HALO=1 in round 5 -- is no longer
         # reachable from the pipeline: parity-green, -1.4 % end to end, both arms in profiles/EXPERIMENTS.md; the kernel stays a tested
         # library entry point)
-        h = ops.groupnorm(x, p[pfx + ".norm1.g"], p[pfx + ".norm1.b"], g, eps, SILU, x2=x2)
-        # conv1 -> norm2 -> SiLU: conv1's output has no other reader (fuse_gn: one launch for reduce + GroupNorm at the small levels)
-        h = ops.conv(h, p[pfx + ".conv1.w"], p[pfx + ".conv1.b"], kh=3, kw=3, pad=1, rowvec=rv, gn_unit=self.gn_unit,
-                     fuse_gn=(p[pfx + ".norm2.g"], p[pfx + ".norm2.b"], g, eps, SILU))
+        m = x.shape[0] * x.shape[1] * x.shape[2]
+        c1 = x.shape[3] + (0 if x2 is None else x2.shape[3])
+        mx1 = (pfx + ".conv1.w8") in p and mxfp8_conv_takes(m, p[pfx + ".conv1.w8"].shape[0], c1)
+        mx2 = (pfx + ".conv2.w8") in p and mxfp8_conv_takes(m, p[pfx + ".conv2.w8"].shape[0], p[pfx + ".conv2.w8"].shape[0])
+        if mx1:
+            # fp8 conv path: norm1 + SiLU quantised to MX-fp8 (one exponent per pixel and 32 channels), the conv on block-scaled tiles
+            q, qs = ops.groupnorm_quant_mxfp8(x, p[pfx + ".norm1.g"], p[pfx + ".norm1.b"], g, eps, SILU, x2=x2)
+            h = ops.conv3x3_mxfp8(q, qs, p[pfx + ".conv1.w8"], p[pfx + ".conv1.sw"], p[pfx + ".conv1.b"], rowvec=rv, gn_unit=self.gn_unit)
+            self.fp8_convs.add(pfx + ".conv1")
+            if not mx2:
+                h = ops.groupnorm(h, p[pfx + ".norm2.g"], p[pfx + ".norm2.b"], g, eps, SILU)
+        else:
+            h = ops.groupnorm(x, p[pfx + ".norm1.g"], p[pfx + ".norm1.b"], g, eps, SILU, x2=x2)
+            # conv1 -> norm2 -> SiLU: conv1's output has no other reader (fuse_gn: one launch for reduce + GroupNorm at the small levels)
+            h = ops.conv(h, p[pfx + ".conv1.w"], p[pfx + ".conv1.b"], kh=3, kw=3, pad=1, rowvec=rv, gn_unit=self.gn_unit,
+                         fuse_gn=None if mx2 else (p[pfx + ".norm2.g"], p[pfx + ".norm2.b"], g, eps, SILU))
         # (the 1x1 shortcut conv on the side stream beside norm1 / conv1 -- MFMA-bound next to an HBM-bound pass -- measured +-0.1 % at
         # 512x512 / 512x704 / 512x768 in round 6, like round 4's finer forks: profiles/r6_sc_fork_ab.txt; not kept)
         if pfx + ".conv_shortcut.w" in p:
@@ -390,6 +427,11 @@ class _Net:
         else:
             assert x2 is None
             sc = x
+        if mx2:
+            q, qs = ops.groupnorm_quant_mxfp8(h, p[pfx + ".norm2.g"], p[pfx + ".norm2.b"], g, eps, SILU)
+            self.fp8_convs.add(pfx + ".conv2")
+            return ops.conv3x3_mxfp8(q, qs, p[pfx + ".conv2.w8"], p[pfx + ".conv2.sw"], p[pfx + ".conv2.b"], residual=sc,
+                                     gn_unit=self.gn_unit)
         return ops.conv(h, p[pfx + ".conv2.w"], p[pfx + ".conv2.b"], kh=3, kw=3, pad=1, residual=sc, gn_unit=self.gn_unit)
 
     def _quantize_block(self, t):
@@ -551,8 +593,8 @@ class _Net:
 class UNet(_Net):
     """UNet2DConditionModel (SD-1.5 topology)."""
 
-    def __init__(self, sd, cfg, dev, dtype, fp8=False):
-        super().__init__(sd, cfg, dev, dtype, fp8)
+    def __init__(self, sd, cfg, dev, dtype, fp8=False, fp8_conv=False):
+        super().__init__(sd, cfg, dev, dtype, fp8, fp8_conv)
         self._pack_encoder()
         pk = self.pk
         bo = cfg["block_out"]
@@ -605,8 +647,8 @@ class UNet(_Net):
 class ControlNet(_Net):
     """ControlNetModel (control_v11p_sd15_canny topology)."""
 
-    def __init__(self, sd, cfg, dev, dtype, fp8=False):
-        super().__init__(sd, cfg, dev, dtype, fp8)
+    def __init__(self, sd, cfg, dev, dtype, fp8=False, fp8_conv=False):
+        super().__init__(sd, cfg, dev, dtype, fp8, fp8_conv)
         self._pack_encoder()
         pk = self.pk
         ce = cfg["cond_embed"]

@@ -84,7 +84,9 @@ def _L():
 
 GEMM_FAMILY_FP8 = 8                  # recorder meta only: launches of saspa_gemm_fp8 (not a SaspaGemmParams.variant)
 GEMM_FAMILY_FF_BLOCK = 16                 # saspa_ff_block (not a saspa_gemm dispatch: the launch names its family itself)
-GEMM_FAMILY_NAMES = {1: "tiled_4wave", 2: "wide_8wave", 3: "wave_specialised", 4: "a_stationary", 8: "fp8_e4m3", 16: "ff_block"}
+GEMM_FAMILY_MXFP8_CONV = 32               # saspa_conv3x3_mxfp8 (block-scaled e4m3 3x3 conv; recorder meta only, like GEMM_FAMILY_FP8)
+GEMM_FAMILY_NAMES = {1: "tiled_4wave", 2: "wide_8wave", 3: "wave_specialised", 4: "a_stationary", 8: "fp8_e4m3", 16: "ff_block",
+                     32: "mxfp8_conv"}
 
 
 def _meta_kernel(p, meta):
@@ -771,6 +773,24 @@ def _gn_nsplit(batch, hw, c8):
     return max(1, min(want, 64, hw // 16 if hw >= 16 else 1))
 
 
+def _epilogue_stats(x, x2, groups):
+    """(stats of x, stats of x2 or None) that the producers' epilogues hung on the tensors (`saspa_gn`, see _gn_stats_for), when
+    they still describe the tensors and a GroupNorm of `groups` groups over cat(x, x2) can use them; else (None, None)."""
+    def _fresh(t):
+        g = getattr(t, "saspa_gn", None) if t is not None else None
+        if g is None or g[2] != t.data_ptr() or g[3] != t._version or g[0].shape[0] * 128 != t.shape[0] * t.shape[1] * t.shape[2]:
+            return None
+        return g
+    b, h, w, c0 = x.shape
+    c1 = 0 if x2 is None else x2.shape[3]
+    ctot = c0 + c1
+    g0, g1 = _fresh(x), _fresh(x2)
+    fused = (g0 is not None and (x2 is None or g1 is not None) and gn_fusion_enabled() and (h * w) % 128 == 0
+             and (x2 is None or g1[1] == g0[1]) and c0 % g0[1] == 0 and c1 % g0[1] == 0 and (ctot // groups) % g0[1] == 0
+             and g0[0].shape[1] * g0[1] == c0 and (x2 is None or g1[0].shape[1] * g1[1] == c1))
+    return (g0, g1) if fused else (None, None)
+
+
 def groupnorm(x, gamma, beta, groups, eps, act=ACT_NONE, x2=None, out=None):
     """GroupNorm(+SiLU) over channels-last x (optionally concatenated with x2) -> [B,H,W,C]."""
     _check_dev(x, gamma, beta, x2, out)
@@ -787,16 +807,8 @@ def groupnorm(x, gamma, beta, groups, eps, act=ACT_NONE, x2=None, out=None):
     if out is None:
         out = torch.empty((b, h, w, ctot), device=x.device, dtype=x.dtype)
     # statistics left by the producers' epilogues (conv(..., gn_unit=...)): no statistics pass
-    def _fresh(t):
-        g = getattr(t, "saspa_gn", None) if t is not None else None
-        if g is None or g[2] != t.data_ptr() or g[3] != t._version or g[0].shape[0] * 128 != t.shape[0] * t.shape[1] * t.shape[2]:
-            return None
-        return g
-    g0, g1 = _fresh(x), _fresh(x2)
-    fused = (g0 is not None and (x2 is None or g1 is not None) and gn_fusion_enabled() and (h * w) % 128 == 0
-             and (x2 is None or g1[1] == g0[1]) and c0 % g0[1] == 0 and c1 % g0[1] == 0 and (ctot // groups) % g0[1] == 0
-             and g0[0].shape[1] * g0[1] == c0 and (x2 is None or g1[0].shape[1] * g1[1] == c1))
-    if fused:
+    g0, g1 = _epilogue_stats(x, x2, groups)
+    if g0 is not None:
         p = _lib.GroupNormParams()
         p.dtype = _dt(x)
         p.x0, p.x1, p.c0, p.c1 = _ptr(x), _ptr(x2), c0, c1
@@ -837,6 +849,101 @@ def groupnorm(x, gamma, beta, groups, eps, act=ACT_NONE, x2=None, out=None):
     s = _stream()
     _lib.check(lib.saspa_groupnorm_stats(C.byref(p), s), "saspa_groupnorm_stats")
     _lib.check(lib.saspa_groupnorm_apply(C.byref(p), s), "saspa_groupnorm_apply")
+    return out
+
+
+def groupnorm_quant_mxfp8(x, gamma, beta, groups, eps, act=ACT_NONE, x2=None):
+    """GroupNorm(+SiLU) over channels-last bf16 x (optionally concatenated with x2), quantised to MX-fp8 for conv3x3_mxfp8 ->
+    (q uint8 [B,H,W,C] e4m3 bytes, qs uint8 [B,H,W,C/32] E8M0 exponents of each pixel's 32-channel blocks):
+    `saspa_groupnorm_quant_mxfp8`.  Statistics as `groupnorm` finds them (the producers' epilogues, else a statistics pass)."""
+    _check_dev(x, gamma, beta, x2)
+    lib = _L()
+    b, h, w, c0 = x.shape
+    c1 = 0 if x2 is None else x2.shape[3]
+    ctot = c0 + c1
+    if x.dtype != torch.bfloat16 or (x2 is not None and x2.dtype != x.dtype):
+        raise TypeError("the MX-fp8 path takes bf16 activations")
+    if x2 is not None and tuple(x2.shape[:3]) != (b, h, w):
+        raise ValueError(f"concat source {tuple(x2.shape)} does not match {tuple(x.shape)}")
+    if gamma.numel() < ctot or beta.numel() < ctot or ctot % groups:
+        raise ValueError("GroupNorm parameters / groups do not match the channel count")
+    q = torch.empty((b, h, w, ctot), device=x.device, dtype=torch.uint8)
+    qs = torch.empty((b, h, w, ctot // 32), device=x.device, dtype=torch.uint8)
+    p = _lib.GroupNormParams()
+    p.dtype = _dt(x)
+    p.x0, p.x1, p.c0, p.c1 = _ptr(x), _ptr(x2), c0, c1
+    p.ldx0 = _pitch4(x)
+    p.ldx1 = 0 if x2 is None else _pitch4(x2)
+    p.batch, p.hw, p.groups, p.eps = b, h * w, groups, float(eps)
+    p.gamma, p.beta = _ptr(gamma), _ptr(beta)
+    p.scale_shift, p.act, p.y, p.ldy = None, int(act), None, 0
+    s = _stream()
+    g0, g1 = _epilogue_stats(x, x2, groups)
+    if g0 is not None:
+        p.partial, p.nsplit = None, 0
+        p.stats0, p.stats1, p.unit = _ptr(g0[0]), (_ptr(g1[0]) if g1 is not None else None), g0[1]
+    else:
+        # pixel splits fixed per image (not _gn_nsplit's share of ~1024 workgroups over the batch): an image's statistics, and so its
+        # bytes, do not depend on the batch it is quantised in
+        nsplit = max(1, min(64, h * w // 16))
+        partial = torch.empty((b * nsplit * ctot * 2,), device=x.device, dtype=torch.float32)
+        p.partial, p.nsplit = _ptr(partial), nsplit
+        _lib.check(lib.saspa_groupnorm_stats(C.byref(p), s), "saspa_groupnorm_stats")
+    _lib.check(lib.saspa_groupnorm_quant_mxfp8(C.byref(p), _ptr(q), ctot, _ptr(qs), ctot // 32, s), "saspa_groupnorm_quant_mxfp8")
+    return q, qs
+
+
+def _conv_mx_params(q, qs, w8, sw, bias, rowvec, residual, out):
+    b, h, w, c = q.shape
+    p = _lib.ConvMxParams()
+    p.q, p.ldq, p.qs, p.ldqs = _ptr(q), c, _ptr(qs), qs.shape[-1]
+    p.batch, p.h, p.w, p.C = b, h, w, c
+    p.kh, p.kw, p.stride, p.pad, p.upsample = 3, 3, 1, 1, 0
+    p.w8, p.ldw, p.N, p.Kp = _ptr(w8), w8.shape[1], w8.shape[0], w8.shape[1]
+    p.sw, p.bias = _ptr(sw), _ptr(bias)
+    p.rowvec, p.ldrv = _ptr(rowvec), (0 if rowvec is None or rowvec.dim() == 1 or rowvec.shape[0] == 1 else rowvec.stride(0))
+    n = w8.shape[0]
+    p.residual, p.ldr = _ptr(residual), (0 if residual is None else _pitch4(residual))
+    p.out, p.ldo = _ptr(out), n
+    return p
+
+
+def conv3x3_mxfp8_eligible(c, n, h=64, w=64, batch=1):
+    """Shapes saspa_conv3x3_mxfp8 runs (3x3 / stride 1 / pad 1 of c channels into n): the library's own host-side answer."""
+    p = _lib.ConvMxParams()
+    p.batch, p.h, p.w, p.C, p.kh, p.kw, p.stride, p.pad = batch, h, w, c, 3, 3, 1, 1
+    p.N, p.Kp = n, (9 * c + 127) // 128 * 128
+    p.ldq, p.ldqs, p.ldw, p.ldo = c, c // 32, p.Kp, n
+    return bool(_lib.load().saspa_conv3x3_mxfp8_eligible(C.byref(p)))
+
+
+def conv3x3_mxfp8(q, qs, w8, sw, bias=None, rowvec=None, residual=None, gn_unit=None):
+    """3x3 / stride 1 / pad 1 conv of MX-fp8 activations (groupnorm_quant_mxfp8's (q, qs)) with e4m3 weights
+    (weights.pack_conv_mxfp8's (w8, sw)) -> bf16 [B,H,W,N]: `saspa_conv3x3_mxfp8`.  out = bf16(sw * sum + bias + rowvec[b])
+    (+ residual); gn_unit: leave the GroupNorm statistics of the output for the next GroupNorm / quantiser (as `conv`)."""
+    _check_dev(q, qs, w8, sw, bias, rowvec, residual)
+    b, h, w, c = q.shape
+    n, kp = w8.shape
+    if kp != (9 * c + 127) // 128 * 128:
+        raise ValueError(f"weights {tuple(w8.shape)} are not weights.pack_conv_mxfp8 of a 3x3 conv over {c} channels")
+    if q.dtype != torch.uint8 or qs.dtype != torch.uint8 or w8.dtype != torch.uint8 or tuple(qs.shape) != (b, h, w, c // 32):
+        raise TypeError("conv3x3_mxfp8 takes uint8 e4m3 bytes / E8M0 exponents")
+    if not (q.is_contiguous() and qs.is_contiguous() and w8.is_contiguous()):
+        raise ValueError("conv3x3_mxfp8 operands must be dense")
+    if residual is not None and (tuple(residual.shape) != (b, h, w, n) or residual.dtype != torch.bfloat16):
+        raise ValueError(f"residual {tuple(residual.shape)} does not match the output [{b},{h},{w},{n}]")
+    out = torch.empty((b, h, w, n), device=q.device, dtype=torch.bfloat16)
+    for name, t in (("sw", sw), ("bias", bias)):
+        if t is not None and (t.dtype != torch.float32 or t.dim() != 1 or t.shape[0] != n or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a dense fp32 [{n}] vector (got {tuple(t.shape)} {t.dtype})")
+    if rowvec is not None and (rowvec.dtype != torch.float32 or rowvec.dim() > 2 or rowvec.stride(-1) != 1 or rowvec.shape[-1] != n
+                               or (rowvec.dim() == 2 and rowvec.shape[0] not in (1, b))):
+        raise ValueError(f"rowvec {tuple(rowvec.shape)} {rowvec.dtype} is not fp32 [1 or {b}, {n}] with dense rows")
+    p = _conv_mx_params(q, qs, w8, sw, bias, rowvec, residual, out)
+    m = b * h * w
+    _gn_stats_for(p, out, gn_unit, b, h * w, n)
+    _launch("gemm", 2.0 * m * n * 9 * c, lambda: _lib.check(_L().saspa_conv3x3_mxfp8(C.byref(p), _stream()), "saspa_conv3x3_mxfp8"),
+            (m, n, 9 * c, 3, 1, 0, False, residual is not None, n, GEMM_FAMILY_MXFP8_CONV, 1))
     return out
 
 

@@ -283,8 +283,10 @@ class StableDiffusionControlNetPipeline:
         self.device = device
         sd, cf = self._state_dicts, self.cfgs
         fp8 = getattr(self, "_fp8", False) or os.environ.get("SASPA_FP8", "0") == "1"
-        self.unet = models.UNet(sd["unet"], cf["unet"], device, cdt, fp8=fp8)
-        self.controlnet = models.ControlNet(sd["controlnet"], cf["controlnet"], device, cdt, fp8=fp8) if self.HAS_CONTROLNET else None
+        fp8_conv = fp8 and (getattr(self, "_fp8_conv", False) or os.environ.get("SASPA_FP8_CONV", "0") == "1")
+        self.unet = models.UNet(sd["unet"], cf["unet"], device, cdt, fp8=fp8, fp8_conv=fp8_conv)
+        self.controlnet = (models.ControlNet(sd["controlnet"], cf["controlnet"], device, cdt, fp8=fp8, fp8_conv=fp8_conv)
+                           if self.HAS_CONTROLNET else None)
         self.vae = models.VAEDecoder(sd["vae"], cf["vae"], device, cdt)
         self.text_encoder = models.CLIPText(sd["text"], cf["text"], device, cdt)
         self._build_extra(sd, cf, device, cdt)
@@ -297,13 +299,18 @@ class StableDiffusionControlNetPipeline:
         if "safety" in sd and "safety" in cf:
             self.safety_checker = models.SafetyChecker(sd["safety"], cf["safety"], device, cdt)
 
-    def enable_fp8(self, on=True):
+    def enable_fp8(self, on=True, convs=False):
         """Call BEFORE `.to()`: the LayerNorm-fed projections of the UNet / ControlNet transformer blocks (cross-attention
         query, GEGLU feed-forward) run as e4m3 W8A8 GEMMs (BASELINE.json configs[4] "fp8 MFMA"; SASPA_FP8=1 does the same).
-        Off by default: the headline metric is quoted in bf16."""
+        convs=True (SASPA_FP8_CONV=1, needs fp8 on): the ResnetBlock2D conv1 / conv2 also run as MX-fp8 (block-scaled e4m3) convs
+        where models.mxfp8_conv_takes admits them (models._Net.fp8_convs lists those that ran).  Off by default: the headline
+        metric is quoted in bf16."""
         if self.unet is not None:
             raise RuntimeError("enable_fp8() must be called before .to(): the weights are quantised at pack time")
+        if convs and not on:
+            raise ValueError("fp8 convs need fp8 on: enable_fp8(True, convs=True)")
         self._fp8 = bool(on)
+        self._fp8_conv = bool(convs)
         return self
 
     def upcast_vae(self, gemm=None):  # SDXL-only hook the reference calls at run_aug/run_aug.py:224

@@ -726,6 +726,18 @@ def quantize_fp8(w):
     return q.view(torch.uint8).contiguous(), scale.contiguous()
 
 
+def pack_conv_mxfp8(w):
+    """[Cout, Cin, 3, 3] fp32 conv weight -> (e4m3 bytes uint8 [Cout, Kp], per-output-channel scale fp32 [Cout]) for
+    saspa_conv3x3_mxfp8: K = (ky*3+kx)*Cin + c (pack_conv's tap-major order, no channel padding), zero padded to Kp = a
+    multiple of 128; the scales of quantize_fp8 on the packed matrix (the padding is zero, so it changes no row maximum)."""
+    pk = pack_conv(w.float(), cin_pad=w.shape[1])
+    k = pk.shape[1]
+    kp = (k + 127) // 128 * 128
+    if kp != k:
+        pk = torch.nn.functional.pad(pk, (0, kp - k))
+    return quantize_fp8(pk)
+
+
 def dequantize_fp8(q_u8, scale):
     return q_u8.view(torch.float8_e4m3fn).float() * scale[:, None]
 

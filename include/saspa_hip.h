@@ -378,6 +378,9 @@ int saspa_resample_u8(const uint8_t* src, uint8_t* dst, long long outer, int in_
  * (CLIPImageProcessor rescale + normalize; SURVEY 8a: a7.9) */
 int saspa_u8_to_act_norm(int dtype, const uint8_t* src, void* dst, long long npix, float mean0, float mean1, float mean2,
                          float std0, float std1, float std2, void* stream);
+/* Pillow's convert("L").convert("RGB") (the grey conversion in front of the LPIPS filter, all_utils/utils.py:577-578): u8 RGB
+ * [npix][3] -> u8 [npix][3] with all three channels = (19595 R + 38470 G + 7471 B + 0x8000) >> 16.  Integer exact; src == dst allowed. */
+int saspa_u8_luma(const uint8_t* src, uint8_t* dst, long long npix, void* stream);
 
 /* StableDiffusionSafetyChecker decision + black-out on the device (no host round trip; SURVEY 8a: a7.9):
  * dots [nimg][ldd] = image embedding . unit(special-care | concept embeddings) (special-care columns first),
@@ -418,6 +421,21 @@ int saspa_pool2d(int dtype, int mode, const void* x, int ldx, void* y, int ldy, 
  * y = sign(x) * sqrt(|x| + eps); out = scale * y / max(||y||_2, 1e-12).  fp32 in / out. */
 int saspa_signsqrt_l2norm(const float* x, long long ldx, float* y, long long ldy, int rows, long long C, float eps,
                           float scale, void* stream);
+/* One feature level of LPIPS (Zhang et al. 2018; lpips v0.1 `normalize_tensor` + `lin` + spatial average) for a batch of pairs, the
+ * distance behind the reference's lpips_min / lpips_max filter (all_utils/utils.py:377-381, :576-590):
+ *   dist[j] (+)= 1/hw * sum_p sum_c w[c] * (a[j][p][c] / (|a[j][p]|_2 + 1e-10) - r[i][p][c] / (|r[i][p]|_2 + 1e-10))^2,  i = ref_index[j]
+ * a: [n][hw][lda], r: [m][hw][ldr] channels-last features as saspa_gemm leaves them (SASPA_BF16 or SASPA_F32 storage; fp32 arithmetic),
+ * w: C non-negative fp32 weights, ref_index: n DEVICE int32 (NOT validated here: the caller guarantees 0 <= ref_index[j] < m),
+ * dist: n fp32, overwritten (accumulate == 0) or added to (accumulate != 0: the five levels sum into one vector).
+ * workspace: n * SASPA_LPIPS_MAX_BLOCKS fp32 of scratch (per-workgroup partial sums; reduced in a fixed order by a second launch).
+ * C % 8 == 0, C <= SASPA_LPIPS_MAX_C, pitches % 8 == 0 and >= C, 16-byte aligned bases, n <= 65535.  The difference form is
+ * evaluated as written (no expanded products): d(x, x) == 0.0 exactly and an all-zero pixel vector contributes 0.  No atomics; how a
+ * pair's pixels are cut over workgroups depends on (hw, C) only, so dist[j] is bit-identical from run to run, for every batch size
+ * and every position of the pair in the batch. */
+#define SASPA_LPIPS_MAX_C 512
+#define SASPA_LPIPS_MAX_BLOCKS 64
+int saspa_lpips_layer(int dtype, const void* a, int lda, const void* r, int ldr, const int* ref_index, const float* w, float* dist,
+                      float* workspace, int n, int hw, int C, int accumulate, void* stream);
 
 /* ---- cv2.resize, 8-bit RGB [n][h][w][3] -> [n][dh][dw][3] (all_utils/utils.py:58-79 `resize_image`) -------
  * saspa_resize_taps_u8: OpenCV's separable fixed-point filters; xofs / yofs = first tap index per destination sample,

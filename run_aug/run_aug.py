@@ -13,7 +13,8 @@ started again ONCE as fresh processes with SASPA_FORK=0 (single-branch step grap
 exist; the exit code is non-zero if that fails too.  SASPA_FORK=0 by hand rules the two-branch capture out from the start.
 
 Environment overlays (optional): SASPA_DATASET, SASPA_WEIGHTS_DIR, SASPA_PROMPTS_FILE,
-SASPA_NUM_INFERENCE_STEPS, SASPA_NUM_PER_IMAGE, SASPA_PRECISION, SASPA_BASE_MODEL (sd_v1.5 | blip_diffusion | sd_xl-turbo)."""
+SASPA_NUM_INFERENCE_STEPS, SASPA_NUM_PER_IMAGE, SASPA_PRECISION, SASPA_BASE_MODEL (sd_v1.5 | blip_diffusion | sd_xl-turbo),
+SASPA_LPIPS_MIN / SASPA_LPIPS_MAX (the LPIPS filter's bounds; both or neither)."""
 import os
 import sys
 from pathlib import Path
@@ -57,6 +58,8 @@ if __name__ == "__main__":
     # ---------------------------- json creation params ----------------------------
     SEMANTIC_FILTERING = 1
     MODEL_CONFIDENCE_BASED_FILTERING = 1
+    LPIPS_MIN = float(os.environ["SASPA_LPIPS_MIN"]) if os.environ.get("SASPA_LPIPS_MIN") else None
+    LPIPS_MAX = float(os.environ["SASPA_LPIPS_MAX"]) if os.environ.get("SASPA_LPIPS_MAX") else None
     # ---------------------------- this build ----------------------------
     BATCH_SIZE = 8
 
@@ -78,7 +81,8 @@ if __name__ == "__main__":
                    RESOLUTION=RESOLUTION, GUIDANCE_SCALE=GUIDANCE_SCALE, NUM_INFERENCE_STEPS=NUM_INFERENCE_STEPS,
                    LOW_THRESHOLD_CANNY=LOW_THRESHOLD_CANNY, HIGH_THRESHOLD_CANNY=HIGH_THRESHOLD_CANNY,
                    CONTROLNET_CONDITIONING_SCALE=CONTROLNET_CONDITIONING_SCALE, SEMANTIC_FILTERING=SEMANTIC_FILTERING,
-                   MODEL_CONFIDENCE_BASED_FILTERING=MODEL_CONFIDENCE_BASED_FILTERING, BATCH_SIZE=BATCH_SIZE,
+                   MODEL_CONFIDENCE_BASED_FILTERING=MODEL_CONFIDENCE_BASED_FILTERING, LPIPS_MIN=LPIPS_MIN, LPIPS_MAX=LPIPS_MAX,
+                   BATCH_SIZE=BATCH_SIZE,
                    PRECISION=os.environ.get("SASPA_PRECISION", "bf16"), WEIGHTS_DIR=os.environ.get("SASPA_WEIGHTS_DIR"),
                    PROMPTS_FILE=os.environ.get("SASPA_PROMPTS_FILE"))
     assert s.DATASET in R.dataset_utils.DATASETS_SUPPORTED

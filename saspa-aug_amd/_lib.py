@@ -8,6 +8,7 @@ LIB_PATH = os.environ.get("SASPA_HIP_LIB") or os.path.join(_HERE, "libsaspa_hip.
 
 SASPA_BF16, SASPA_F32, SASPA_F32X3 = 0, 1, 2
 SASPA_EINVAL, SASPA_EALIGN, SASPA_ERANGE = -1, -2, -3      # include/saspa_hip.h
+LPIPS_MAX_C, LPIPS_MAX_BLOCKS = 512, 64                    # SASPA_LPIPS_MAX_C / SASPA_LPIPS_MAX_BLOCKS
 ERRORS = {-1: "SASPA_EINVAL (null pointer / bad size)", -2: "SASPA_EALIGN (16-byte alignment / channel multiple)",
           -3: "SASPA_ERANGE (unsupported shape)"}
 
@@ -138,9 +139,11 @@ SYMBOLS = {
     "saspa_canny": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "saspa_resample_u8": (_I, [_P, _P, _LL, _I, _I, _I, _P, _P, _I, _P]),
     "saspa_u8_to_act_norm": (_I, [_I, _P, _P, _LL, _F, _F, _F, _F, _F, _F, _P]),
+    "saspa_u8_luma": (_I, [_P, _P, _LL, _P]),
     "saspa_safety_decide": (_I, [_P, _I, _P, _I, _I, _P, _I, _P, _I, C.c_double, _P, _LL, _P, _P]),
     "saspa_pool2d": (_I, [_I, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "saspa_signsqrt_l2norm": (_I, [_P, _LL, _P, _LL, _I, _LL, _F, _F, _P]),
+    "saspa_lpips_layer": (_I, [_I, _P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "saspa_resize_taps_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P]),
     "saspa_hed_fuse": (_I, [C.POINTER(HedFuseParams), _P]),
     "saspa_gemm_fp8": (_I, [C.POINTER(GemmF8Params), _P]),

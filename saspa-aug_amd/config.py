@@ -66,6 +66,12 @@ CLIP_RN50 = dict(image_size=224, layers=(3, 4, 6, 3), width=64, heads=32, embed_
 # BaseUtils.load_baseline_model, all_utils/dataset_utils.py:101-109), 32 attention maps, 224 x 224 crops
 WSDAN_CAL_R101 = dict(image_size=224, layers=(3, 4, 23, 3), width=64, attentions=32)
 WSDAN_CAL_R50 = dict(image_size=224, layers=(3, 4, 6, 3), width=64, attentions=32)
+# LPIPS v0.1 with the AlexNet backbone (`lpips.LPIPS(net='alex')`, all_utils/utils.py:270): torchvision AlexNet `features` (conv
+# 11x11/4 pad 2, max-pool 3/2, conv 5x5 pad 2, max-pool 3/2, three 3x3 convs; a ReLU after each conv = the five taps) and one
+# non-negative 1x1 `lin` layer per tap.  Recalled from the public torchvision / lpips sources.
+LPIPS_ALEX = dict(channels=(64, 192, 384, 256, 256))
+LPIPS_SHIFT = (-0.030, -0.088, -0.188)     # lpips ScalingLayer on [-1, 1] inputs
+LPIPS_SCALE = (0.458, 0.448, 0.450)
 
 
 # controlnet_aux HEDdetector network (ControlNetHED_Apache2: VGG-16 conv stack, one 1x1 side output per block); the
@@ -79,7 +85,7 @@ def tiny_filters(num_classes=12):
     rn = dict(image_size=64, layers=(1, 1, 1, 1), width=16, heads=4, embed_dim=32, vocab=512, text_width=32, text_heads=2,
               text_layers=2, context=77)
     cal = dict(image_size=64, layers=(1, 1, 2, 1), width=16, attentions=8, num_classes=num_classes)
-    return dict(clip_rn50=rn, cal=cal)
+    return dict(clip_rn50=rn, cal=cal, lpips_alex=dict(channels=(8, 16, 24, 16, 16)))
 
 
 def tiny_xl(width=32, ctx1=32, ctx2=64, groups=8, vae_width=16):

@@ -1,6 +1,7 @@
 // Kernels of the filter stage that follows generation (all_utils/utils.py:306-323, :357-375): pooling of the
 // CLIP-RN50 / ResNet feature extractors and the sign-sqrt + L2-normalise tail of WSDAN_CAL's bilinear attention pooling.
-// Both are HBM-bound streaming kernels (16-byte vectors of 8 channels per lane); the convolutions and linears of the two
+// saspa_lpips_layer is one feature level of the LPIPS distance (lpips_min / lpips_max filter, all_utils/utils.py:377-381).
+// All are HBM-bound streaming kernels (16-byte vectors of 8 channels per lane); the convolutions and linears of the two
 // models are saspa_gemm launches (BatchNorm folded into weights + bias, ReLU in the epilogue).
 #include "common.h"
 
@@ -86,6 +87,84 @@ __global__ __launch_bounds__(256) void signsqrt_l2norm_kernel(const float* x, lo
   }
 }
 
+// ---- LPIPS level -----------------------------------------------------------------------------------------------------------
+// A pixel's channel vector lives in the registers of LPP lanes (LPP = the power of two >= C / 8, at most 64: one wave), 8 channels per
+// lane, from the 16-byte loads until the weighted squared difference is summed: each feature row is read once.  256 / LPP pixel slots
+// per workgroup; workgroup b of pair j owns the pixels [b * ppb, (b + 1) * ppb), slot s the pixels s, s + slots, ... of that range.
+// Every sum has a fixed shape: 8 values per lane as a tree, xor-butterflies inside the slot / wave, the four waves in order through
+// LDS, the workgroups of a pair by one wave of the finishing launch.  nblk and ppb are functions of (hw, C) alone.
+// (no FMA contraction anywhere in this kernel: both operands of a pair must see the very same operation sequence)
+__device__ __forceinline__ float tree8(const float* t) {
+#pragma clang fp contract(off)
+  return ((t[0] + t[1]) + (t[2] + t[3])) + ((t[4] + t[5]) + (t[6] + t[7]));
+}
+
+// x / (|x|_2 + 1e-10) over the slot's lanes (lpips.normalize_tensor: the eps sits outside the root); a zero vector stays zero
+__device__ __forceinline__ void lpips_unit(float* v, int lpp) {
+#pragma clang fp contract(off)
+  float sq[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) sq[i] = v[i] * v[i];
+  float s = tree8(sq);
+  for (int o = lpp >> 1; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  const float d = sqrtf(s) + 1e-10f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) v[i] = v[i] / d;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void lpips_layer_kernel(const T* __restrict__ a, int lda, const T* __restrict__ r, int ldr,
+                                                          const int* __restrict__ ref_index, const float* __restrict__ w,
+                                                          float* __restrict__ partial, int hw, int C, int lpp, int ppb) {
+#pragma clang fp contract(off)
+  __shared__ float part[4];
+  const int j = blockIdx.y, tid = threadIdx.x;
+  const int slots = 256 / lpp, slot = tid / lpp, q = tid % lpp;
+  const bool live = q * 8 < C;                              // lanes beyond C / 8 of a slot carry zeros through the butterflies
+  const T* ap = a + (long long)j * hw * lda + q * 8;
+  const T* rp = r + (long long)ref_index[j] * hw * ldr + q * 8;
+  float wt[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) wt[i] = live ? w[q * 8 + i] : 0.0f;
+  const int p0 = blockIdx.x * ppb, p1 = min(hw, p0 + ppb);
+  float acc = 0.0f;
+  // the trip count is uniform over the wave (the shuffles need every lane); a slot past the range works on zeros
+  for (int pb = p0; pb < p1; pb += slots) {
+    const int p = pb + slot;
+    float va[8], vr[8];
+    if (live && p < p1) {
+      ld8(ap + (long long)p * lda, va);
+      ld8(rp + (long long)p * ldr, vr);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) va[i] = vr[i] = 0.0f;
+    }
+    lpips_unit(va, lpp);
+    lpips_unit(vr, lpp);
+    float t[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const float d = va[i] - vr[i];
+      t[i] = wt[i] * (d * d);
+    }
+    acc += tree8(t);
+  }
+  acc = wave_sum(acc);
+  if ((tid & 63) == 0) part[tid >> 6] = acc;
+  __syncthreads();
+  if (tid == 0) partial[(long long)j * SASPA_LPIPS_MAX_BLOCKS + blockIdx.x] = (part[0] + part[1]) + (part[2] + part[3]);
+}
+
+__global__ __launch_bounds__(64) void lpips_finish_kernel(const float* __restrict__ partial, float* __restrict__ dist, int nblk, int hw,
+                                                          int accumulate) {
+  const int j = blockIdx.x, lane = threadIdx.x;
+  const float s = wave_sum(lane < nblk ? partial[(long long)j * SASPA_LPIPS_MAX_BLOCKS + lane] : 0.0f);
+  if (lane == 0) {
+    const float d = s / (float)hw;
+    dist[j] = accumulate ? dist[j] + d : d;
+  }
+}
+
 }  // namespace
 
 extern "C" int saspa_pool2d(int dtype, int mode, const void* x, int ldx, void* y, int ldy, int batch, int hin, int win, int C, int k,
@@ -119,6 +198,33 @@ extern "C" int saspa_signsqrt_l2norm(const float* x, long long ldx, float* y, lo
   if (!x || !y || rows <= 0 || C <= 0 || ldx < C || ldy < C) return SASPA_EINVAL;
   hipLaunchKernelGGL(signsqrt_l2norm_kernel, dim3((unsigned)rows), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x, ldx, y, ldy,
                      C, eps, scale);
+  SASPA_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int saspa_lpips_layer(int dtype, const void* a, int lda, const void* r, int ldr, const int* ref_index, const float* w,
+                                 float* dist, float* workspace, int n, int hw, int C, int accumulate, void* stream) {
+  if (!a || !r || !ref_index || !w || !dist || !workspace || n <= 0 || hw <= 0 || C <= 0) return SASPA_EINVAL;
+  if (dtype != SASPA_BF16 && dtype != SASPA_F32) return SASPA_EINVAL;
+  if (C % 8 || lda % 8 || ldr % 8 || lda < C || ldr < C || !aligned16(a) || !aligned16(r) || !aligned16(w)) return SASPA_EALIGN;
+  if ((reinterpret_cast<uintptr_t>(dist) | reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(ref_index)) & 3u) return SASPA_EALIGN;
+  if (C > SASPA_LPIPS_MAX_C || n > 65535) return SASPA_ERANGE;          // 8 channels per lane, one wave per pixel; grid.y
+  int lpp = 1;
+  while (lpp * 8 < C) lpp <<= 1;
+  const int slots = 256 / lpp;
+  // at least four pixels per slot and workgroup, at most SASPA_LPIPS_MAX_BLOCKS workgroups per pair: (hw, C) decide, never n
+  int nblk = (hw + 4 * slots - 1) / (4 * slots);
+  if (nblk > SASPA_LPIPS_MAX_BLOCKS) nblk = SASPA_LPIPS_MAX_BLOCKS;
+  const int ppb = (hw + nblk - 1) / nblk;
+  nblk = (hw + ppb - 1) / ppb;                                           // no empty workgroup
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const dim3 g((unsigned)nblk, (unsigned)n), t(256);
+  if (dtype == SASPA_BF16)
+    hipLaunchKernelGGL(lpips_layer_kernel<bf16_t>, g, t, 0, s, (const bf16_t*)a, lda, (const bf16_t*)r, ldr, ref_index, w, workspace, hw, C, lpp, ppb);
+  else
+    hipLaunchKernelGGL(lpips_layer_kernel<float>, g, t, 0, s, (const float*)a, lda, (const float*)r, ldr, ref_index, w, workspace, hw, C, lpp, ppb);
+  SASPA_CHECK_LAUNCH();
+  hipLaunchKernelGGL(lpips_finish_kernel, dim3((unsigned)n), dim3(64), 0, s, (const float*)workspace, dist, nblk, hw, accumulate);
   SASPA_CHECK_LAUNCH();
   return 0;
 }

@@ -4,6 +4,8 @@
 //                        coefficients with 22 fractional bits, accumulator seeded with 1 << 21, result clamped to
 //                        0..255 -- bit-exact against Pillow.  The coefficient / bounds tables are host set-up.
 //   saspa_u8_to_act_norm u8 RGB -> channels-last activations ((x / 255) - mean) / std, 8-channel pixels.
+//   saspa_u8_luma        Pillow's convert("L").convert("RGB") (ITU-R 601-2 luma in 16-bit fixed point), the grey
+//                        conversion in front of the LPIPS filter.
 // HBM-bound byte work (a 512x512x3 image is 786 KB); nothing here is GEMM-shaped.
 #include "common.h"
 
@@ -51,6 +53,18 @@ __global__ __launch_bounds__(256) void u8_to_act_norm_kernel(const uint8_t* src,
       Elem<float>::store_chunk((float*)dst + it * 8, a);
       Elem<float>::store_chunk((float*)dst + it * 8 + 4, a + 4);
     }
+  }
+}
+
+// Pillow ImagingConvert rgb2l: L = (R * 19595 + G * 38470 + B * 7471 + 0x8000) >> 16, written to all three channels
+__global__ __launch_bounds__(256) void u8_luma_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, long long npix) {
+  for (long long it = (long long)blockIdx.x * 256 + threadIdx.x; it < npix; it += (long long)gridDim.x * 256) {
+    const uint8_t* s = src + it * 3;
+    const uint8_t l = (uint8_t)(((unsigned)s[0] * 19595u + (unsigned)s[1] * 38470u + (unsigned)s[2] * 7471u + 0x8000u) >> 16);
+    uint8_t* d = dst + it * 3;
+    d[0] = l;
+    d[1] = l;
+    d[2] = l;
   }
 }
 
@@ -118,6 +132,13 @@ extern "C" int saspa_u8_to_act_norm(int dtype, const uint8_t* src, void* dst, lo
     hipLaunchKernelGGL(u8_to_act_norm_kernel<float>, dim3(grid_for(npix)), dim3(256), 0, s, src, (float*)dst, npix, mean0, mean1, mean2, std0, std1, std2);
   else
     return SASPA_EINVAL;
+  SASPA_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int saspa_u8_luma(const uint8_t* src, uint8_t* dst, long long npix, void* stream) {
+  if (!src || !dst || npix <= 0) return SASPA_EINVAL;
+  hipLaunchKernelGGL(u8_luma_kernel, dim3(grid_for(npix)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), src, dst, npix);
   SASPA_CHECK_LAUNCH();
   return 0;
 }

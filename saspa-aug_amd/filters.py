@@ -5,6 +5,8 @@ sequences of the gfx950 kernels.
   * `SemanticFilter` -- OpenAI CLIP RN50 (`clip.load('RN50')`, all_utils/utils.py:253): image tower = ModifiedResNet +
     attention pool, text tower = 12-layer transformer; an augmented image passes when the dataset's positive prompt
     (`ds_utils.get_basic_prompt()`) beats the six negative prompts (:306-312, `get_semantic_filtering` :169-177).
+  * `LpipsAlex` -- LPIPS v0.1 on AlexNet (`lpips.LPIPS(net='alex')`, all_utils/utils.py:269-270): an augmented image passes when
+    `lpips_min <= d(original, augmented) <= lpips_max` (:377-381), both images grey, 256 x 256 (`calc_lpips_distance` :576-590).
   * `ConfidenceFilter` -- the baseline classifier WSDAN_CAL (fgvc/models/cal.py:131-228; loader
     all_utils/dataset_utils.py:87-115): passes when the SOURCE image's label is among the top-k (10) logits (:357-366).
 
@@ -24,7 +26,7 @@ import torch
 
 from . import imageproc, models, ops
 from . import weights as W
-from .config import CLIP_RN50, WSDAN_CAL_R50, WSDAN_CAL_R101
+from .config import CLIP_RN50, LPIPS_ALEX, LPIPS_SCALE, LPIPS_SHIFT, WSDAN_CAL_R50, WSDAN_CAL_R101
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -75,6 +77,19 @@ class _Convs:
         t = pk.to(self.dev, self.dtype)
         t.saspa_korder = 1 if chunk else 0
         self.p[name + ".w"], self.p[name + ".b"], self.p[name + ".k"] = t, b.to(self.dev, torch.float32).contiguous(), (kh, kw)
+
+    def conv_bias(self, name, conv):
+        """A conv with its own bias and no BatchNorm (AlexNet)."""
+        w = self.sd[conv + ".weight"].float()
+        kh, kw = w.shape[2], w.shape[3]
+        pk = W.pack_conv(w)
+        chunk = W.chunk_major_ok(kh, kw, W.round8(w.shape[1]), 0, self.dtype)
+        if chunk:
+            pk = W.to_chunk_major(pk, kh * kw, self.dtype)
+        t = pk.to(self.dev, self.dtype)
+        t.saspa_korder = 1 if chunk else 0
+        self.p[name + ".w"], self.p[name + ".k"] = t, (kh, kw)
+        self.p[name + ".b"] = self.sd[conv + ".bias"].to(self.dev, torch.float32).contiguous()
 
     def run(self, name, x, stride=1, pad=0, act=RELU, residual=None):
         kh, kw = self.p[name + ".k"]
@@ -254,6 +269,76 @@ class ConfidenceFilter:
         return np.array([int((row > row[int(lb)]).sum()) < self.top_k for lb, row in zip(labels, lg)], dtype=bool)
 
 
+class LpipsAlex:
+    """`lpips.LPIPS(net='alex')` (v0.1) for batches of pairs: ScalingLayer, torchvision AlexNet `features` up to each of the five ReLUs,
+    and per level unit-normalise / difference / square / `lin` weights / spatial mean in ONE kernel (ops.lpips_layer); the five levels
+    sum into one fp32 vector.  The originals' features are computed once and shared by their augmentations through `ref_index`."""
+    STRIDE_PAD = ((4, 2), (1, 2), (1, 1), (1, 1), (1, 1))
+
+    def __init__(self, sd, cfg, dev, dtype=torch.float32):
+        self.cfg, self.dev, self.dtype = cfg, dev, dtype
+        c = self.c = _Convs(sd, dev, dtype)
+        for i, (idx, _) in enumerate(W.LPIPS_ALEX_CONVS):
+            c.conv_bias(f"c{i}", f"features.{idx}")
+        self.lin = []
+        for i, ch in enumerate(cfg["channels"]):
+            w = sd[f"lin{i}.model.1.weight"].reshape(-1).float()
+            if w.numel() != ch or bool((w < 0).any()):
+                raise ValueError(f"lin{i}: expected {ch} non-negative channel weights")
+            self.lin.append(w.contiguous().to(dev))
+        # [0, 1] -> [-1, 1] -> ScalingLayer, folded: (2x - 1 - shift) / scale = (x - (1 + shift) / 2) / (scale / 2)
+        self.mean = tuple((1.0 + sh) / 2.0 for sh in LPIPS_SHIFT)
+        self.std = tuple(sc / 2.0 for sc in LPIPS_SCALE)
+        c.sd = None
+
+    def preprocess(self, images_u8, resize=(256, 256), grey=True):
+        """device u8 [k,H,W,3] -> [k,h,w,8] network input: `convert("L").convert("RGB")` (grey), `Image.resize(resize)` (PIL's
+        default filter, BICUBIC; `resize` = (width, height) like PIL), ToTensor, x * 2 - 1, ScalingLayer."""
+        x = images_u8.contiguous()
+        if grey:
+            x = ops.u8_luma(x)
+        if resize:
+            x = imageproc.resize_u8(x, int(resize[1]), int(resize[0]), filt="bicubic")
+        return imageproc.normalize_u8(x, self.dtype, self.mean, self.std)
+
+    def features(self, pixels):
+        """The five ReLU outputs, channels-last as ops.conv leaves them."""
+        c, feats, x = self.c, [], pixels
+        for i, (stride, pad) in enumerate(self.STRIDE_PAD):
+            if i in (1, 2):
+                x = ops.pool2d(x, 3, 2, 0, mode="max")
+            x = c.run(f"c{i}", x, stride=stride, pad=pad)
+            feats.append(x)
+        return feats
+
+    @torch.no_grad()
+    def distance(self, aug_px, ref_px, ref_index):
+        """Pre-processed batches [n,h,w,8] / [m,h,w,8] (same h, w) and ref_index (host ints or a tensor, one per augmentation)
+        -> fp32 [n] on the device.  ref_index is validated HERE (the kernel trusts it)."""
+        n, m = aug_px.shape[0], ref_px.shape[0]
+        if tuple(aug_px.shape[1:]) != tuple(ref_px.shape[1:]):
+            raise ValueError(f"LPIPS needs both images of a pair at one size, got {tuple(aug_px.shape[1:3])} and {tuple(ref_px.shape[1:3])}")
+        idx = np.asarray(ref_index.cpu() if torch.is_tensor(ref_index) else ref_index).astype(np.int64).reshape(-1)
+        if idx.size != n or (idx.size and (idx.min() < 0 or idx.max() >= m)):
+            raise ValueError(f"ref_index must hold {n} values in [0, {m})")
+        idx_d = ops.h2d(torch.from_numpy(idx.astype(np.int32)), aug_px.device)
+        fa, fr = self.features(aug_px), self.features(ref_px)
+        dist = torch.empty((n,), device=aug_px.device, dtype=torch.float32)
+        ws = torch.empty((n * ops._lib.LPIPS_MAX_BLOCKS,), device=aug_px.device, dtype=torch.float32)
+        for i, (a, r) in enumerate(zip(fa, fr)):
+            ch = self.cfg["channels"][i]
+            ops.lpips_layer(a[..., :ch] if a.shape[-1] != ch else a, r[..., :ch] if r.shape[-1] != ch else r, idx_d, self.lin[i],
+                            dist, accumulate=i > 0, workspace=ws)
+        return dist
+
+    def forward(self, aug_u8, ref_u8, ref_index, resize=(256, 256), grey=True):
+        """Two device u8 batches [n,H,W,3] / [m,H',W',3] -> fp32 [n]: d(ref_u8[ref_index[j]], aug_u8[j]).  `resize=None` keeps the
+        sizes; a pair of unequal sizes is then a ValueError (the reference would fail inside the network)."""
+        if not resize and tuple(aug_u8.shape[1:3]) != tuple(ref_u8.shape[1:3]):
+            raise ValueError(f"LPIPS without resize needs equal sizes, got {tuple(aug_u8.shape[1:3])} and {tuple(ref_u8.shape[1:3])}")
+        return self.distance(self.preprocess(aug_u8, resize, grey), self.preprocess(ref_u8, resize, grey), ref_index)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # checkpoints
 # ---------------------------------------------------------------------------------------------------------------------
@@ -313,6 +398,60 @@ def filter_checkpoints(ds_utils, weights_dir, semantic=True, confidence=True):
     return rn, cp
 
 
+def lpips_checkpoints(weights_dir):
+    """(torchvision AlexNet file, lpips `alex.pth`) under `<weights_dir>/lpips/` -- `alexnet*.pth` (torchvision ships it as
+    alexnet-owt-7be5be79.pth) and `alex.pth` -- or (None, None) when synthetic filter weights were asked for.  The rule of
+    `filter_checkpoints`: a missing file is a FileNotFoundError unless SASPA_SYNTHETIC_FILTERS=1."""
+    d = Path(weights_dir, "lpips") if weights_dir else None
+    nets = sorted(p for p in d.glob("alexnet*.pth")) if d else []
+    lin = d / "alex.pth" if d else None
+    if len(nets) == 1 and lin.exists():
+        return str(nets[0]), str(lin)
+    if len(nets) > 1:
+        raise FileNotFoundError(f"Found {len(nets)} alexnet*.pth files in {d}. Expected 1")
+    if synthetic_filters_allowed():
+        return None, None
+    raise FileNotFoundError(
+        f"LPIPS filter: {d or '<WEIGHTS_DIR>/lpips'} must hold torchvision's AlexNet weights (alexnet*.pth) and the lpips package's "
+        "alex.pth.  Give WEIGHTS_DIR, set LPIPS_MIN = LPIPS_MAX = None, or opt in to synthetic filter weights with "
+        "SASPA_SYNTHETIC_FILTERS=1")
+
+
+N_PARAMS_ALEX_FEATURES, N_PARAMS_LPIPS_LIN = 2469696, 1152
+
+
+def load_lpips_alex(alex_path, lin_path):
+    """The two checkpoints -> one fp32 state dict with the keys `weights.lpips_alex_spec` names (the classifier half of the
+    torchvision file is dropped; a `net.`/`module.` prefix is tolerated)."""
+    sd = {}
+    for path, keep in ((alex_path, "features."), (lin_path, "lin")):
+        ck = torch.load(path, map_location="cpu", weights_only=True)
+        ck = ck["state_dict"] if "state_dict" in ck else ck
+        for k, v in ck.items():
+            k = k.replace("module.", "")
+            if torch.is_tensor(v) and k.startswith(keep):
+                sd[k] = v.float()
+    want = {n: tuple(shape) for n, shape, _ in W.lpips_alex_spec(LPIPS_ALEX)}
+    bad = [n for n, shape in want.items() if n not in sd or tuple(sd[n].shape) != shape]
+    if bad:
+        raise KeyError(f"LPIPS checkpoints {alex_path}, {lin_path}: missing / mis-shaped tensors {bad[:4]}")
+    sd = {n: sd[n] for n in want}
+    nf = sum(v.numel() for k, v in sd.items() if k.startswith("features."))
+    assert (nf, sum(v.numel() for v in sd.values()) - nf) == (N_PARAMS_ALEX_FEATURES, N_PARAMS_LPIPS_LIN)
+    return sd
+
+
+def build_lpips(dev, weights_dir=None):
+    """The LPIPS model of the lpips_min / lpips_max filter and the diversity measure; checkpoints by `lpips_checkpoints`."""
+    net, lin = lpips_checkpoints(weights_dir)
+    if net:
+        sd = load_lpips_alex(net, lin)
+    else:
+        logging.warning("LPIPS filter: SASPA_SYNTHETIC_FILTERS=1 -> SYNTHETIC AlexNet / lin weights; its distances are those of a random model")
+        sd = W.synth_state_dict("lpips_alex", LPIPS_ALEX, 13)
+    return LpipsAlex(sd, LPIPS_ALEX, dev)
+
+
 def build_filters(ds_utils, dev, semantic=True, confidence=True, weights_dir=None, top_k=10, tokenizer=None):
     """The filter models for a dataset.  `weights_dir` holds `clip/RN50.pt` and `checkpoints/<dataset>/*.pth` (the
     reference's `all_utils/checkpoints/<name>/`).  A missing checkpoint is an error (filter_checkpoints); only with
@@ -354,16 +493,79 @@ def _image_size(path):
         return im.size[1], im.size[0]
 
 
-def apply_filters(mapping, original_images_paths, ds_utils, dev, semantic=None, confidence=None, batch_size=32):
+def _load_original_u8(path):
+    """An original for the LPIPS filter as u8 RGB.  The reference calls `convert("L")` on whatever mode the file decodes to; here
+    everything that is not RGB or L (RGBA, CMYK, P ...) goes through `convert("RGB")` first and the device computes the luma."""
+    from PIL import Image
+    with Image.open(path) as im:
+        return np.asarray(im.convert("RGB"))
+
+
+def lpips_bounds(lpips_min, lpips_max):
+    """The reference applies `lpips_min <= d <= lpips_max` when `lpips_min or lpips_max` (all_utils/utils.py:377-379) and dies with a
+    TypeError inside its loop when only one is given; here that is a ValueError before anything is read.  -> enabled?"""
+    if not (lpips_min or lpips_max):
+        return False
+    if lpips_min is None or lpips_max is None:
+        raise ValueError(f"the LPIPS filter needs both bounds (lpips_min = {lpips_min}, lpips_max = {lpips_max})")
+    return True
+
+
+def _refs_on_device(model, refs, dev, resize, grey, want_hw=None):
+    """Pre-process host originals (mixed sizes) one size group at a time -> [m,h,w,8] in the order given."""
+    if not resize:
+        for r in refs:
+            if want_hw is not None and tuple(r.shape[:2]) != tuple(want_hw):
+                raise ValueError(f"LPIPS without resize needs equal sizes, got {tuple(r.shape[:2])} and {tuple(want_hw)}")
+    out = [None] * len(refs)
+    by_size = {}
+    for i, r in enumerate(refs):
+        by_size.setdefault(r.shape[:2], []).append(i)
+    for _, ids in sorted(by_size.items()):
+        px = model.preprocess(ops.h2d(torch.from_numpy(np.stack([refs[i] for i in ids])), dev), resize, grey)
+        for k, i in enumerate(ids):
+            out[i] = px[k:k + 1]
+    return torch.cat(out).contiguous() if len(out) > 1 else out[0]
+
+
+def lpips_pair_distances(model, pairs, dev=None, resize=(256, 256), grey=True, batch_size=32):
+    """[(original path, augmented path)] -> [float] LPIPS distances, batched by augmented-image size; an original is decoded once
+    per run of consecutive pairs that share it."""
+    dev = model.dev if dev is None else dev
+    groups = {}
+    for k, (op, ap) in enumerate(pairs):
+        groups.setdefault(_image_size(ap), []).append(k)
+    out = [0.0] * len(pairs)
+    for size, ks in sorted(groups.items()):
+        for i in range(0, len(ks), batch_size):
+            chunk = ks[i:i + batch_size]
+            refs, idx, last = [], [], None
+            for k in chunk:
+                if pairs[k][0] != last:
+                    last = pairs[k][0]
+                    refs.append(_load_original_u8(last))
+                idx.append(len(refs) - 1)
+            aug = ops.h2d(torch.from_numpy(np.stack([_load_original_u8(pairs[k][1]) for k in chunk])), dev)
+            d = model.distance(model.preprocess(aug, resize, grey), _refs_on_device(model, refs, dev, resize, grey, size), idx)
+            for k, v in zip(chunk, d.cpu().tolist()):
+                out[k] = v
+    return out
+
+
+def apply_filters(mapping, original_images_paths, ds_utils, dev, semantic=None, confidence=None, batch_size=32, lpips=None,
+                  lpips_min=None, lpips_max=None, resize=(256, 256)):
     """mapping: {original file name: [augmented paths]} as `match_augmented_images` builds it (every original present).
     Returns (filtered mapping, counters).  Per original image the reference first drops the augmentations whose
     classifier top-k misses the source label, then those CLIP does not recognise as the meta class; both decisions are
     per augmented image and independent, so they are evaluated in batches (grouped by image size) and combined.
     Memory: a first pass reads only the PNG headers to group the paths by size; pixels are decoded per batch on a
-    prefetch thread, so at most two batches are resident on the host (a real dataset has 13-16k augmentations of ~1 MB)."""
+    prefetch thread, so at most two batches are resident on the host (a real dataset has 13-16k augmentations of ~1 MB).
+    `lpips` (an LpipsAlex) with both bounds adds the reference's second filter, between the two (:377-381): the augmented batch
+    already on the device is reused, every original is decoded once per run of consecutive augmentations of a batch, and a dropped
+    image is counted once, under the first filter that drops it (top-k, then LPIPS, then semantic)."""
     from concurrent.futures import ThreadPoolExecutor
     if dev is None:
-        for m in (semantic, confidence):
+        for m in (semantic, confidence, lpips):
             if m is not None:
                 dev = m.dev
                 break
@@ -375,27 +577,46 @@ def apply_filters(mapping, original_images_paths, ds_utils, dev, semantic=None, 
     work = [(name, ap) for name, aps in mapping.items() for ap in aps]
     keep = {}
     counters = dict(not_in_top_k=0, semantic=0)
+    use_lpips = lpips is not None and lpips_bounds(lpips_min, lpips_max)
+    if use_lpips:
+        counters["lpips"] = 0
+        orig_path = {Path(ip).name: ip for ip in original_images_paths}
     groups = {}
     for name, ap in work:
         groups.setdefault(_image_size(ap), []).append((name, ap))
     chunks = [items[i:i + batch_size] for _, items in sorted(groups.items()) for i in range(0, len(items), batch_size)]
 
     def decode(chunk):
-        return np.stack([_load_u8(ap) for _, ap in chunk])
+        pixels = np.stack([_load_u8(ap) for _, ap in chunk])
+        refs, idx, last = [], [], None
+        if use_lpips:
+            for name, _ in chunk:
+                if name != last:
+                    last = name
+                    refs.append(_load_original_u8(orig_path[name]))
+                idx.append(len(refs) - 1)
+        return pixels, refs, idx
 
     with ThreadPoolExecutor(max_workers=1) as pool:
         nxt = pool.submit(decode, chunks[0]) if chunks else None
         for ci, chunk in enumerate(chunks):
-            pixels = nxt.result()
+            pixels, refs, idx = nxt.result()
             nxt = pool.submit(decode, chunks[ci + 1]) if ci + 1 < len(chunks) else None
             batch = ops.h2d(torch.from_numpy(pixels), dev)
             ok_c = confidence.passes(batch, [labels[name] for name, _ in chunk]) if confidence is not None else np.ones(len(chunk), bool)
             ok_s = semantic.passes(batch) if semantic is not None else np.ones(len(chunk), bool)
-            for (name, ap), c_ok, s_ok in zip(chunk, ok_c, ok_s):
+            ok_l = np.ones(len(chunk), bool)
+            if use_lpips:
+                ref_px = _refs_on_device(lpips, refs, dev, resize, True, pixels.shape[1:3])
+                d = lpips.distance(lpips.preprocess(batch, resize, True), ref_px, idx).cpu().numpy().astype(np.float64)   # host control flow
+                ok_l = (lpips_min <= d) & (d <= lpips_max)
+            for (name, ap), c_ok, l_ok, s_ok in zip(chunk, ok_c, ok_l, ok_s):
                 if not c_ok:
-                    counters["not_in_top_k"] += 1          # dropped first: never reaches the semantic filter (:357-366)
+                    counters["not_in_top_k"] += 1          # dropped first: never reaches the other filters (:357-366)
+                elif not l_ok:
+                    counters["lpips"] += 1                 # second (:377-381)
                 elif not s_ok:
                     counters["semantic"] += 1
-                keep[ap] = bool(c_ok and s_ok)
+                keep[ap] = bool(c_ok and l_ok and s_ok)
     out = {name: [ap for ap in aps if keep[ap]] for name, aps in mapping.items()}
     return out, counters

@@ -1076,6 +1076,54 @@ def signsqrt_l2norm(x, eps, scale=1.0):
     return out
 
 
+def lpips_layer(a, r, ref_index, w, dist=None, accumulate=False, workspace=None):
+    """One LPIPS level (saspa_lpips_layer): a [n, ..., C] / r [m, ..., C] channels-last features of the same dtype and pixel count
+    (the conv outputs as they are: any pixel pitch >= C), ref_index device int32 [n] (values in [0, m): the CALLER's guarantee, the
+    kernel does not look), w fp32 [C] >= 0 -> fp32 [n]:  dist (+)= mean_p sum_c w_c (a_hat - r_hat[ref_index])^2."""
+    _check_dev(a, r, ref_index, w, dist, workspace)
+    if r.dim() != a.dim() or a.dtype != r.dtype or tuple(a.shape[1:]) != tuple(r.shape[1:]):
+        raise ValueError(f"feature maps {tuple(a.shape)} {a.dtype} / {tuple(r.shape)} {r.dtype} do not pair up")
+    n, m, c = a.shape[0], r.shape[0], a.shape[-1]
+    if n <= 0 or m <= 0:
+        raise ValueError("empty batch")
+
+    def rows(t):
+        if t.dim() not in (3, 4):
+            raise ValueError("features must be [n, hw, C] or [n, h, w, C]")
+        t4 = t.unsqueeze(1) if t.dim() == 3 else t
+        return _pitch4(t4), t4.shape[1] * t4.shape[2]
+    (lda, hw), (ldr, _) = rows(a), rows(r)
+    if ref_index.dtype != torch.int32 or ref_index.dim() != 1 or ref_index.numel() != n or not ref_index.is_contiguous():
+        raise ValueError("ref_index must be a contiguous int32 [n] device tensor")
+    if w.dtype != torch.float32 or w.numel() != c or not w.is_contiguous():
+        raise ValueError(f"w must be a contiguous fp32 [{c}] vector")
+    if c % 8 or c > _lib.LPIPS_MAX_C:
+        raise ValueError(f"C = {c}: the kernel takes multiples of 8 up to {_lib.LPIPS_MAX_C}")
+    if dist is None:
+        if accumulate:
+            raise ValueError("accumulate needs the vector to add to")
+        dist = torch.empty((n,), device=a.device, dtype=torch.float32)
+    elif dist.dtype != torch.float32 or dist.numel() != n or not dist.is_contiguous():
+        raise ValueError("dist must be a contiguous fp32 [n] vector")
+    if workspace is None:
+        workspace = torch.empty((n * _lib.LPIPS_MAX_BLOCKS,), device=a.device, dtype=torch.float32)
+    elif workspace.dtype != torch.float32 or workspace.numel() < n * _lib.LPIPS_MAX_BLOCKS or not workspace.is_contiguous():
+        raise ValueError(f"workspace must hold n * {_lib.LPIPS_MAX_BLOCKS} fp32")
+    _lib.check(_L().saspa_lpips_layer(_dt(a), _ptr(a), lda, _ptr(r), ldr, _ptr(ref_index), _ptr(w), _ptr(dist), _ptr(workspace), n, hw,
+                                      c, int(bool(accumulate)), _stream()), "saspa_lpips_layer")
+    return dist
+
+
+def u8_luma(img_u8):
+    """PIL convert("L").convert("RGB") of a device u8 [..., 3] tensor (saspa_u8_luma; integer exact)."""
+    _check_dev(img_u8)
+    if img_u8.dtype != torch.uint8 or img_u8.dim() < 1 or img_u8.shape[-1] != 3 or not img_u8.is_contiguous() or img_u8.numel() == 0:
+        raise ValueError("u8_luma expects a contiguous, non-empty u8 [..., 3] tensor")
+    out = torch.empty_like(img_u8)
+    _lib.check(_L().saspa_u8_luma(_ptr(img_u8), _ptr(out), img_u8.numel() // 3, _stream()), "saspa_u8_luma")
+    return out
+
+
 def embed_tokens(ids, tok, pos, npos):
     _check_dev(ids, tok, pos)
     lib = _L()

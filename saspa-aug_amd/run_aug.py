@@ -150,6 +150,8 @@ class Settings:
     CONTROLNET_CONDITIONING_SCALE: float = 0.75
     SEMANTIC_FILTERING: int = 1
     MODEL_CONFIDENCE_BASED_FILTERING: int = 1
+    LPIPS_MIN: float = None            # both or neither (:551-552): keep lpips_min <= LPIPS_alex(original, augmented) <= lpips_max
+    LPIPS_MAX: float = None
     STYLE_IMG_FROM_DIFF_IMG: bool = True   # blip_diffusion: subject image = another image of the same class (:548)
     # additions of this build
     BATCH_SIZE: int = 8
@@ -735,18 +737,19 @@ def host_threads(local_world=1):
     return max(1, min(4, n // max(1, int(local_world))))
 
 
-def main(s: Settings, ds_utils=None, batch_generator=None, dist=None, pipe=None, filter_models=None):
+def main(s: Settings, ds_utils=None, batch_generator=None, dist=None, pipe=None, filter_models=None, lpips_model=None):
     """`_main` with torch's CPU pool held at `host_threads()` for the duration of the run (restored afterwards)."""
     world = dist.get_world_size() if dist is not None else 1
     before = torch.get_num_threads()
     torch.set_num_threads(host_threads(int(os.environ.get("LOCAL_WORLD_SIZE", world))))
     try:
-        return _main(s, ds_utils=ds_utils, batch_generator=batch_generator, dist=dist, pipe=pipe, filter_models=filter_models)
+        return _main(s, ds_utils=ds_utils, batch_generator=batch_generator, dist=dist, pipe=pipe, filter_models=filter_models,
+                     lpips_model=lpips_model)
     finally:
         torch.set_num_threads(before)
 
 
-def _main(s: Settings, ds_utils=None, batch_generator=None, dist=None, pipe=None, filter_models=None):
+def _main(s: Settings, ds_utils=None, batch_generator=None, dist=None, pipe=None, filter_models=None, lpips_model=None):
     """The generation loop.  `batch_generator` is injectable for host-logic tests; the default
     builds the HIP pipeline (fails loudly without an MI355X).  `filter_models` = (SemanticFilter | None,
     ConfidenceFilter | None) to reuse built filter models; None builds them on s.DEVICE when a filter flag is set."""
@@ -785,9 +788,15 @@ def _main(s: Settings, ds_utils=None, batch_generator=None, dist=None, pipe=None
     else:                                           # gpt-meta_class, ALIA: one prompt per line
         prompts = read_prompts(prompts_file)
         logging.info(f"Read {len(prompts)} prompts from {prompts_file}")
-    aug_json_path = utils.get_aug_json_path(output_folder, semantic_filtering=s.SEMANTIC_FILTERING,
+    aug_json_path = utils.get_aug_json_path(output_folder, lpips_min=s.LPIPS_MIN, lpips_max=s.LPIPS_MAX,
+                                            semantic_filtering=s.SEMANTIC_FILTERING,
                                             model_confidence_based_filtering=s.MODEL_CONFIDENCE_BASED_FILTERING)
     logging.info(f"Augmented json path will be at: \n{aug_json_path}")
+    if lpips_model is None and (s.LPIPS_MIN or s.LPIPS_MAX):
+        # the same rule for the LPIPS filter: both bounds, and its two checkpoints, before anything is generated
+        from . import filters as _filters
+        _filters.lpips_bounds(s.LPIPS_MIN, s.LPIPS_MAX)
+        _filters.lpips_checkpoints(s.WEIGHTS_DIR)
     if filter_models is None and (s.SEMANTIC_FILTERING or s.MODEL_CONFIDENCE_BASED_FILTERING):
         # fail BEFORE hours of generation, not after: a filter flag with no checkpoint behind it is an error unless
         # synthetic filter weights were asked for explicitly (SASPA_SYNTHETIC_FILTERS=1)
@@ -927,12 +936,12 @@ def _main(s: Settings, ds_utils=None, batch_generator=None, dist=None, pipe=None
                      f"{sum(i.skip for i in items)} skipped (already existed)")
         n_files = len(list(Path(output_folder).glob("*.*")))
         # the filter stage runs on this rank's GPU whether the models are built here or handed in
-        fdev = torch.device(s.DEVICE) if (s.SEMANTIC_FILTERING or s.MODEL_CONFIDENCE_BASED_FILTERING) else None
+        fdev = torch.device(s.DEVICE) if (s.SEMANTIC_FILTERING or s.MODEL_CONFIDENCE_BASED_FILTERING or s.LPIPS_MIN or s.LPIPS_MAX) else None
         json_path = utils.create_json_of_image_name_to_augmented_images_paths(
-            ds_utils, output_folder, semantic_filtering=s.SEMANTIC_FILTERING,
+            ds_utils, output_folder, lpips_min=s.LPIPS_MIN, lpips_max=s.LPIPS_MAX, semantic_filtering=s.SEMANTIC_FILTERING,
             model_confidence_based_filtering=s.MODEL_CONFIDENCE_BASED_FILTERING, init_log=False,
             original_images_paths=ds_utils.original_images_paths, min_files=min(10, max(1, n_files)),
-            filter_models=filter_models, weights_dir=s.WEIGHTS_DIR, device=fdev)
+            filter_models=filter_models, weights_dir=s.WEIGHTS_DIR, device=fdev, lpips_model=lpips_model)
     if dist is not None:
         dist.barrier()
     return dict(items=items, status=status, json_path=json_path, output_folder=output_folder, mine=mine, n_batches=len(batches),

@@ -7,8 +7,9 @@ interface for this path (same names, argument meaning and outputs):
   get_aug_json_path             all_utils/utils.py:194-218
   create_json_of_image_name_to_augmented_images_paths   all_utils/utils.py:221-465 (PNG integrity
         sweep, stem matching, JSON layout, and the semantic / model-confidence filters, which run
-        on the gfx950 kernels: saspa_aug_amd/filters.py; LPIPS / per-class CLIP / ALIA filters are
-        baseline branches and raise NotImplementedError)
+        on the gfx950 kernels, as does the LPIPS min / max filter: saspa_aug_amd/filters.py; the per-class CLIP / ALIA
+        filters are baseline branches and raise NotImplementedError)
+  calc_lpips_given_aug_json     all_utils/utils.py:764-817
   check_folder_of_images_with_pil   all_utils/utils.py:681-703
   init_logging                  all_utils/utils.py:593-612
 
@@ -179,12 +180,19 @@ def create_json_of_image_name_to_augmented_images_paths(dataset, augmented_image
                                                         semantic_filtering=False, model_confidence_based_filtering=False,
                                                         conf_top_k: int = 10, filter_confidence_higher_than: int = None,
                                                         init_log=True, alia_conf_filtering=False, original_images_paths=None,
-                                                        min_files=10, filter_models=None, weights_dir=None, device=None):
+                                                        min_files=10, filter_models=None, weights_dir=None, device=None,
+                                                        lpips_model=None):
     """`dataset` may be a dataset name (resolved through dataset_utils.DS_UTILS_DICT) or any
-    object with `.original_images_paths`."""
+    object with `.original_images_paths`.  `filter_models` = (semantic, confidence) models built by the caller, `lpips_model` an
+    `filters.LpipsAlex`; each is built here from `weights_dir` when its filter is on and it is not given.  `lpips_min` / `lpips_max`
+    keep an augmented image when `lpips_min <= LPIPS_alex(original, augmented) <= lpips_max` (both grey, resized to `resize`); the
+    reference needs both once either is set (it raises a TypeError in its loop otherwise) -- here one bound alone is a ValueError."""
     assert not (clip_filtering and model_confidence_based_filtering)
-    if any([lpips_min, lpips_max, clip_filtering, alia_conf_filtering]):
-        raise NotImplementedError("LPIPS / CLIP-per-class / ALIA filters are baseline branches (out of scope, SURVEY 2 row 7)")
+    if any([clip_filtering, alia_conf_filtering]):
+        raise NotImplementedError("CLIP-per-class / ALIA filters are baseline branches (out of scope, SURVEY 2 row 7)")
+    if (lpips_min or lpips_max) and (lpips_min is None or lpips_max is None):
+        raise ValueError(f"the LPIPS filter needs both bounds (lpips_min = {lpips_min}, lpips_max = {lpips_max})")
+    lpips_filtering = bool(lpips_min or lpips_max)
     if not str(augmented_image_folder_path).endswith("/images"):
         augmented_image_folder_path = str(Path(augmented_image_folder_path) / "images")
     json_path = get_aug_json_path(augmented_image_folder_path, lpips_min, lpips_max, clip_filtering, clip_filtering_discount,
@@ -203,25 +211,37 @@ def create_json_of_image_name_to_augmented_images_paths(dataset, augmented_image
         raise FileNotFoundError(f"augmented_image_folder_path = {augmented_image_folder_path} doesn't exist or has less "
                                 f"than {min_files} images")
     mapping = match_augmented_images(original_images_paths, os.listdir(augmented_image_folder_path), augmented_image_folder_path)
-    if semantic_filtering or model_confidence_based_filtering:
-        # the filter stage: CLIP-RN50 semantic filter + baseline-classifier top-k filter on the gfx950 kernels
+    if semantic_filtering or model_confidence_based_filtering or lpips_filtering:
+        # the filter stage: CLIP-RN50 semantic filter, baseline-classifier top-k filter and LPIPS min / max filter on
+        # the gfx950 kernels
         from . import filters
         if isinstance(dataset, str):
             from . import dataset_utils
             dataset = dataset_utils.DS_UTILS_DICT[dataset](print_func=logging.info)
-        if filter_models is None:
+        need_two = bool(semantic_filtering or model_confidence_based_filtering) and filter_models is None
+        need_lpips = lpips_filtering and lpips_model is None
+        if need_two or need_lpips:
             if device is None:
                 device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
             if device is None:
-                raise RuntimeError("the semantic / model-confidence filters run on the MI355X only (no CPU path); pass "
-                                   "semantic_filtering=0, model_confidence_based_filtering=0 to write the unfiltered aug.json")
+                raise RuntimeError("the semantic / model-confidence / LPIPS filters run on the MI355X only (no CPU path); pass "
+                                   "semantic_filtering=0, model_confidence_based_filtering=0 and no lpips bounds to write the "
+                                   "unfiltered aug.json")
+        if need_two:
             filter_models = filters.build_filters(dataset, device, bool(semantic_filtering), bool(model_confidence_based_filtering),
                                                   weights_dir, conf_top_k)
-        sem, conf = filter_models
+        if need_lpips:
+            lpips_model = filters.build_lpips(device, weights_dir)
+        sem, conf = filter_models if filter_models is not None else (None, None)
         if filter_confidence_higher_than:
             raise NotImplementedError("filter_confidence_higher_than is an ablation knob of the reference (unused by run_aug)")
         mapping, counters = filters.apply_filters(mapping, original_images_paths, dataset, device, sem if semantic_filtering else None,
-                                                  conf if model_confidence_based_filtering else None)
+                                                  conf if model_confidence_based_filtering else None,
+                                                  lpips=lpips_model if lpips_filtering else None, lpips_min=lpips_min,
+                                                  lpips_max=lpips_max, resize=resize)
+        if lpips_filtering:
+            logging.info(f"For filter = lpips_min, filtered {counters['lpips']} images")
+            logging.info(f"For filter = lpips_max, filtered {counters['lpips']} images")
         if semantic_filtering:
             logging.info(f"For filter = semantic_filtering, filtered {counters['semantic']} images")
         if model_confidence_based_filtering:
@@ -235,6 +255,45 @@ def create_json_of_image_name_to_augmented_images_paths(dataset, augmented_image
         counts[len(v)] = counts.get(len(v), 0) + 1
     logging.info(f"dict_num_augmentations_per_image = {dict(sorted(counts.items()))}")
     return json_path
+
+
+def calc_lpips_given_aug_json(dataset, aug_json, net="alex", compute_on=3000, resize_to=None, lpips_model=None, weights_dir=None,
+                              device=None):
+    """Diversity measure of a finished aug.json (all_utils/utils.py:764-817): the LPIPS distance of every (original, augmented)
+    pair -- RGB, no grey conversion, [0, 1] mapped to [-1, 1], resized to `resize_to` = (width, height) when given -- over at most
+    `compute_on` randomly sampled originals.  Returns (mean, population std, values).  Only net="alex" exists here.  Images that
+    decode to something other than RGB go through `convert("RGB")`, as in the reference; without `resize_to` a pair of unequal
+    sizes is a ValueError (the reference fails inside the network and returns (None, None, None))."""
+    if net != "alex":
+        raise NotImplementedError(f"LPIPS net={net!r}: only the AlexNet variant is built (the reference's filter uses it)")
+    if not Path(aug_json).exists():
+        raise FileNotFoundError(f"File not found: {aug_json}")
+    with open(aug_json, "r") as f:
+        aug_data = json.load(f)
+    if len(aug_data) > compute_on:
+        aug_data = dict(random.sample(sorted(aug_data.items()), compute_on))
+    if isinstance(dataset, str):
+        from . import dataset_utils
+        dataset = dataset_utils.DS_UTILS_DICT[dataset]()
+    from . import filters
+    all_src_paths = dataset.original_images_paths
+    pairs = []
+    for file_name, aug_list in aug_data.items():
+        if not aug_list:
+            continue
+        file_path = [x for x in all_src_paths if file_name in x]
+        assert len(file_path) == 1, f"list length: {len(file_path)} for {file_name}"
+        pairs += [(file_path[0], aug) for aug in aug_list]
+    if lpips_model is None:
+        if device is None:
+            if not torch.cuda.is_available():
+                raise RuntimeError("calc_lpips_given_aug_json runs on the MI355X only (no CPU path)")
+            device = torch.device("cuda", torch.cuda.current_device())
+        lpips_model = filters.build_lpips(device, weights_dir)
+    values = filters.lpips_pair_distances(lpips_model, pairs, device, resize=resize_to, grey=False)
+    mean, std = (float(np.mean(values)), float(np.std(values))) if values else (float("nan"), float("nan"))
+    logging.info(f"Mean: {mean}, Std: {std}")
+    return mean, std, values
 
 
 def _log_file_for(logdir, logfile, stamp):

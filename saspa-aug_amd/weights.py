@@ -363,7 +363,20 @@ def hed_spec(cfg):
     return spec
 
 
-SPECS.update(clip_rn50=clip_rn50_spec, cal=wsdan_cal_spec, vae_enc=vae_encoder_spec, hed=hed_spec)
+LPIPS_ALEX_CONVS = ((0, 11), (3, 5), (6, 3), (8, 3), (10, 3))      # (index in torchvision AlexNet.features, window)
+
+
+def lpips_alex_spec(cfg):
+    """torchvision AlexNet `features.{0,3,6,8,10}.{weight,bias}` + lpips v0.1 `lin{0..4}.model.1.weight` ([1, C, 1, 1], >= 0)."""
+    spec, cin = [], 3
+    for (idx, k), co in zip(LPIPS_ALEX_CONVS, cfg["channels"]):
+        spec += [(f"features.{idx}.weight", (co, cin, k, k), "w"), (f"features.{idx}.bias", (co,), "bias")]
+        cin = co
+    spec += [(f"lin{i}.model.1.weight", (1, c, 1, 1), "lin") for i, c in enumerate(cfg["channels"])]
+    return spec
+
+
+SPECS.update(clip_rn50=clip_rn50_spec, cal=wsdan_cal_spec, vae_enc=vae_encoder_spec, hed=hed_spec, lpips_alex=lpips_alex_spec)
 
 
 def fold_bn(conv_w, sd, bn_pfx, eps=1e-5):
@@ -479,6 +492,8 @@ def synth_state_dict(kind, cfg, seed=0):
             t = torch.randn(shape, generator=g) / math.sqrt(shape[0])
         elif k == "w_fc":           # classifier over unit-norm x 100 features: keeps the logits O(1) apart
             t = torch.randn(shape, generator=g) * 0.05
+        elif k == "lin":            # LPIPS channel weights: non-negative
+            t = torch.rand(shape, generator=g) * (2.0 / shape[1])
         elif k == "logit_scale":
             t = torch.tensor(math.log(100.0))
         elif k == "hed_norm":       # per-channel pixel mean on the 0..255 scale

@@ -436,6 +436,30 @@ int saspa_signsqrt_l2norm(const float* x, long long ldx, float* y, long long ldy
 #define SASPA_LPIPS_MAX_BLOCKS 64
 int saspa_lpips_layer(int dtype, const void* a, int lda, const void* r, int ldr, const int* ref_index, const float* w, float* dist,
                       float* workspace, int n, int hw, int C, int accumulate, void* stream);
+/* The class head of a filter decision: one row of class logits, its softmax and the entries a decision looks at, on the device --
+ * the per-class CLIP filter of the Real-Guidance baseline (all_utils/utils.py:180-191, :383-393: softmax over ALL class prompts, the
+ * source image's class >= 1 / n_classes / discount) and the too-high-confidence test on the baseline classifier's logits (:368-373).
+ * One launch per batch, one workgroup of 256 threads per row, fp32 throughout.
+ *   embedding mode (cls != NULL): feat [rows][ldf] = UNNORMALISED image embeddings of width D, cls [C][ldc] = unit text rows;
+ *       u = feat / sqrt(sum feat^2) (normalize != 0; feat as it is otherwise),  z_c = scale * sum_d u_d cls[c][d]
+ *   logits mode (cls == NULL, D == C): feat [rows][ldf] holds the logits,  z_c = scale * feat[c]
+ * labels: rows DEVICE int32.  Per row:
+ *   stats[4 * row + 0..3] = z_label,  p_label = exp(z_label - m) / sum_c exp(z_c - m) with m = max_c z_c,  m,  log-sum-exp of the row
+ *   idx[2 * row + 0..1]   = argmax (the LOWEST c with z_c == m),  the number of c with z_c strictly greater than z_label
+ *   logits [rows][ldl] (optional, may be NULL) = z
+ * A label outside [0, C) cannot be seen from the host: that row gets four NaN statistics and two -1 indices (its logits are still
+ * written).  Every sum has a fixed shape (lanes stride the row, xor-butterflies inside a wave, the four waves in order through
+ * LDS); no atomics; a row never looks at another row, so its results are bit-identical from run to run, for every batch size and
+ * every position in the batch.
+ * Host-side validation: null feat / labels / stats / idx or rows < 1 -> SASPA_EINVAL; feat / cls / logits not 16-byte aligned,
+ * ldf / ldc / ldl not multiples of 4 or shorter than the row, stats / idx / labels not 4-byte aligned -> SASPA_EALIGN;
+ * C < 1, D < 1, D > SASPA_CLASS_HEAD_MAX_D, C > SASPA_CLASS_HEAD_MAX_C (the LDS plan: the embedding and the row of logits are
+ * resident, 4 * (D + C) bytes), or D != C in logits mode -> SASPA_ERANGE.  (CLIP RN50: D = 1024; the largest class list of the
+ * reference's datasets: C = 431.) */
+#define SASPA_CLASS_HEAD_MAX_D 2048
+#define SASPA_CLASS_HEAD_MAX_C 4096
+int saspa_class_head(const float* feat, int ldf, const float* cls, int ldc, const int* labels, float scale, int normalize,
+                     float* stats, int* idx, float* logits, int ldl, int rows, int D, int C, void* stream);
 
 /* ---- cv2.resize, 8-bit RGB [n][h][w][3] -> [n][dh][dw][3] (all_utils/utils.py:58-79 `resize_image`) -------
  * saspa_resize_taps_u8: OpenCV's separable fixed-point filters; xofs / yofs = first tap index per destination sample,

@@ -14,7 +14,8 @@ exist; the exit code is non-zero if that fails too.  SASPA_FORK=0 by hand rules 
 
 Environment overlays (optional): SASPA_DATASET, SASPA_WEIGHTS_DIR, SASPA_PROMPTS_FILE,
 SASPA_NUM_INFERENCE_STEPS, SASPA_NUM_PER_IMAGE, SASPA_PRECISION, SASPA_BASE_MODEL (sd_v1.5 | blip_diffusion | sd_xl-turbo),
-SASPA_LPIPS_MIN / SASPA_LPIPS_MAX (the LPIPS filter's bounds; both or neither)."""
+SASPA_LPIPS_MIN / SASPA_LPIPS_MAX (the LPIPS filter's bounds; both or neither), SASPA_CLIP_FILTERING=per_class with
+SASPA_CLIP_FILTERING_DISCOUNT (the per-class CLIP filter; it replaces the model-confidence filter, which it cannot be combined with)."""
 import os
 import sys
 from pathlib import Path
@@ -60,6 +61,10 @@ if __name__ == "__main__":
     MODEL_CONFIDENCE_BASED_FILTERING = 1
     LPIPS_MIN = float(os.environ["SASPA_LPIPS_MIN"]) if os.environ.get("SASPA_LPIPS_MIN") else None
     LPIPS_MAX = float(os.environ["SASPA_LPIPS_MAX"]) if os.environ.get("SASPA_LPIPS_MAX") else None
+    CLIP_FILTERING_TYPE = os.environ.get("SASPA_CLIP_FILTERING") or None      # out of "per_class" only
+    CLIP_FILTERING_DISCOUNT = float(os.environ["SASPA_CLIP_FILTERING_DISCOUNT"]) if os.environ.get("SASPA_CLIP_FILTERING_DISCOUNT") else 1
+    if CLIP_FILTERING_TYPE:
+        MODEL_CONFIDENCE_BASED_FILTERING = 0
     # ---------------------------- this build ----------------------------
     BATCH_SIZE = 8
 
@@ -82,7 +87,7 @@ if __name__ == "__main__":
                    LOW_THRESHOLD_CANNY=LOW_THRESHOLD_CANNY, HIGH_THRESHOLD_CANNY=HIGH_THRESHOLD_CANNY,
                    CONTROLNET_CONDITIONING_SCALE=CONTROLNET_CONDITIONING_SCALE, SEMANTIC_FILTERING=SEMANTIC_FILTERING,
                    MODEL_CONFIDENCE_BASED_FILTERING=MODEL_CONFIDENCE_BASED_FILTERING, LPIPS_MIN=LPIPS_MIN, LPIPS_MAX=LPIPS_MAX,
-                   BATCH_SIZE=BATCH_SIZE,
+                   CLIP_FILTERING_TYPE=CLIP_FILTERING_TYPE, CLIP_FILTERING_DISCOUNT=CLIP_FILTERING_DISCOUNT, BATCH_SIZE=BATCH_SIZE,
                    PRECISION=os.environ.get("SASPA_PRECISION", "bf16"), WEIGHTS_DIR=os.environ.get("SASPA_WEIGHTS_DIR"),
                    PROMPTS_FILE=os.environ.get("SASPA_PROMPTS_FILE"))
     assert s.DATASET in R.dataset_utils.DATASETS_SUPPORTED

@@ -9,6 +9,7 @@ LIB_PATH = os.environ.get("SASPA_HIP_LIB") or os.path.join(_HERE, "libsaspa_hip.
 SASPA_BF16, SASPA_F32, SASPA_F32X3 = 0, 1, 2
 SASPA_EINVAL, SASPA_EALIGN, SASPA_ERANGE = -1, -2, -3      # include/saspa_hip.h
 LPIPS_MAX_C, LPIPS_MAX_BLOCKS = 512, 64                    # SASPA_LPIPS_MAX_C / SASPA_LPIPS_MAX_BLOCKS
+CLASS_HEAD_MAX_D, CLASS_HEAD_MAX_C = 2048, 4096            # SASPA_CLASS_HEAD_MAX_D / SASPA_CLASS_HEAD_MAX_C
 ERRORS = {-1: "SASPA_EINVAL (null pointer / bad size)", -2: "SASPA_EALIGN (16-byte alignment / channel multiple)",
           -3: "SASPA_ERANGE (unsupported shape)"}
 
@@ -144,6 +145,7 @@ SYMBOLS = {
     "saspa_pool2d": (_I, [_I, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "saspa_signsqrt_l2norm": (_I, [_P, _LL, _P, _LL, _I, _LL, _F, _F, _P]),
     "saspa_lpips_layer": (_I, [_I, _P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "saspa_class_head": (_I, [_P, _I, _P, _I, _P, _F, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
     "saspa_resize_taps_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P]),
     "saspa_hed_fuse": (_I, [C.POINTER(HedFuseParams), _P]),
     "saspa_gemm_fp8": (_I, [C.POINTER(GemmF8Params), _P]),

@@ -165,7 +165,138 @@ __global__ __launch_bounds__(64) void lpips_finish_kernel(const float* __restric
   }
 }
 
+// ---- class head ------------------------------------------------------------------------------------------------------------
+// One workgroup (4 waves) per row.  Embedding mode: the row's embedding is staged once in LDS (and scaled to unit length there), then
+// wave w takes the classes w, w + 4, ...: 64 lanes x 16 bytes of the class row per load, an xor-butterfly, lane 0 writes z_c to LDS.
+// The row statistics read z from LDS only.  Every reduction: lanes stride the row, butterfly inside the wave, the four waves in
+// order through LDS -- the same shape for every row whatever else is in the launch.
+struct MaxIdx {
+  float m;
+  int i;
+};
+__device__ __forceinline__ MaxIdx better(MaxIdx a, MaxIdx b) {          // the larger value; of equal values the lower index
+  return (b.m > a.m || (b.m == a.m && b.i < a.i)) ? b : a;
+}
+
+template <bool EMB>
+__global__ __launch_bounds__(256) void class_head_kernel(const float* __restrict__ feat, int ldf, const float* __restrict__ cls, int ldc,
+                                                         const int* __restrict__ labels, float scale, int normalize,
+                                                         float* __restrict__ stats, int* __restrict__ idx, float* __restrict__ logits,
+                                                         int ldl, int D, int C) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  __shared__ float redf[4];
+  __shared__ int redi[4];
+  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float* fr = feat + (long long)row * ldf;
+  float* z = smem;
+  if constexpr (EMB) {
+    float* u = smem;
+    z = smem + ((D + 3) & ~3);
+    float ss = 0.0f;
+    for (int i = tid; i < D; i += 256) {
+      const float v = fr[i];
+      u[i] = v;
+      ss += v * v;
+    }
+    ss = wave_sum(ss);
+    if (lane == 0) redf[wave] = ss;
+    __syncthreads();
+    const float inv = normalize ? 1.0f / sqrtf((redf[0] + redf[1]) + (redf[2] + redf[3])) : 1.0f;
+    for (int i = tid; i < D; i += 256) u[i] *= inv;       // a thread rescales the elements it staged itself
+    __syncthreads();
+    const int D4 = D >> 2;
+    const float4* u4 = reinterpret_cast<const float4*>(u);
+    for (int c = wave; c < C; c += 4) {
+      const float* cr = cls + (long long)c * ldc;
+      const float4* c4 = reinterpret_cast<const float4*>(cr);
+      float acc = 0.0f;
+      for (int j = lane; j < D4; j += 64) {
+        const float4 t = c4[j], v = u4[j];
+        acc += (t.x * v.x + t.y * v.y) + (t.z * v.z + t.w * v.w);
+      }
+      for (int i = (D4 << 2) + lane; i < D; i += 64) acc += cr[i] * u[i];
+      acc = wave_sum(acc);
+      if (lane == 0) z[c] = scale * acc;
+    }
+  } else {
+    for (int c = tid; c < C; c += 256) z[c] = scale * fr[c];
+  }
+  __syncthreads();
+  if (logits) {
+    float* lr = logits + (long long)row * ldl;
+    for (int c = tid; c < C; c += 256) lr[c] = z[c];
+  }
+  // m = max_c z_c and the lowest c that reaches it
+  MaxIdx best{-INFINITY, 0x7fffffff};
+  for (int c = tid; c < C; c += 256) best = better(best, MaxIdx{z[c], c});
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) best = better(best, MaxIdx{__shfl_xor(best.m, o, 64), __shfl_xor(best.i, o, 64)});
+  if (lane == 0) {
+    redf[wave] = best.m;
+    redi[wave] = best.i;
+  }
+  __syncthreads();
+  best = better(better(MaxIdx{redf[0], redi[0]}, MaxIdx{redf[1], redi[1]}), better(MaxIdx{redf[2], redi[2]}, MaxIdx{redf[3], redi[3]}));
+  __syncthreads();
+  const int label = labels[row];
+  const bool valid = (unsigned)label < (unsigned)C;
+  const float zl = valid ? z[label] : 0.0f;
+  float s = 0.0f;
+  int ng = 0;
+  for (int c = tid; c < C; c += 256) {
+    const float v = z[c];
+    s += expf(v - best.m);
+    ng += v > zl ? 1 : 0;
+  }
+  s = wave_sum(s);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) ng += __shfl_xor(ng, o, 64);
+  if (lane == 0) {
+    redf[wave] = s;
+    redi[wave] = ng;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    const float tot = (redf[0] + redf[1]) + (redf[2] + redf[3]);
+    float* st = stats + 4ll * row;
+    int* ix = idx + 2ll * row;
+    if (valid) {
+      st[0] = zl;
+      st[1] = expf(zl - best.m) / tot;
+      st[2] = best.m;
+      st[3] = best.m + logf(tot);
+      ix[0] = best.i;
+      ix[1] = (redi[0] + redi[1]) + (redi[2] + redi[3]);
+    } else {
+      const float nan = __builtin_nanf("");
+      st[0] = st[1] = st[2] = st[3] = nan;
+      ix[0] = ix[1] = -1;
+    }
+  }
+}
+
 }  // namespace
+
+extern "C" int saspa_class_head(const float* feat, int ldf, const float* cls, int ldc, const int* labels, float scale, int normalize,
+                                float* stats, int* idx, float* logits, int ldl, int rows, int D, int C, void* stream) {
+  if (!feat || !labels || !stats || !idx || rows <= 0) return SASPA_EINVAL;
+  if (C < 1 || D < 1 || D > SASPA_CLASS_HEAD_MAX_D || C > SASPA_CLASS_HEAD_MAX_C || (!cls && D != C)) return SASPA_ERANGE;
+  if (!aligned16(feat) || ldf % 4 || ldf < D) return SASPA_EALIGN;
+  if (cls && (!aligned16(cls) || ldc % 4 || ldc < D)) return SASPA_EALIGN;
+  if (logits && (!aligned16(logits) || ldl % 4 || ldl < C)) return SASPA_EALIGN;
+  if ((reinterpret_cast<uintptr_t>(stats) | reinterpret_cast<uintptr_t>(idx) | reinterpret_cast<uintptr_t>(labels)) & 3u) return SASPA_EALIGN;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const dim3 g((unsigned)rows), t(256);
+  if (cls) {
+    const size_t lds = sizeof(float) * (size_t)(((D + 3) & ~3) + C);
+    hipLaunchKernelGGL(class_head_kernel<true>, g, t, lds, s, feat, ldf, cls, ldc, labels, scale, normalize, stats, idx, logits, ldl, D, C);
+  } else {
+    hipLaunchKernelGGL(class_head_kernel<false>, g, t, sizeof(float) * (size_t)C, s, feat, ldf, cls, ldc, labels, scale, normalize, stats,
+                       idx, logits, ldl, D, C);
+  }
+  SASPA_CHECK_LAUNCH();
+  return 0;
+}
 
 extern "C" int saspa_pool2d(int dtype, int mode, const void* x, int ldx, void* y, int ldy, int batch, int hin, int win, int C, int k,
                             int stride, int pad, void* stream) {

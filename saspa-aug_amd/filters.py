@@ -8,7 +8,16 @@ sequences of the gfx950 kernels.
   * `LpipsAlex` -- LPIPS v0.1 on AlexNet (`lpips.LPIPS(net='alex')`, all_utils/utils.py:269-270): an augmented image passes when
     `lpips_min <= d(original, augmented) <= lpips_max` (:377-381), both images grey, 256 x 256 (`calc_lpips_distance` :576-590).
   * `ConfidenceFilter` -- the baseline classifier WSDAN_CAL (fgvc/models/cal.py:131-228; loader
-    all_utils/dataset_utils.py:87-115): passes when the SOURCE image's label is among the top-k (10) logits (:357-366).
+    all_utils/dataset_utils.py:87-115): passes when the SOURCE image's label is among the top-k (10) logits (:357-366); with
+    `too_high` (the reference's `filter_confidence_higher_than`, :368-373) an image that passes top-k is dropped when the softmax
+    probability of that label exceeds the bound.
+  * `ClassFilter` -- the per-class CLIP filter of the Real-Guidance baseline (`clip_filtering="per_class"`, :272-304, :180-191,
+    :383-393): the same CLIP RN50 against one prompt per CLASS of the dataset; passes when the softmax over all class prompts gives
+    the source image's class at least `1 / n_classes / discount`.  A softmax probability needs the image norm and `logit_scale`
+    (an argmax does not), so the row of logits, its softmax and the entries the decisions read are one kernel, `ops.class_head`.
+
+Mirrored text, declared: `NEGATIVE_PROMPTS` and the five `CLASS_PROMPT_TEMPLATES` strings are the reference's wording (:307, :278-295)
+because they ARE the contract -- the strings CLIP sees.
 
 MI355X-first choices: BatchNorm (inference) is folded into the conv weights + a bias at pack time, ReLU rides in the GEMM
 epilogue (`SASPA_ACT_RELU`, `SASPA_ACT_ADD_RELU` for the bottleneck's add-then-ReLU), pooling is one streaming kernel,
@@ -32,6 +41,15 @@ IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
 NEGATIVE_PROMPTS = ["a photo of an object", "a photo of a scene", "a photo of geometric shapes", "a photo", "an image",
                     "a black photo"]                                     # all_utils/utils.py:307
+# the class prompts of the per-class CLIP filter, per dataset (all_utils/utils.py:277-295); `{name}` = a class / part string
+CLASS_PROMPT_TEMPLATES = {
+    "planes": "a photo of a {name}, a type of aircraft.",
+    "synthetic": "a photo of a {name}, a type of aircraft.",
+    "cars": "a photo of a {name}, a type of car.",
+    "dtd": "a photo of a {name}, a type of texture.",
+    "cub": "a photo of a {name}, a type of a bird.",
+    "compcars-parts": "a photo of the {name}, of a car.",
+}
 RELU, ADD_RELU = ops.ACT_RELU, ops.ACT_ADD_RELU
 
 
@@ -166,36 +184,123 @@ class ClipRN50Visual:
         return ops.linear(o.view(b, ch), p["c.w"], p["c.b"])
 
 
-class SemanticFilter:
-    """CLIP_selector (all_utils/utils.py:137-166) with the prompts [positive] + NEGATIVE_PROMPTS; `passes(images)` is
-    `get_semantic_filtering` for a batch: argmax over the prompts == 0."""
-
-    def __init__(self, sd, cfg, dev, positive_prompt, tokenizer, dtype=torch.float32):
-        self.cfg, self.dev, self.dtype = cfg, dev, dtype
-        self.visual = ClipRN50Visual(sd, cfg, dev, dtype)
-        tcfg = dict(vocab=cfg["vocab"], width=cfg["text_width"], layers=cfg["text_layers"], heads=cfg["text_heads"],
-                    mlp=4 * cfg["text_width"], max_pos=cfg["context"])
-        text = models.CLIPText(W.openai_clip_text_to_hf(sd, cfg["text_layers"]), tcfg, dev, dtype)
-        self.prompts = [positive_prompt] + NEGATIVE_PROMPTS
-        ids = np.concatenate([tokenizer(pr) for pr in self.prompts])          # [7, 77]
+def clip_text_unit_rows(sd, cfg, dev, prompts, tokenizer, dtype=torch.float32, chunk=64):
+    """The CLIP text tower over `prompts`, `chunk` prompts per pass -> unit text embeddings fp32 [len(prompts), embed_dim]: a
+    constant of the run (TextEncoder + `text_features / text_features.norm()`, all_utils/utils.py:113-134, :161)."""
+    tcfg = dict(vocab=cfg["vocab"], width=cfg["text_width"], layers=cfg["text_layers"], heads=cfg["text_heads"],
+                mlp=4 * cfg["text_width"], max_pos=cfg["context"])
+    text = models.CLIPText(W.openai_clip_text_to_hf(sd, cfg["text_layers"]), tcfg, dev, dtype)
+    out = []
+    for i in range(0, len(prompts), chunk):
+        ids = np.concatenate([tokenizer(pr) for pr in prompts[i:i + chunk]])   # [k, 77]
         ids_t = ops.h2d(torch.from_numpy(ids), dev)
-        hidden = text.forward(ids_t)                                          # final-LN states [7, 77, width]
+        hidden = text.forward(ids_t)                                          # final-LN states [k, 77, width]
         eot = ids_t.argmax(dim=-1)                                            # clip: the EOT token has the highest id
-        rows = hidden[torch.arange(len(self.prompts), device=dev), eot].contiguous()
+        rows = hidden[torch.arange(ids.shape[0], device=dev), eot].contiguous()
         feats = ops.linear(rows.float(), text.p["text_projection.w"].float())[:, :cfg["embed_dim"]]
-        # constant for the run: unit text embeddings (the image norm and logit_scale are common factors of the argmax)
-        self.text_unit = torch.nn.functional.normalize(feats.double(), dim=-1).float().contiguous()
-        del text
+        out.append(torch.nn.functional.normalize(feats.double(), dim=-1).float())
+    return (torch.cat(out) if len(out) > 1 else out[0]).contiguous()
+
+
+class _ClipImageSide:
+    """What the two CLIP filters share: the image tower (one `ClipRN50Visual` may serve both) and the embedding of a batch."""
 
     @torch.no_grad()
-    def logits(self, images_u8):
-        """device u8 [n,H,W,3] -> fp32 [n, 7] cosine-similarity logits up to the common positive factor."""
+    def embed(self, images_u8):
+        """device u8 [n,H,W,3] -> fp32 [n, embed_dim] UNNORMALISED image embeddings."""
         px = rn50_preprocess(images_u8, self.dtype, self.cfg["image_size"])
-        e = self.visual.forward(px)[:, :self.cfg["embed_dim"]].float().contiguous()
+        return self.visual.forward(px)[:, :self.cfg["embed_dim"]].float().contiguous()
+
+
+class SemanticFilter(_ClipImageSide):
+    """CLIP_selector (all_utils/utils.py:137-166) with the prompts [positive] + NEGATIVE_PROMPTS; `passes(images)` is
+    `get_semantic_filtering` for a batch: argmax over the prompts == 0.  `visual`: an image tower built elsewhere (the per-class
+    filter's) to share."""
+
+    def __init__(self, sd, cfg, dev, positive_prompt, tokenizer, dtype=torch.float32, visual=None):
+        self.cfg, self.dev, self.dtype = cfg, dev, dtype
+        self.visual = visual if visual is not None else ClipRN50Visual(sd, cfg, dev, dtype)
+        self.prompts = [positive_prompt] + NEGATIVE_PROMPTS
+        # constant for the run: unit text embeddings (the image norm and logit_scale are common factors of the argmax)
+        self.text_unit = clip_text_unit_rows(sd, cfg, dev, self.prompts, tokenizer, dtype)
+
+    @torch.no_grad()
+    def logits(self, images_u8, embedding=None):
+        """device u8 [n,H,W,3] -> fp32 [n, 7] cosine-similarity logits up to the common positive factor.  `embedding`: the batch's
+        `embed()` when the caller already has it."""
+        e = self.embed(images_u8) if embedding is None else embedding
         return ops.linear(e, self.text_unit)[:, :len(self.prompts)]
 
-    def passes(self, images_u8):
-        return np.argmax(self.logits(images_u8).cpu().numpy(), axis=-1) == 0       # the decision is host control flow
+    def passes(self, images_u8, embedding=None):
+        return np.argmax(self.logits(images_u8, embedding).cpu().numpy(), axis=-1) == 0       # the decision is host control flow
+
+
+def class_prompts(ds_utils):
+    """(class list, prompts) of the per-class CLIP filter for a dataset (all_utils/utils.py:274-299).  The class list is
+    `sorted(set(get_classes()))` -- the reference indexes an unordered set; the decision does not depend on the order -- and
+    compcars-parts asks about the photographed PART (`sorted(part_to_string.values())`)."""
+    name = getattr(ds_utils, "name", None)
+    if name not in CLASS_PROMPT_TEMPLATES:
+        raise NotImplementedError(f"per-class CLIP filter: no class prompts for dataset {name!r}")
+    if name == "compcars-parts":
+        classes = sorted(set(ds_utils.part_to_string.values()))
+    else:
+        classes = sorted(set(ds_utils.get_classes()))
+    return classes, [CLASS_PROMPT_TEMPLATES[name].format(name=c) for c in classes]
+
+
+def class_labels(ds_utils, original_images_paths, classes):
+    """{original file name: index of its class in `classes`} (all_utils/utils.py:384-389): planes / synthetic / cars look the class
+    string up by `stem.split("_")[0]` in the stem-keyed dict, the others by image path (compcars-parts: the part folder)."""
+    index = {c: i for i, c in enumerate(classes)}
+    name = ds_utils.name
+    if name in ("planes", "synthetic", "cars"):
+        table = ds_utils.get_image_stem_to_class_str_dict()
+        return {Path(ip).name: index[table[Path(ip).stem.split("_")[0]]] for ip in original_images_paths}
+    if name == "compcars-parts":
+        return {Path(ip).name: index[ds_utils.part_to_string[Path(ip).parent.name]] for ip in original_images_paths}
+    table = ds_utils.get_image_path_to_class_str_dict()
+    return {Path(ip).name: index[table[ip]] for ip in original_images_paths}
+
+
+def class_threshold(n_classes, discount=1):
+    """`threhold = 1 / len(classnames) / clip_filtering_discount` (all_utils/utils.py:303): chance level, divided by the discount."""
+    return 1 / n_classes / discount
+
+
+class ClassFilter(_ClipImageSide):
+    """CLIP_selector with one prompt per class (`template.format(name=class)`) and `get_clip_filtering` for a batch
+    (all_utils/utils.py:180-191): softmax(logit_scale.exp() * unit(image) @ unit(text)^T)[label] >= 1 / n_classes / discount.
+    The unit text matrix [C, embed_dim] and the scale are constants of the run; per batch the image tower runs once and one
+    `ops.class_head` launch turns the embeddings into the probabilities."""
+
+    def __init__(self, sd, cfg, dev, class_names, template, tokenizer, discount=1, dtype=torch.float32, visual=None):
+        if not class_names:
+            raise ValueError("the per-class CLIP filter needs at least one class")
+        self.cfg, self.dev, self.dtype = cfg, dev, dtype
+        self.visual = visual if visual is not None else ClipRN50Visual(sd, cfg, dev, dtype)
+        self.class_names = list(class_names)
+        self.prompts = [template.format(name=c) for c in self.class_names]
+        self.text_unit = clip_text_unit_rows(sd, cfg, dev, self.prompts, tokenizer, dtype)
+        self.scale = float(sd["logit_scale"].float().exp())                   # logit_scale.exp(), a constant of the checkpoint
+        self.discount = discount
+        self.threshold = class_threshold(len(self.class_names), discount)
+
+    @torch.no_grad()
+    def probs(self, images_u8, labels, embedding=None):
+        """device u8 [n,H,W,3], labels (host ints, one per image, each in [0, C)) -> fp32 [n] on the device: the softmax probability
+        of every image's own class.  Labels are validated HERE (the kernel only marks a bad row with NaN)."""
+        lb = np.asarray(labels).astype(np.int64).reshape(-1)
+        n = images_u8.shape[0] if embedding is None else embedding.shape[0]
+        if lb.size != n or (lb.size and (lb.min() < 0 or lb.max() >= len(self.class_names))):
+            raise ValueError(f"labels must hold {n} values in [0, {len(self.class_names)})")
+        e = self.embed(images_u8) if embedding is None else embedding
+        stats, _, _ = ops.class_head(e, ops.h2d(torch.from_numpy(lb.astype(np.int32)), e.device), self.text_unit, self.scale, True,
+                                     width=self.cfg["embed_dim"])
+        return stats[:, 1]
+
+    def passes(self, images_u8, labels, embedding=None):
+        return self.probs(images_u8, labels, embedding).cpu().numpy().astype(np.float64) >= self.threshold   # host control flow
 
 
 class WSDANCAL:
@@ -254,10 +359,11 @@ class WSDANCAL:
 
 
 class ConfidenceFilter:
-    def __init__(self, sd, cfg, dev, top_k=10, dtype=torch.float32):
+    def __init__(self, sd, cfg, dev, top_k=10, dtype=torch.float32, too_high=None):
         self.cfg, self.dev, self.dtype = cfg, dev, dtype
         self.model = WSDANCAL(sd, cfg, dev, dtype)
         self.top_k = min(int(top_k), self.model.num_classes)                  # all_utils/utils.py:319
+        self.too_high = too_high or None                                      # `if filter_confidence_higher_than:` (:368)
 
     @torch.no_grad()
     def logits(self, images_u8):
@@ -265,8 +371,24 @@ class ConfidenceFilter:
 
     def passes(self, images_u8, labels):
         """`correct_label in logits.topk(k)[1]` per image (all_utils/utils.py:363-364); labels: ints, one per image."""
-        lg = self.logits(images_u8).float().cpu().numpy()                      # the decision is host control flow
-        return np.array([int((row > row[int(lb)]).sum()) < self.top_k for lb, row in zip(labels, lg)], dtype=bool)
+        if self.too_high is None:
+            lg = self.logits(images_u8).float().cpu().numpy()                  # the decision is host control flow
+            return np.array([int((row > row[int(lb)]).sum()) < self.top_k for lb, row in zip(labels, lg)], dtype=bool)
+        return self.passes_and_too_high(images_u8, labels)
+
+    @torch.no_grad()
+    def passes_and_too_high(self, images_u8, labels):
+        """(top-k mask, too-high mask) from ONE logits-mode `ops.class_head` launch on the classifier's logits: the label is in the
+        top k when fewer than k logits are strictly greater, and it is too confident when softmax(logits)[label] > too_high
+        (all_utils/utils.py:363-373).  The second mask is False wherever the first is: the reference tests it in the `elif`."""
+        lb = np.asarray(labels).astype(np.int64).reshape(-1)
+        if lb.size != images_u8.shape[0] or (lb.size and (lb.min() < 0 or lb.max() >= self.model.num_classes)):
+            raise ValueError(f"labels must hold {images_u8.shape[0]} values in [0, {self.model.num_classes})")
+        lg = self.logits(images_u8).float()
+        stats, idx, _ = ops.class_head(lg, ops.h2d(torch.from_numpy(lb.astype(np.int32)), lg.device), width=self.model.num_classes)
+        in_top_k = idx[:, 1].cpu().numpy() < self.top_k                         # the decisions are host control flow
+        high = stats[:, 1].cpu().numpy().astype(np.float64) > (self.too_high if self.too_high is not None else np.inf)
+        return in_top_k, high & in_top_k
 
 
 class LpipsAlex:
@@ -368,21 +490,23 @@ def synthetic_filters_allowed():
     return os.environ.get("SASPA_SYNTHETIC_FILTERS", "0") not in ("", "0")
 
 
-def filter_checkpoints(ds_utils, weights_dir, semantic=True, confidence=True):
-    """Paths of the checkpoints the enabled filters need: (clip RN50 path | None, baseline checkpoint path | None).
+def filter_checkpoints(ds_utils, weights_dir, semantic=True, confidence=True, per_class=False):
+    """Paths of the checkpoints the enabled filters need: (clip RN50 path | None, baseline checkpoint path | None); the per-class
+    CLIP filter (`per_class`) reads the same `clip/RN50.pt` as the semantic filter.
     Raises FileNotFoundError for a missing / ambiguous checkpoint unless synthetic filter weights were asked for
     explicitly -- a filtered aug.json must never reflect the decisions of random models (the reference asserts exactly
     one baseline checkpoint, all_utils/dataset_utils.py:92, and loads the real CLIP, all_utils/utils.py:253)."""
     name = "compcars" if "compcars" in ds_utils.name else ds_utils.name
     rn = cp = None
-    if semantic:
+    if semantic or per_class:
         cand = os.path.join(weights_dir, "clip", "RN50.pt") if weights_dir else None
         if cand and os.path.exists(cand):
             rn = cand
         elif not synthetic_filters_allowed():
+            which, knob = ("semantic filter", "SEMANTIC_FILTERING = 0") if semantic else ("per-class CLIP filter", "CLIP_FILTERING_TYPE = None")
             raise FileNotFoundError(
-                f"semantic filter: {cand or '<WEIGHTS_DIR>/clip/RN50.pt'} not found.  Give WEIGHTS_DIR with the OpenAI CLIP RN50 "
-                "checkpoint, set SEMANTIC_FILTERING = 0, or opt in to synthetic filter weights with SASPA_SYNTHETIC_FILTERS=1")
+                f"{which}: {cand or '<WEIGHTS_DIR>/clip/RN50.pt'} not found.  Give WEIGHTS_DIR with the OpenAI CLIP RN50 "
+                f"checkpoint, set {knob}, or opt in to synthetic filter weights with SASPA_SYNTHETIC_FILTERS=1")
     if confidence:
         cdir = Path(weights_dir, "checkpoints", name) if weights_dir else None
         cps = sorted(cdir.glob("*.pth")) if cdir else []
@@ -452,21 +576,30 @@ def build_lpips(dev, weights_dir=None):
     return LpipsAlex(sd, LPIPS_ALEX, dev)
 
 
-def build_filters(ds_utils, dev, semantic=True, confidence=True, weights_dir=None, top_k=10, tokenizer=None):
-    """The filter models for a dataset.  `weights_dir` holds `clip/RN50.pt` and `checkpoints/<dataset>/*.pth` (the
-    reference's `all_utils/checkpoints/<name>/`).  A missing checkpoint is an error (filter_checkpoints); only with
-    SASPA_SYNTHETIC_FILTERS=1 does the stage run on architecture-exact SYNTHETIC weights, and says so loudly."""
+def build_filters(ds_utils, dev, semantic=True, confidence=True, weights_dir=None, top_k=10, tokenizer=None, per_class=False,
+                  discount=1, too_high=None):
+    """The filter models for a dataset: (semantic, confidence), and with `per_class` (semantic, confidence, per-class CLIP filter).
+    `weights_dir` holds `clip/RN50.pt` and `checkpoints/<dataset>/*.pth` (the reference's `all_utils/checkpoints/<name>/`).  A
+    missing checkpoint is an error (filter_checkpoints); only with SASPA_SYNTHETIC_FILTERS=1 does the stage run on
+    architecture-exact SYNTHETIC weights, and says so loudly.  The two CLIP filters share one image tower (the reference loads one
+    `clip.load('RN50')` for both, all_utils/utils.py:252-255)."""
     from .tokenizer import make_tokenizer
-    sem = conf = None
-    rn, cp = filter_checkpoints(ds_utils, weights_dir, semantic, confidence)
-    if semantic:
+    sem = conf = cls = None
+    rn, cp = filter_checkpoints(ds_utils, weights_dir, semantic, confidence, per_class)
+    if semantic or per_class:
         if rn:
             sd = load_clip_rn50(rn)
         else:
-            logging.warning("semantic filter: SASPA_SYNTHETIC_FILTERS=1 -> SYNTHETIC CLIP-RN50 weights; its decisions are those of a random model")
+            logging.warning(f"{'semantic' if semantic else 'per-class CLIP'} filter: SASPA_SYNTHETIC_FILTERS=1 -> SYNTHETIC CLIP-RN50 weights; its decisions are those of a random model")
             sd = W.synth_state_dict("clip_rn50", CLIP_RN50, 11)
         tok = tokenizer or make_tokenizer(os.path.join(weights_dir, "clip") if weights_dir else None, CLIP_RN50["vocab"], pad_id=0)
-        sem = SemanticFilter(sd, CLIP_RN50, dev, ds_utils.get_basic_prompt(), tok)
+        visual = None
+        if per_class:
+            classes, _ = class_prompts(ds_utils)
+            cls = ClassFilter(sd, CLIP_RN50, dev, classes, CLASS_PROMPT_TEMPLATES[ds_utils.name], tok, discount)
+            visual = cls.visual
+        if semantic:
+            sem = SemanticFilter(sd, CLIP_RN50, dev, ds_utils.get_basic_prompt(), tok, visual=visual)
     if confidence:
         if cp:
             sd, cfg = load_cal_checkpoint(cp)
@@ -474,8 +607,8 @@ def build_filters(ds_utils, dev, semantic=True, confidence=True, weights_dir=Non
             logging.warning("confidence filter: SASPA_SYNTHETIC_FILTERS=1 -> SYNTHETIC WSDAN_CAL (resnet101) weights; its decisions are those of a random model")
             cfg = dict(WSDAN_CAL_R101, num_classes=max(2, ds_utils.num_classes))
             sd = W.synth_state_dict("cal", cfg, 12)
-        conf = ConfidenceFilter(sd, cfg, dev, top_k)
-    return sem, conf
+        conf = ConfidenceFilter(sd, cfg, dev, top_k, too_high=too_high)
+    return (sem, conf, cls) if per_class else (sem, conf)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -553,7 +686,7 @@ def lpips_pair_distances(model, pairs, dev=None, resize=(256, 256), grey=True, b
 
 
 def apply_filters(mapping, original_images_paths, ds_utils, dev, semantic=None, confidence=None, batch_size=32, lpips=None,
-                  lpips_min=None, lpips_max=None, resize=(256, 256)):
+                  lpips_min=None, lpips_max=None, resize=(256, 256), class_filter=None):
     """mapping: {original file name: [augmented paths]} as `match_augmented_images` builds it (every original present).
     Returns (filtered mapping, counters).  Per original image the reference first drops the augmentations whose
     classifier top-k misses the source label, then those CLIP does not recognise as the meta class; both decisions are
@@ -562,10 +695,14 @@ def apply_filters(mapping, original_images_paths, ds_utils, dev, semantic=None, 
     prefetch thread, so at most two batches are resident on the host (a real dataset has 13-16k augmentations of ~1 MB).
     `lpips` (an LpipsAlex) with both bounds adds the reference's second filter, between the two (:377-381): the augmented batch
     already on the device is reused, every original is decoded once per run of consecutive augmentations of a batch, and a dropped
-    image is counted once, under the first filter that drops it (top-k, then LPIPS, then semantic)."""
+    image is counted once, under the first filter that drops it (top-k, then LPIPS, then semantic).
+    `class_filter` (a ClassFilter) adds the per-class CLIP filter of the Real-Guidance baseline between LPIPS and semantic
+    (:383-399; counter `clip_filtering`); when it and the semantic filter share their image tower, the tower runs once per batch.
+    A ConfidenceFilter with `too_high` also drops, among the images that pass top-k, those it is too sure of (:368-375; counter
+    `too_high_confidence`).  Order of attribution: top-k / too-high, LPIPS, per-class CLIP, semantic."""
     from concurrent.futures import ThreadPoolExecutor
     if dev is None:
-        for m in (semantic, confidence, lpips):
+        for m in (semantic, confidence, lpips, class_filter):
             if m is not None:
                 dev = m.dev
                 break
@@ -577,6 +714,13 @@ def apply_filters(mapping, original_images_paths, ds_utils, dev, semantic=None, 
     work = [(name, ap) for name, aps in mapping.items() for ap in aps]
     keep = {}
     counters = dict(not_in_top_k=0, semantic=0)
+    use_high = confidence is not None and getattr(confidence, "too_high", None) is not None
+    if use_high:
+        counters["too_high_confidence"] = 0
+    if class_filter is not None:
+        counters["clip_filtering"] = 0
+        cls_labels = class_labels(ds_utils, original_images_paths, class_filter.class_names)
+    shared_tower = class_filter is not None and semantic is not None and getattr(semantic, "visual", None) is class_filter.visual
     use_lpips = lpips is not None and lpips_bounds(lpips_min, lpips_max)
     if use_lpips:
         counters["lpips"] = 0
@@ -603,20 +747,33 @@ def apply_filters(mapping, original_images_paths, ds_utils, dev, semantic=None, 
             pixels, refs, idx = nxt.result()
             nxt = pool.submit(decode, chunks[ci + 1]) if ci + 1 < len(chunks) else None
             batch = ops.h2d(torch.from_numpy(pixels), dev)
-            ok_c = confidence.passes(batch, [labels[name] for name, _ in chunk]) if confidence is not None else np.ones(len(chunk), bool)
-            ok_s = semantic.passes(batch) if semantic is not None else np.ones(len(chunk), bool)
+            ok_c, high = np.ones(len(chunk), bool), np.zeros(len(chunk), bool)
+            if use_high:
+                ok_c, high = confidence.passes(batch, [labels[name] for name, _ in chunk])
+            elif confidence is not None:
+                ok_c = confidence.passes(batch, [labels[name] for name, _ in chunk])
+            emb = class_filter.embed(batch) if shared_tower else None            # one image-tower pass for both CLIP filters
+            ok_p = class_filter.passes(batch, [cls_labels[name] for name, _ in chunk], embedding=emb) if class_filter is not None else np.ones(len(chunk), bool)
+            if semantic is None:
+                ok_s = np.ones(len(chunk), bool)
+            else:
+                ok_s = semantic.passes(batch, embedding=emb) if shared_tower else semantic.passes(batch)
             ok_l = np.ones(len(chunk), bool)
             if use_lpips:
                 ref_px = _refs_on_device(lpips, refs, dev, resize, True, pixels.shape[1:3])
                 d = lpips.distance(lpips.preprocess(batch, resize, True), ref_px, idx).cpu().numpy().astype(np.float64)   # host control flow
                 ok_l = (lpips_min <= d) & (d <= lpips_max)
-            for (name, ap), c_ok, l_ok, s_ok in zip(chunk, ok_c, ok_l, ok_s):
+            for (name, ap), c_ok, h_bad, l_ok, p_ok, s_ok in zip(chunk, ok_c, high, ok_l, ok_p, ok_s):
                 if not c_ok:
                     counters["not_in_top_k"] += 1          # dropped first: never reaches the other filters (:357-366)
+                elif h_bad:
+                    counters["too_high_confidence"] += 1   # the `elif` of the same loop (:368-375)
                 elif not l_ok:
                     counters["lpips"] += 1                 # second (:377-381)
+                elif not p_ok:
+                    counters["clip_filtering"] += 1        # third (:383-399)
                 elif not s_ok:
                     counters["semantic"] += 1
-                keep[ap] = bool(c_ok and l_ok and s_ok)
+                keep[ap] = bool(c_ok and not h_bad and l_ok and p_ok and s_ok)
     out = {name: [ap for ap in aps if keep[ap]] for name, aps in mapping.items()}
     return out, counters

@@ -1114,6 +1114,42 @@ def lpips_layer(a, r, ref_index, w, dist=None, accumulate=False, workspace=None)
     return dist
 
 
+def class_head(feat, labels, cls=None, scale=1.0, normalize=True, width=None, want_logits=False):
+    """The class head of a filter decision (saspa_class_head), one launch per batch.  Embedding mode (`cls` fp32 [C, D'] unit text rows):
+    feat fp32 [n, D'] unnormalised embeddings, z = scale * unit(feat) @ cls^T over the first `width` (default: all) columns.  Logits mode
+    (`cls` None): feat fp32 [n, C'] holds the logits, z = scale * feat[:, :width].  labels: device int32 [n], values in [0, C) -- the
+    CALLER checks them; the kernel answers a label outside the range with NaN statistics and -1 indices.
+    -> (stats fp32 [n, 4] = z_label, softmax(z)[label], max z, logsumexp z;  idx int32 [n, 2] = argmax (lowest index of equal logits),
+    number of logits strictly greater than z_label;  logits fp32 [n, C] or None)."""
+    _check_dev(feat, labels, cls)
+    if feat.dtype != torch.float32 or feat.dim() != 2 or feat.stride(1) != 1:
+        raise ValueError("class_head expects an fp32 [rows, width] matrix with a contiguous last dim")
+    n = feat.shape[0]
+    d = int(feat.shape[1] if width is None else width)
+    if n < 1 or d < 1 or d > feat.shape[1]:
+        raise ValueError(f"class_head: {n} rows of width {d} out of a [{n}, {feat.shape[1]}] matrix")
+    if labels.dtype != torch.int32 or labels.dim() != 1 or labels.numel() != n or not labels.is_contiguous():
+        raise ValueError("labels must be a contiguous int32 [rows] device tensor")
+    ldc = 0
+    if cls is not None:
+        if cls.dtype != torch.float32 or cls.dim() != 2 or cls.stride(1) != 1 or cls.shape[1] < d:
+            raise ValueError(f"cls must be an fp32 [C, >= {d}] matrix with a contiguous last dim")
+        c = cls.shape[0]
+        ldc = cls.stride(0) if c > 1 else (d + 3) // 4 * 4
+    else:
+        c = d
+    if d > _lib.CLASS_HEAD_MAX_D or c > _lib.CLASS_HEAD_MAX_C:
+        raise ValueError(f"class_head holds a row of at most {_lib.CLASS_HEAD_MAX_D} features and {_lib.CLASS_HEAD_MAX_C} classes in LDS, got {d} / {c}")
+    stats = torch.empty((n, 4), device=feat.device, dtype=torch.float32)
+    idx = torch.empty((n, 2), device=feat.device, dtype=torch.int32)
+    ldl = (c + 3) // 4 * 4
+    logits = torch.empty((n, ldl), device=feat.device, dtype=torch.float32) if want_logits else None
+    ldf = feat.stride(0) if n > 1 else (d + 3) // 4 * 4                      # one row: its pitch is never used
+    _lib.check(_L().saspa_class_head(_ptr(feat), ldf, _ptr(cls), ldc, _ptr(labels), float(scale),
+                                     int(bool(normalize)), _ptr(stats), _ptr(idx), _ptr(logits), ldl, n, d, c, _stream()), "saspa_class_head")
+    return stats, idx, (logits[:, :c] if want_logits else None)
+
+
 def u8_luma(img_u8):
     """PIL convert("L").convert("RGB") of a device u8 [..., 3] tensor (saspa_u8_luma; integer exact)."""
     _check_dev(img_u8)

@@ -152,6 +152,9 @@ class Settings:
     MODEL_CONFIDENCE_BASED_FILTERING: int = 1
     LPIPS_MIN: float = None            # both or neither (:551-552): keep lpips_min <= LPIPS_alex(original, augmented) <= lpips_max
     LPIPS_MAX: float = None
+    CLIP_FILTERING_TYPE: str = None    # "per_class" (the only type): the per-class CLIP filter of the Real-Guidance baseline
+    CLIP_FILTERING_DISCOUNT: float = 1  # its threshold is 1 / n_classes / discount
+    FOLDER_STEPS_GS_SUFFIX: bool = False   # run_aug_real_guidance.py names its folder "..._seed_{S}_num_inf_steps_{N}_gs_{G}"
     STYLE_IMG_FROM_DIFF_IMG: bool = True   # blip_diffusion: subject image = another image of the same class (:548)
     # additions of this build
     BATCH_SIZE: int = 8
@@ -201,7 +204,10 @@ def output_folder_for(s: Settings, root_path):
         base_model_folder += f"-SDEdit_strength_{s.SDEDIT_STRENGTH}"
     if s.CONTROLNET:
         base_model_folder = base_model_folder.replace("regular/", "controlnet/")
-    return f"{root_path}/aug_data/{base_model_folder}/{s.CONTROLNET}/{prompt_str_for(s)}_seed_{s.SEED}/images"
+    run = f"{prompt_str_for(s)}_seed_{s.SEED}"
+    if s.FOLDER_STEPS_GS_SUFFIX:
+        run += f"_num_inf_steps_{s.NUM_INFERENCE_STEPS}_gs_{s.GUIDANCE_SCALE}"
+    return f"{root_path}/aug_data/{base_model_folder}/{s.CONTROLNET}/{run}/images"
 
 
 def read_prompts(prompts_file):
@@ -737,22 +743,25 @@ def host_threads(local_world=1):
     return max(1, min(4, n // max(1, int(local_world))))
 
 
-def main(s: Settings, ds_utils=None, batch_generator=None, dist=None, pipe=None, filter_models=None, lpips_model=None):
+def main(s: Settings, ds_utils=None, batch_generator=None, dist=None, pipe=None, filter_models=None, lpips_model=None,
+         class_filter=None):
     """`_main` with torch's CPU pool held at `host_threads()` for the duration of the run (restored afterwards)."""
     world = dist.get_world_size() if dist is not None else 1
     before = torch.get_num_threads()
     torch.set_num_threads(host_threads(int(os.environ.get("LOCAL_WORLD_SIZE", world))))
     try:
         return _main(s, ds_utils=ds_utils, batch_generator=batch_generator, dist=dist, pipe=pipe, filter_models=filter_models,
-                     lpips_model=lpips_model)
+                     lpips_model=lpips_model, class_filter=class_filter)
     finally:
         torch.set_num_threads(before)
 
 
-def _main(s: Settings, ds_utils=None, batch_generator=None, dist=None, pipe=None, filter_models=None, lpips_model=None):
+def _main(s: Settings, ds_utils=None, batch_generator=None, dist=None, pipe=None, filter_models=None, lpips_model=None,
+          class_filter=None):
     """The generation loop.  `batch_generator` is injectable for host-logic tests; the default
     builds the HIP pipeline (fails loudly without an MI355X).  `filter_models` = (SemanticFilter | None,
-    ConfidenceFilter | None) to reuse built filter models; None builds them on s.DEVICE when a filter flag is set."""
+    ConfidenceFilter | None) to reuse built filter models; None builds them on s.DEVICE when a filter flag is set.
+    `class_filter`: a built ClassFilter for CLIP_FILTERING_TYPE = "per_class", likewise."""
     rank = dist.get_rank() if dist is not None else 0
     world = dist.get_world_size() if dist is not None else 1
     png = _PngWriters(4)
@@ -788,7 +797,13 @@ def _main(s: Settings, ds_utils=None, batch_generator=None, dist=None, pipe=None
     else:                                           # gpt-meta_class, ALIA: one prompt per line
         prompts = read_prompts(prompts_file)
         logging.info(f"Read {len(prompts)} prompts from {prompts_file}")
+    if s.CLIP_FILTERING_TYPE and s.CLIP_FILTERING_TYPE != "per_class":
+        raise NotImplementedError(f'CLIP_FILTERING_TYPE = {s.CLIP_FILTERING_TYPE!r}: "per_class" is the only type')
+    assert not (s.CLIP_FILTERING_TYPE and s.MODEL_CONFIDENCE_BASED_FILTERING), \
+        "can't use both CLIP_FILTERING_TYPE and MODEL_CONFIDENCE_BASED_FILTERING"
     aug_json_path = utils.get_aug_json_path(output_folder, lpips_min=s.LPIPS_MIN, lpips_max=s.LPIPS_MAX,
+                                            clip_filtering=s.CLIP_FILTERING_TYPE or False,
+                                            clip_filtering_discount=s.CLIP_FILTERING_DISCOUNT,
                                             semantic_filtering=s.SEMANTIC_FILTERING,
                                             model_confidence_based_filtering=s.MODEL_CONFIDENCE_BASED_FILTERING)
     logging.info(f"Augmented json path will be at: \n{aug_json_path}")
@@ -797,11 +812,16 @@ def _main(s: Settings, ds_utils=None, batch_generator=None, dist=None, pipe=None
         from . import filters as _filters
         _filters.lpips_bounds(s.LPIPS_MIN, s.LPIPS_MAX)
         _filters.lpips_checkpoints(s.WEIGHTS_DIR)
-    if filter_models is None and (s.SEMANTIC_FILTERING or s.MODEL_CONFIDENCE_BASED_FILTERING):
+    need_two = filter_models is None and bool(s.SEMANTIC_FILTERING or s.MODEL_CONFIDENCE_BASED_FILTERING)
+    need_class = class_filter is None and bool(s.CLIP_FILTERING_TYPE)
+    if need_two or need_class:
         # fail BEFORE hours of generation, not after: a filter flag with no checkpoint behind it is an error unless
         # synthetic filter weights were asked for explicitly (SASPA_SYNTHETIC_FILTERS=1)
         from . import filters as _filters
-        _filters.filter_checkpoints(ds_utils, s.WEIGHTS_DIR, bool(s.SEMANTIC_FILTERING), bool(s.MODEL_CONFIDENCE_BASED_FILTERING))
+        if need_class:
+            _filters.class_prompts(ds_utils)          # a dataset without class prompts is refused here too
+        _filters.filter_checkpoints(ds_utils, s.WEIGHTS_DIR, bool(s.SEMANTIC_FILTERING) and need_two,
+                                    bool(s.MODEL_CONFIDENCE_BASED_FILTERING) and need_two, per_class=need_class)
 
     blip = "blip_diffusion" in s.BASE_MODEL
     items = plan_work(s, ds_utils.original_images_paths, prompts, output_folder, image_classes_dict,
@@ -936,9 +956,11 @@ def _main(s: Settings, ds_utils=None, batch_generator=None, dist=None, pipe=None
                      f"{sum(i.skip for i in items)} skipped (already existed)")
         n_files = len(list(Path(output_folder).glob("*.*")))
         # the filter stage runs on this rank's GPU whether the models are built here or handed in
-        fdev = torch.device(s.DEVICE) if (s.SEMANTIC_FILTERING or s.MODEL_CONFIDENCE_BASED_FILTERING or s.LPIPS_MIN or s.LPIPS_MAX) else None
+        fdev = torch.device(s.DEVICE) if (s.SEMANTIC_FILTERING or s.MODEL_CONFIDENCE_BASED_FILTERING or s.LPIPS_MIN or s.LPIPS_MAX
+                                          or s.CLIP_FILTERING_TYPE) else None
         json_path = utils.create_json_of_image_name_to_augmented_images_paths(
-            ds_utils, output_folder, lpips_min=s.LPIPS_MIN, lpips_max=s.LPIPS_MAX, semantic_filtering=s.SEMANTIC_FILTERING,
+            ds_utils, output_folder, lpips_min=s.LPIPS_MIN, lpips_max=s.LPIPS_MAX, clip_filtering=s.CLIP_FILTERING_TYPE or False,
+            clip_filtering_discount=s.CLIP_FILTERING_DISCOUNT, class_filter=class_filter, semantic_filtering=s.SEMANTIC_FILTERING,
             model_confidence_based_filtering=s.MODEL_CONFIDENCE_BASED_FILTERING, init_log=False,
             original_images_paths=ds_utils.original_images_paths, min_files=min(10, max(1, n_files)),
             filter_models=filter_models, weights_dir=s.WEIGHTS_DIR, device=fdev, lpips_model=lpips_model)

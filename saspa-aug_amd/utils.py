@@ -7,8 +7,9 @@ interface for this path (same names, argument meaning and outputs):
   get_aug_json_path             all_utils/utils.py:194-218
   create_json_of_image_name_to_augmented_images_paths   all_utils/utils.py:221-465 (PNG integrity
         sweep, stem matching, JSON layout, and the semantic / model-confidence filters, which run
-        on the gfx950 kernels, as does the LPIPS min / max filter: saspa_aug_amd/filters.py; the per-class CLIP / ALIA
-        filters are baseline branches and raise NotImplementedError)
+        on the gfx950 kernels, as do the LPIPS min / max filter, the per-class CLIP filter of the Real-Guidance baseline
+        (`clip_filtering="per_class"`) and the `filter_confidence_higher_than` bound: saspa_aug_amd/filters.py; the ALIA
+        confidence filter is a baseline branch and raises NotImplementedError, as does any other `clip_filtering` type)
   calc_lpips_given_aug_json     all_utils/utils.py:764-817
   check_folder_of_images_with_pil   all_utils/utils.py:681-703
   init_logging                  all_utils/utils.py:593-612
@@ -181,15 +182,21 @@ def create_json_of_image_name_to_augmented_images_paths(dataset, augmented_image
                                                         conf_top_k: int = 10, filter_confidence_higher_than: int = None,
                                                         init_log=True, alia_conf_filtering=False, original_images_paths=None,
                                                         min_files=10, filter_models=None, weights_dir=None, device=None,
-                                                        lpips_model=None):
+                                                        lpips_model=None, class_filter=None):
     """`dataset` may be a dataset name (resolved through dataset_utils.DS_UTILS_DICT) or any
     object with `.original_images_paths`.  `filter_models` = (semantic, confidence) models built by the caller, `lpips_model` an
     `filters.LpipsAlex`; each is built here from `weights_dir` when its filter is on and it is not given.  `lpips_min` / `lpips_max`
     keep an augmented image when `lpips_min <= LPIPS_alex(original, augmented) <= lpips_max` (both grey, resized to `resize`); the
-    reference needs both once either is set (it raises a TypeError in its loop otherwise) -- here one bound alone is a ValueError."""
-    assert not (clip_filtering and model_confidence_based_filtering)
-    if any([clip_filtering, alia_conf_filtering]):
-        raise NotImplementedError("CLIP-per-class / ALIA filters are baseline branches (out of scope, SURVEY 2 row 7)")
+    reference needs both once either is set (it raises a TypeError in its loop otherwise) -- here one bound alone is a ValueError.
+    `clip_filtering` names a TYPE of CLIP filter and "per_class" is the only one (the reference: "out of 'per_class' only"): keep an
+    augmented image when CLIP-RN50's softmax over the class prompts of the whole dataset gives the source image's class at least
+    `1 / n_classes / clip_filtering_discount`; `class_filter` = a built `filters.ClassFilter` (its own discount then holds).
+    `filter_confidence_higher_than` drops, among the images that pass top-k, those whose softmax probability of the source label
+    exceeds it; a `filter_models` confidence model handed in must have been built with the same `too_high`."""
+    assert not (clip_filtering and model_confidence_based_filtering), "can't use both clip_filtering and model_confidence_based_filtering"
+    if alia_conf_filtering or (clip_filtering and clip_filtering != "per_class"):
+        raise NotImplementedError('clip_filtering knows the type "per_class" only; the ALIA confidence filter is a baseline branch '
+                                  "(not built)")
     if (lpips_min or lpips_max) and (lpips_min is None or lpips_max is None):
         raise ValueError(f"the LPIPS filter needs both bounds (lpips_min = {lpips_min}, lpips_max = {lpips_max})")
     lpips_filtering = bool(lpips_min or lpips_max)
@@ -211,41 +218,61 @@ def create_json_of_image_name_to_augmented_images_paths(dataset, augmented_image
         raise FileNotFoundError(f"augmented_image_folder_path = {augmented_image_folder_path} doesn't exist or has less "
                                 f"than {min_files} images")
     mapping = match_augmented_images(original_images_paths, os.listdir(augmented_image_folder_path), augmented_image_folder_path)
-    if semantic_filtering or model_confidence_based_filtering or lpips_filtering:
-        # the filter stage: CLIP-RN50 semantic filter, baseline-classifier top-k filter and LPIPS min / max filter on
-        # the gfx950 kernels
+    if semantic_filtering or model_confidence_based_filtering or lpips_filtering or clip_filtering:
+        # the filter stage: CLIP-RN50 semantic and per-class filters, baseline-classifier top-k / too-high filter and
+        # LPIPS min / max filter on the gfx950 kernels
         from . import filters
         if isinstance(dataset, str):
             from . import dataset_utils
             dataset = dataset_utils.DS_UTILS_DICT[dataset](print_func=logging.info)
         need_two = bool(semantic_filtering or model_confidence_based_filtering) and filter_models is None
         need_lpips = lpips_filtering and lpips_model is None
-        if need_two or need_lpips:
+        need_class = bool(clip_filtering) and class_filter is None
+        if need_two or need_lpips or need_class:
             if device is None:
                 device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
             if device is None:
-                raise RuntimeError("the semantic / model-confidence / LPIPS filters run on the MI355X only (no CPU path); pass "
-                                   "semantic_filtering=0, model_confidence_based_filtering=0 and no lpips bounds to write the "
-                                   "unfiltered aug.json")
-        if need_two:
-            filter_models = filters.build_filters(dataset, device, bool(semantic_filtering), bool(model_confidence_based_filtering),
-                                                  weights_dir, conf_top_k)
+                raise RuntimeError("the semantic / model-confidence / LPIPS / per-class CLIP filters run on the MI355X only (no CPU "
+                                   "path); pass semantic_filtering=0, model_confidence_based_filtering=0, clip_filtering=None and no "
+                                   "lpips bounds to write the unfiltered aug.json")
+        if need_two or need_class:
+            # one call: the two CLIP filters then share their image tower; a model the caller handed in is kept
+            built = filters.build_filters(dataset, device, bool(semantic_filtering) and need_two,
+                                          bool(model_confidence_based_filtering) and need_two, weights_dir, conf_top_k,
+                                          per_class=need_class, discount=clip_filtering_discount,
+                                          too_high=filter_confidence_higher_than)
+            if need_two:
+                filter_models = built[:2]
+            if need_class:
+                class_filter = built[2]
         if need_lpips:
             lpips_model = filters.build_lpips(device, weights_dir)
         sem, conf = filter_models if filter_models is not None else (None, None)
-        if filter_confidence_higher_than:
-            raise NotImplementedError("filter_confidence_higher_than is an ablation knob of the reference (unused by run_aug)")
+        too_high = filter_confidence_higher_than if model_confidence_based_filtering else None
+        if too_high and getattr(conf, "too_high", None) != too_high:
+            raise ValueError(f"filter_confidence_higher_than = {too_high} but the confidence model handed in was built with "
+                             f"too_high = {getattr(conf, 'too_high', None)}")
+        if clip_filtering:
+            logging.info(f"using CLIP filtering, of type {clip_filtering}")
+            logging.info(f"total number of classes = {len(class_filter.class_names)}")
+            logging.info(f"using CLIP filtering with threshold = {class_filter.threshold}")
+        if too_high:
+            logging.info(f"using model_confidence_based_filtering with filter_confidence_higher_than = {too_high}")
         mapping, counters = filters.apply_filters(mapping, original_images_paths, dataset, device, sem if semantic_filtering else None,
                                                   conf if model_confidence_based_filtering else None,
                                                   lpips=lpips_model if lpips_filtering else None, lpips_min=lpips_min,
-                                                  lpips_max=lpips_max, resize=resize)
+                                                  lpips_max=lpips_max, resize=resize,
+                                                  class_filter=class_filter if clip_filtering else None)
         if lpips_filtering:
             logging.info(f"For filter = lpips_min, filtered {counters['lpips']} images")
             logging.info(f"For filter = lpips_max, filtered {counters['lpips']} images")
+        if clip_filtering:
+            logging.info(f"For filter = clip_filtering, filtered {counters['clip_filtering']} images")
         if semantic_filtering:
             logging.info(f"For filter = semantic_filtering, filtered {counters['semantic']} images")
         if model_confidence_based_filtering:
             logging.info(f"For filter = not_in_top_{conf_top_k}, filtered {counters['not_in_top_k']} images")
+            logging.info(f"For filter = too_high_confidence, filtered {counters.get('too_high_confidence', 0)} images")
     Path(json_path).parent.mkdir(parents=True, exist_ok=True)
     with open(json_path, "w") as f:
         json.dump(mapping, f)

@@ -35,6 +35,15 @@ LIMITS = {
     "norm": dict(max=2.2, rms=0.9, bias=0.0145, slope=0.0095),
     "elem": dict(max=2.2, rms=1.0, bias=0.025, slope=0.09),
     "f32x3": dict(max=0.9, rms=0.2, bias=0.006, slope=0.036),
+    # the fused transformer-block chains (chain_*_scale).  "xattn" / "ff": launches with a zero residual, where the reference's last
+    # rounding point is the output itself and a right result differs from it by rare one-ulp flips; "as": the A-stationary GEMM's
+    # fused LayerNorm / GEGLU / V^T forms; "chain_res": the chains with the residual kept, where the output rounding dominates.
+    # max of "xattn" / "ff" is set by ONE legitimate flip at the element where a bf16 ulp is largest against the (worst-case, hence
+    # generous) chain magnitude; the subtle slips there (a truncating pack, tanh-GELU, a wrong scale) are caught by the slope
+    "xattn": dict(max=0.8, rms=0.002, bias=0.00015, slope=0.01),
+    "ff": dict(max=0.3, rms=0.0011, bias=0.0005, slope=0.006),
+    "as": dict(max=0.7, rms=0.1, bias=0.003, slope=0.03),
+    "chain_res": dict(max=0.4, rms=0.014, bias=0.0002, slope=0.02),
 }
 STATS = ("max", "rms", "bias", "slope")
 Z_NOISE = 8.0           # standard errors of bias / slope granted on top of the systematic limit (8 sigma: never by chance)
@@ -160,6 +169,36 @@ def norm_scale(xhat, gamma, beta, mu_rstd=None):
     if mu_rstd is not None:
         s = s + 2.0 ** -15 * (mu_rstd.double() * gamma.double()).abs()
     return _floor(s)
+
+
+# ------------------------------------------------------------------ magnitudes through a chain of fused stages
+# A fused kernel hands stage k's result to stage k + 1 as bf16 in registers.  A flipped rounding of that intermediate moves it by
+# at most one unit of ITS scale s^(k), and every product it enters by that times the other factor: stage k + 1's scale is the
+# magnitude of its own terms (the single-stage helpers above) plus s^(k) pushed through |W| (through p and |V| for attention).
+# The helpers only compose magnitudes; the limits they are checked against live in LIMITS.
+def chain_gemm_scale(a, b, bias=None, *, prev=None, residual=None):
+    """out = A B^T + bias (+ residual) with A an intermediate of per-element scale `prev` ([M, K], or None: A is an exact input):
+    gemm_scale's own terms + prev @ |B|^T."""
+    s = _abs64(a) @ _abs64(b).t()
+    if bias is not None:
+        s = s + _abs64(bias)
+    if prev is not None:
+        s = s + prev.double() @ _abs64(b).t()
+    if residual is not None:
+        s = s + _abs64(residual)
+    return _floor(s)
+
+
+def chain_attn_scale(p, v, o, k, prev_q, *, logit_unit=math.log(2.0)):
+    """O = p V with p [..., nq, nk] the normalised softmax weights of logits q k^T taken in the log2 domain (logit_unit = ln 2 per
+    logit unit; 1.0 for natural-log logits), q an intermediate of scale prev_q [..., nq, d]: attn_scale's own terms (sum_j p_ij
+    |v_j|) plus the query's scale pushed through the softmax: a logit moves by prev_q |k_j|, its weight by p_ij logit_unit times
+    that, the output by that times |v_j - o_i| (the first-order sensitivity of a normalised weighted mean)."""
+    p, v, o = p.double(), v.double(), o.double()
+    t = logit_unit * (prev_q.double() @ _abs64(k).transpose(-1, -2)) * p                 # [..., nq, nk]: |dp_ij| per unit
+    # sum_j t_ij |v_jc - o_ic| <= sum_j t_ij |v_jc| + (sum_j t_ij) |o_ic| would lose the cancellation a dominant key has (v_j = o_i)
+    push = torch.einsum("...qk,...qkc->...qc", t, (v.unsqueeze(-3) - o.unsqueeze(-2)).abs())
+    return _floor(p @ v.abs() + push)
 
 
 def elem_scale(*factors, floor=2.0 ** -8):

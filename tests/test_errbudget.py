@@ -2,7 +2,11 @@
 in another order, split-K slabs, bf16-rounded P and softmax level, bf16 intermediates where the kernels round, RNE output) stay
 within HALF the family's limits, and a catalogue of subtly wrong results ("mutants": truncating output rounding, a missing tail
 mask, a dropped key or K slice, a wrong eps / scale / variance, ...) exceeds TWICE the limits.  A later loosening or tightening of
-a limit that breaks either margin turns this file red."""
+a limit that breaks either margin turns this file red.
+
+The fused transformer-block kernels (saspa_xattn_block, saspa_ff_block, the A-stationary GEMM's fused forms) have their float64
+references here as well (xattn_ref / ff_ref / as_ref: the chain with RNE-to-bf16 at exactly the hand-offs the kernels pack at, each
+citing its source line), their magnitudes composed stage by stage (errbudget.chain_*_scale), and families of their own."""
 import functools
 import math
 
@@ -154,7 +158,7 @@ def _attn_ref(qq, kk, vv, scale, causal=False):
 
 
 def _attn_emul(qq, kk, vv, scale, *, causal=False, causal_shift=0, kt=64, level_bf16=False, l_from_bf16=False, rnd=rne,
-               pad_keys=0):
+               pad_keys=0, rnd_p=rne):
     """The kernels' online softmax: 64-key tiles, fp32 logits in the log2 domain, running level m (rounded to bf16 like v4 when
     level_bf16), p = exp2(s - m) rounded to bf16 for the P V MFMA, l summed from fp32 p (or from the bf16 p: the ones row),
     O rescaled when the level moves, RNE output.  pad_keys appends zero keys with zero values that are NOT masked (mutant)."""
@@ -177,7 +181,7 @@ def _attn_emul(qq, kk, vv, scale, *, causal=False, causal_shift=0, kt=64, level_
         alpha = torch.where(torch.isfinite(m), torch.exp2(m - m_new), torch.zeros_like(m))
         p = torch.exp2(st - m_new)
         p = torch.where(torch.isfinite(m_new), p, torch.zeros_like(p))
-        pb = p.to(BF).float()
+        pb = rnd_p(p).float()
         l = l * alpha + (pb if l_from_bf16 else p).sum(-1, keepdim=True)
         o = o * alpha + pb @ f32(vv[..., k0:k0 + kt, :])
         m = m_new
@@ -532,8 +536,394 @@ def _f32x3_cases():
     return out
 
 
-FAMILIES = {"gemm": (_gemm_cases, UNIT_BF16), "attn": (_attn_cases, UNIT_BF16), "norm": (_norm_cases, UNIT_BF16),
-            "elem": (_elem_cases, UNIT_BF16), "f32x3": (_f32x3_cases, UNIT_F32X3)}
+# ------------------------------------------------------------------ fused transformer-block chains
+# saspa_xattn_block, saspa_ff_block and the A-stationary GEMM's fused forms hand bf16 intermediates from stage to stage in
+# registers.  Each *_ref below is the float64 chain on the bf16 operands with RNE-to-bf16 applied exactly where the kernel packs
+# (every rounding point cites its source line in csrc/), and the chain magnitude of tests/errbudget.py; each *_emul is the same
+# chain in fp32 with the summation orders the kernels are free to choose -- and, by option, one slip at a time (the mutants).
+XA_C, XA_HEADS, XA_D = 320, 8, 40
+XA_QS = XA_D ** -0.5 * LOG2E           # the softmax scale and log2 e, folded into to_q (weights.pack_xattn_w's contract)
+LOWVAR_EVERY = 8                       # rows 3 mod 8 of the chain operands have variance 1e-6: there eps decides the result
+
+
+def f32v(t):
+    """A float64 tensor of fp32-representable values (gamma / beta / biases reach the kernels as fp32)."""
+    return t.float().double()
+
+
+def _chain_rows(m, seed, mean, std):
+    """bf16 token rows [m, 320]; every LOWVAR_EVERY-th row (from row 3) is 0.01 + 1e-3 z: its variance is a tenth of eps = 1e-5."""
+    x = _rand(m, XA_C, seed=seed) * std + mean
+    x[3::LOWVAR_EVERY] = _rand(m, XA_C, seed=seed + 50)[3::LOWVAR_EVERY] * 1e-3 + 0.01
+    return q(x)
+
+
+def _mm32(a, w, rev=False):
+    """a w^T accumulated in fp32, K ascending or descending."""
+    a, w = f32(a), f32(w)
+    return a.flip(1) @ w.flip(1).t() if rev else a @ w.t()
+
+
+def _xa_heads(t, nsamp):
+    """[nsamp * n, 320] -> [nsamp, heads, n, 40]."""
+    return t.reshape(nsamp, -1, XA_HEADS, XA_D).permute(0, 2, 1, 3)
+
+
+def _xa_flat(t):
+    return t.permute(0, 2, 1, 3).reshape(-1, XA_C)
+
+
+def xattn_operands(nsamp, ntok, nk, seed, shift=4.0):
+    """Operands of saspa_xattn_block that make tail slips visible (attn_operands' two features, through the fused chain):
+    - LayerNorm channel 0 is ~1 (beta 1, gamma 1/16) and channel 0 of every head's query reads it alone, channel 0 of every key is
+      -shift sqrt(d): every real logit carries a common offset of about -shift (natural log), which the softmax ignores but an
+      unmasked zero key at logit 0 does not -- it takes e^shift times its fair weight;
+    - the LAST key of sample s is 4 x the reference query of that sample's token ntok // 2: that token's output is the last value;
+    - keys and values differ per sample; every LOWVAR_EVERY-th row has variance 1e-6 (eps decides its LayerNorm)."""
+    m = nsamp * ntok
+    x = _chain_rows(m, seed, 0.3, 1.5)
+    gamma, beta = f32v(1 + 0.2 * _rand(XA_C, seed=seed + 1)), f32v(0.1 * _rand(XA_C, seed=seed + 2))
+    gamma[0], beta[0] = 1.0 / 16, 1.0
+    wq = _rand(XA_C, XA_C, seed=seed + 3, scale=1 / math.sqrt(XA_C))
+    wq[::XA_D] = 0.0
+    wq[::XA_D, 0] = 1.0
+    wq = q(wq * XA_QS)
+    wo = q(_rand(XA_C, XA_C, seed=seed + 4, scale=1 / math.sqrt(XA_C)))
+    bo = f32v(0.2 * _rand(XA_C, seed=seed + 5))
+    k = _rand(nsamp, nk, XA_C, seed=seed + 6)
+    v = q(_rand(nsamp, nk, XA_C, seed=seed + 7))
+    k[..., ::XA_D] = -shift * math.sqrt(XA_D)
+    op = dict(x=x, gamma=gamma, beta=beta, eps=1e-5, wq=wq, wo=wo, bo=bo, v=v, nsamp=nsamp, ntok=ntok, nk=nk)
+    if nk > 1:
+        qref = rne(rne(_ln_ref(x, gamma, beta, 1e-5)[0]) @ wq.t()) / XA_QS
+        k[:, -1] = 4.0 * qref.reshape(nsamp, ntok, XA_C)[:, ntok // 2]
+    op["k"] = q(k)
+    return op
+
+
+def xattn_ref(op, res=None):
+    """float64 saspa_xattn_block (csrc/saspa_xattn.hip) -> (out [M, 320], chain magnitude).  res: the residual (None: x)."""
+    from tests.errbudget import chain_attn_scale, chain_gemm_scale
+    x, g, b, eps, ns = op["x"], op["gamma"], op["beta"], op["eps"], op["nsamp"]
+    res = x if res is None else res
+    ln, xhat = _ln_ref(x, g, b, eps)
+    n = rne(ln)                                        # LayerNorm output packed to bf16: saspa_xattn.hip:154-155 (pack8)
+    qf = rne(n @ op["wq"].t())                         # Q^T accumulators (bias rows 0..319 are zero) packed: :219-221, :232-233
+    qh, kh, vh = _xa_heads(qf, ns), _xa_heads(op["k"], ns), _xa_heads(op["v"], ns)
+    s = qh @ kh.transpose(-1, -2)                      # log2-domain logits, fp32; keys >= nk are -inf (:303), here absent
+    p = rne(torch.exp2(s - s.amax(-1, keepdim=True)))  # P^T packed to bf16 for the P V MFMA: :312-314
+    den = p.sum(-1, keepdim=True)                      # row 40 of V^T is ones: the denominator is the sum of the bf16 P: :324-325
+    o = rne((p @ vh) / den)                            # O^T / denominator packed to bf16: :326-334
+    of = _xa_flat(o)
+    y = rne(of @ op["wo"].t() + op["bo"])              # to_out accumulators (bias = initial value) packed to bf16: finish(), :370-374
+    out = y + res                                      # staging tile unpacked, + residual in fp32 (:391-394); the pack that
+                                                       # follows (:395) is the output rounding the budget measures
+    s_n = norm_scale(xhat, g, b, mu_rstd(x, eps))
+    s_q = _xa_heads(chain_gemm_scale(n, op["wq"], prev=s_n), ns)
+    s_o = torch.stack([chain_attn_scale(p[i] / den[i], vh[i], o[i], kh[i], s_q[i]) for i in range(ns)])
+    return out, chain_gemm_scale(of, op["wo"], op["bo"], prev=_xa_flat(s_o), residual=res)
+
+
+def xattn_emul(op, res=None, *, rev=False, onepass=False, rnd_p=rne, rnd_o=rne, drop_last=False, pad_keys=0, qscale=1.0, eps_mul=1.0,
+               bo_cols=XA_C, res_neighbour=False, prev_sample_keys=False, drop_tail_head=None):
+    """The fused chain in fp32: LayerNorm (_ln_emul), to_q, ONE 96-key tile of the online softmax with the denominator summed from
+    the bf16 P (_attn_emul, kt = 96, l_from_bf16), to_out with the two-rounding epilogue.  The options are the mutants."""
+    x, ns, nk = op["x"], op["nsamp"], op["nk"]
+    res = (x if res is None else res).clone()
+    if res_neighbour:                                  # the last row of every sample adds its neighbour's residual
+        last = torch.arange(1, ns + 1) * op["ntok"] - 1
+        res[last] = res[last - 1]
+    n = _ln_emul(x, op["gamma"], op["beta"], op["eps"], onepass=onepass, eps_used=op["eps"] * eps_mul)
+    qh = _xa_heads(rne(_mm32(n, op["wq"], rev) * qscale), ns).clone()
+    if drop_tail_head is not None:                     # the tail block (channels 32..39) of one head left out of Q K^T
+        qh[:, drop_tail_head, :, 32:] = 0.0
+    kh, vh = _xa_heads(op["k"], ns), _xa_heads(op["v"], ns)
+    if prev_sample_keys:
+        kh, vh = kh.roll(1, 0), vh.roll(1, 0)
+    if drop_last:
+        kh, vh = kh[..., :-1, :], vh[..., :-1, :]
+    # (_attn_emul multiplies by scale * log2 e: the queries are already in the log2 domain)
+    o = _attn_emul(qh, kh, vh, 1.0 / LOG2E, kt=96, l_from_bf16=True, rnd=rnd_o, rnd_p=rnd_p, pad_keys=pad_keys)
+    bo = f32(op["bo"]).clone()
+    bo[bo_cols:] = 0.0
+    return rne(f32(rne(_mm32(_xa_flat(o), op["wo"], rev) + bo)) + f32(res))
+
+
+def _one_flip(ref, s):
+    """The reference with ONE output a bf16 ulp off, at the element where an ulp is largest against the scale.  With a zero residual
+    the reference's last rounding point is the output, so a right kernel differs from it by such flips only -- anywhere: the max
+    limit has to grant the worst-placed one."""
+    ulp = torch.exp2(torch.floor(torch.log2(ref.abs().clamp_min(1e-30))) - 7)
+    i = int((ulp / s).argmax())
+    got = ref.clone()
+    got.view(-1)[i] += ulp.reshape(-1)[i]
+    return got
+
+
+def _xattn_cases(zero_res=True):
+    """Zero residual ('xattn': the branch alone sets the scale; the reference's last rounding point is then the output itself, so
+    a right result differs from it by rare one-ulp flips only) or the residual x ('chain_res': the output rounding dominates)."""
+    out = []
+    shapes = [(2, 256, 77, 101), (2, 256, 33, 111), (3, 128, 1, 121)] if zero_res else [(2, 256, 77, 101)]
+    for (nsamp, ntok, nk, seed) in shapes:                                  # (one key: the output is to_out of a row of V)
+        op = xattn_operands(nsamp, ntok, nk, seed)
+        res = torch.zeros_like(op["x"]) if zero_res else None
+        ref, s = xattn_ref(op, res)
+        tag = f"xattn {nsamp}x{ntok} nk={nk} {'zero residual' if zero_res else 'residual x'}"
+        emu = functools.partial(xattn_emul, op, res)
+        out.append((f"legit fp32 {tag}", emu(), ref, s, True))
+        out.append((f"legit reversed-K, one-pass LayerNorm statistics {tag}", emu(rev=True, onepass=True), ref, s, True))
+        if not zero_res:
+            out.append((f"mutant residual of the neighbouring row in a sample's last row {tag}", emu(res_neighbour=True), ref, s,
+                        False))
+            continue
+        out.append((f"legit one output flipped by an ulp, worst placed {tag}", _one_flip(ref, s), ref, s, True))
+        out.append((f"mutant to_out bias missing on last 8 columns {tag}", emu(bo_cols=XA_C - 8), ref, s, False))
+        if nk == 1:
+            continue
+        out.append((f"mutant LayerNorm eps x 10 {tag}", emu(eps_mul=10.0), ref, s, False))
+        out.append((f"mutant truncating pack of P {tag}", emu(rnd_p=trunc), ref, s, False))
+        out.append((f"mutant truncating pack of O {tag}", emu(rnd_o=trunc), ref, s, False))
+        out.append((f"mutant last key dropped {tag}", emu(drop_last=True), ref, s, False))
+        # (the denominator counts the pad keys, as a ones row over all 96 slots would: with the ones row zero past nk an unmasked
+        # zero key changes nothing but the level, which is why the GPU file poisons the pad KEYS and asks for bit-equality)
+        out.append((f"mutant keys nk..95 left unmasked (zero logit) {tag}", emu(pad_keys=96 - nk), ref, s, False))
+        out.append((f"mutant softmax scale (d+8)^-0.5 {tag}", emu(qscale=math.sqrt(XA_D / (XA_D + 8.0))), ref, s, False))
+        out.append((f"mutant sample s reads sample s-1's keys {tag}", emu(prev_sample_keys=True), ref, s, False))
+        out.append((f"mutant channels 32..39 of one head dropped from Q K^T {tag}", emu(drop_tail_head=5), ref, s, False))
+    return out
+
+
+def ff_operands(m, f, seed):
+    x = _chain_rows(m, seed, 0.2, 1.5)
+    return dict(x=x, gamma=f32v(1 + 0.1 * _rand(XA_C, seed=seed + 1)), beta=f32v(0.1 * _rand(XA_C, seed=seed + 2)), eps=1e-5,
+                w1=q(_rand(2 * f, XA_C, seed=seed + 3, scale=1 / math.sqrt(XA_C))),
+                b1=f32v(_rand(2 * f, seed=seed + 4, scale=0.2) + torch.cat([torch.ones(f), torch.zeros(f)])),
+                w2=q((_rand(XA_C, f, seed=seed + 5) + 0.5) / math.sqrt(f)), b2=f32v(_rand(XA_C, seed=seed + 6, scale=0.2)), f=f)
+
+
+def ff_ref(op, res=None, ln=True):
+    """float64 saspa_ff_block (csrc/saspa_ff.hip; the four-wave and the wave-specialised kernel round at the same points) ->
+    (out [M, 320], chain magnitude).  res: the residual (None: x)."""
+    from tests.errbudget import chain_gemm_scale
+    x, g, b, eps, f = op["x"], op["gamma"], op["beta"], op["eps"], op["f"]
+    res = x if res is None else res
+    s_n = None
+    n = x
+    if ln:
+        lnv, xhat = _ln_ref(x, g, b, eps)
+        n = rne(lnv)                                   # LayerNorm output packed to bf16: saspa_ff.hip:151-152 (ws: :411-412)
+        s_n = norm_scale(xhat, g, b, mu_rstd(x, eps))
+    a = n @ op["w1"].t() + op["b1"]                    # [v ; g], fp32 accumulators with b1 as the initial value: :176-179
+    hv, hg = a[:, :f], a[:, f:]
+    h = rne(hv * F.gelu(hg))                           # the gated hidden state packed to bf16: :265-266 (ws: :490-491)
+    y = rne(h @ op["w2"].t())                          # Y^T accumulators packed into the staging tile BEFORE b2: :281 (ws: :547)
+    y = rne(y + op["b2"])                              # + b2 in fp32, packed: :302-303 (ws: :566-567)
+    out = y + res                                      # + residual in fp32: :306 (ws: :570); the pack that follows is the
+                                                       # output rounding the budget measures
+    mv = chain_gemm_scale(n, op["w1"][:f], op["b1"][:f], prev=s_n)
+    mg = chain_gemm_scale(n, op["w1"][f:], op["b1"][f:], prev=s_n)
+    s_h = geglu_gemm_scale(hv, hg, mv, mg)
+    return out, chain_gemm_scale(h, op["w2"], op["b2"], prev=s_h, residual=res)
+
+
+def _erf_as(x):
+    """common.h fast_erf: Abramowitz & Stegun 7.1.26 (|error| <= 1.5e-7) in fp32."""
+    ax = x.abs()
+    t = 1.0 / (0.3275911 * ax + 1.0)
+    poly = ((((1.061405429 * t - 1.453152027) * t + 1.421413741) * t - 0.284496736) * t + 0.254829592) * t
+    return torch.copysign(1.0 - poly * torch.exp2(-ax * ax * 1.4426950408889634), x)
+
+
+def ff_emul(op, res=None, ln=True, *, rev=False, onepass=False, gelu="erf", rnd_h=rne, swap_slice=None, b1_missing_slice=None,
+            drop_last32=False, b2_cols=XA_C, skip_ln=False):
+    """The fused chain in fp32; value and gate stay fp32 until their product is rounded.  The options are the mutants."""
+    x, f = op["x"], op["f"]
+    res = x if res is None else res
+    n = _ln_emul(x, op["gamma"], op["beta"], op["eps"], onepass=onepass) if ln and not skip_ln else x
+    b1 = f32(op["b1"]).clone()
+    if b1_missing_slice is not None:
+        sl = slice(32 * b1_missing_slice, 32 * b1_missing_slice + 32)
+        b1[sl] = 0.0
+        b1[f:][sl] = 0.0
+    a = _mm32(n, op["w1"], rev) + b1
+    hv, hg = a[:, :f].clone(), a[:, f:].clone()
+    if swap_slice is not None:                         # one 32-feature slice packed gates first
+        sl = slice(32 * swap_slice, 32 * swap_slice + 32)
+        hv[:, sl], hg[:, sl] = a[:, f:][:, sl], a[:, :f][:, sl]
+    if gelu == "erf":
+        gl = F.gelu(hg)
+    elif gelu == "tanh":
+        gl = F.gelu(hg, approximate="tanh")
+    else:
+        gl = 0.5 * hg * (1.0 + _erf_as(hg * 0.70710678118654752440))
+    h = rnd_h(hv * gl)
+    if drop_last32:
+        h = h.clone()
+        h[:, -32:] = 0.0
+    b2 = f32(op["b2"]).clone()
+    b2[b2_cols:] = 0.0
+    return rne(f32(rne(f32(rne(_mm32(h, op["w2"], rev))) + b2)) + f32(res))
+
+
+def _ff_cases(zero_res=True):
+    out = []
+    shapes = [(128, 32, True, 201), (128, 64, True, 211), (256, 1280, True, 221), (256, 1280, False, 231)] if zero_res else \
+        [(128, 64, True, 241)]
+    for (m, f, ln, seed) in shapes:
+        op = ff_operands(m, f, seed)
+        res = torch.zeros_like(op["x"]) if zero_res else None
+        ref, s = ff_ref(op, res, ln)
+        tag = f"ff {m}x{f}{'' if ln else ' no LayerNorm'} {'zero residual' if zero_res else 'residual x'}"
+        emu = functools.partial(ff_emul, op, res, ln)
+        out.append((f"legit fp32, value and gate fp32 until the product {tag}", emu(), ref, s, True))
+        out.append((f"legit reversed-K, one-pass LayerNorm statistics {tag}", emu(rev=True, onepass=True), ref, s, True))
+        out.append((f"legit polynomial erf {tag}", emu(gelu="as"), ref, s, True))
+        if not zero_res:
+            continue
+        out.append((f"legit one output flipped by an ulp, worst placed {tag}", _one_flip(ref, s), ref, s, True))
+        # tanh-GELU differs from erf-GELU by at most 5e-4, the size of the hidden state's own bf16 rounding; behind 1280 random
+        # columns of W2 with a LayerNorm in front it is inside the sampling noise of 256 rows.  It shows where few features are mixed
+        # (the GPU file's F = 32 and F = 64 cases) and without the LayerNorm, where the gates are wider.
+        if f <= 64 or not ln:
+            out.append((f"mutant tanh-gelu {tag}", emu(gelu="tanh"), ref, s, False))
+        out.append((f"mutant truncated hidden state {tag}", emu(rnd_h=trunc), ref, s, False))
+        out.append((f"mutant value and gate rows of one 32-feature slice swapped {tag}", emu(swap_slice=f // 32 - 1), ref, s, False))
+        out.append((f"mutant b1 missing on one slice {tag}", emu(b1_missing_slice=f // 64), ref, s, False))
+        out.append((f"mutant last 32 hidden features dropped {tag}", emu(drop_last32=True), ref, s, False))
+        out.append((f"mutant b2 missing on last 8 columns {tag}", emu(b2_cols=XA_C - 8), ref, s, False))
+        if ln:
+            out.append((f"mutant LayerNorm skipped {tag}", emu(skip_ln=True), ref, s, False))
+    return out
+
+
+def as_operands(m, n, seed, kind="normal", geglu=False):
+    """A-stationary GEMM operands (K = 320): x of `kind` (_norm_inputs, plus 'const': every third row constant), w, bias,
+    LayerNorm gamma / beta, a residual."""
+    x = _norm_inputs("normal" if kind == "const" else kind, (m, XA_C), seed)
+    if kind == "const":
+        x[::3] = q(torch.full((XA_C,), 0.7, dtype=torch.float64))
+    return dict(x=x, w=q(_rand(n, XA_C, seed=seed + 1, scale=1 / math.sqrt(XA_C))), b=f32v(_rand(n, seed=seed + 2)),
+                gamma=f32v(1 + 0.3 * _rand(XA_C, seed=seed + 3)), beta=f32v(0.2 * _rand(XA_C, seed=seed + 4)),
+                res=q(_rand(m, n // 2 if geglu else n, seed=seed + 5)))
+
+
+def as_ref(op, *, bias=True, residual=False, ln=None, geglu=False):
+    """float64 A-stationary GEMM (csrc/saspa_gemm_as.hip) -> (out, chain magnitude).  ln: eps of the fused LayerNorm or None;
+    geglu: out = v * gelu(g) with rows 0..N/2-1 of w the values, N/2.. the gates (the UNPACKED order)."""
+    from tests.errbudget import chain_gemm_scale
+    x, w = op["x"], op["w"]
+    b = op["b"] if bias else None
+    s_n, n = None, x
+    if ln is not None:
+        lnv, xhat = _ln_ref(x, op["gamma"], op["beta"], ln)
+        n = rne(lnv)                                   # fused LayerNorm output packed to bf16: saspa_gemm_as.hip:211-212
+        s_n = norm_scale(xhat, op["gamma"], op["beta"], mu_rstd(x, ln))
+    y = n @ w.t() + (0 if b is None else b)
+    if geglu:
+        f = w.shape[0] // 2
+        mv = chain_gemm_scale(n, w[:f], None if b is None else b[:f], prev=s_n)
+        mg = chain_gemm_scale(n, w[f:], None if b is None else b[f:], prev=s_n)
+        # value and gate stay fp32 accumulators (Done.sv); ONE rounding, of the product (:329-330): the output rounding
+        return y[:, :f] * F.gelu(y[:, f:]), geglu_gemm_scale(y[:, :f], y[:, f:], mv, mg)
+    if residual:
+        # accumulators (bias = initial value) packed to bf16 by finish() (:316), the staging tile unpacked and the residual added
+        # in fp32 (:355-359); the pack that follows (:360) is the output rounding.  Without a residual :316 IS the output rounding.
+        y = rne(y) + op["res"]
+    return y, chain_gemm_scale(n, w, b, prev=s_n, residual=op["res"] if residual else None)
+
+
+def as_emul(op, *, bias=True, residual=False, ln=None, geglu=False, rev=False, onepass=False, eps_used=None, unbiased=False,
+            gate_shift=0):
+    x, w = op["x"], op["w"]
+    n = x if ln is None else _ln_emul(x, op["gamma"], op["beta"], ln, onepass=onepass, eps_used=eps_used, unbiased=unbiased)
+    y = _mm32(n, w, rev) + (f32(op["b"]) if bias else 0.0)
+    if geglu:
+        f = w.shape[0] // 2
+        return rne(y[:, :f] * F.gelu(y[:, f:].roll(gate_shift, 1)))
+    y = rne(y)
+    return rne(f32(y) + f32(op["res"])) if residual else y
+
+
+def vt_tail(y, n_split, rows_per_batch):
+    """The transposed tail of the Q | K | V^T launch: columns >= n_split of y [M, N] as [batch, N - n_split, rows_per_batch]."""
+    return y[:, n_split:].reshape(-1, rows_per_batch, y.shape[1] - n_split).transpose(1, 2)
+
+
+def _as_plain_cases():
+    """The unfused A-stationary forms: they join the 'gemm' family under its limits (the two-rounding residual epilogue is a
+    documented rounding point of the reference)."""
+    out = []
+    for (m, n, seed) in [(257, 64, 301), (449, 320, 305)]:
+        op = as_operands(m, n, seed)
+        for name, kw in [("plain", dict(bias=False)), ("bias", dict()), ("residual", dict(residual=True))]:
+            ref, s = as_ref(op, **kw)
+            tag = f"A-stationary {name} {m}x320x{n}"
+            out.append((f"legit fp32 {tag}", as_emul(op, **kw), ref, s, True))
+            out.append((f"legit reversed-K {tag}", as_emul(op, rev=True, **kw), ref, s, True))
+            g = as_emul(op, **kw)
+            g[-1] = g[-2]
+            out.append((f"mutant ragged last block: its last row copies its neighbour {tag}", g, ref, s, False))
+    return out
+
+
+def _as_cases():
+    out = []
+    # fused LayerNorm (+ bias); x std 0.5 for the eps 1e-3 mutant (the variance has to be small enough for 1e-3 to matter)
+    for (m, n, kind, seed) in [(512, 320, "normal", 311), (384, 320, "lowvar", 315), (384, 64, "offset", 319), (257, 320, "const", 323)]:
+        op = as_operands(m, n, seed, kind)
+        if kind == "normal":
+            op["x"] = q(op["x"] * 0.25)
+        ref, s = as_ref(op, ln=1e-5)
+        tag = f"A-stationary LayerNorm {m}x320x{n} {kind}"
+        out.append((f"legit fp32 {tag}", as_emul(op, ln=1e-5), ref, s, True))
+        out.append((f"legit reversed-K, one-pass statistics {tag}", as_emul(op, ln=1e-5, rev=True, onepass=True), ref, s, True))
+        if kind == "normal":
+            out.append((f"mutant fused LayerNorm n-1 variance {tag}", as_emul(op, ln=1e-5, unbiased=True), ref, s, False))
+            out.append((f"mutant fused LayerNorm eps 1e-3 {tag}", as_emul(op, ln=1e-5, eps_used=1e-3), ref, s, False))
+        if kind == "lowvar":
+            out.append((f"mutant fused LayerNorm eps x 10 {tag}", as_emul(op, ln=1e-5, eps_used=1e-4), ref, s, False))
+        g = as_emul(op, ln=1e-5)
+        g[-1] = g[-2]
+        out.append((f"mutant ragged last block: its last row copies its neighbour {tag}", g, ref, s, False))
+    # fused LayerNorm + GEGLU: 160-column packing (N = 320) and 128-column packing (N = 1024)
+    for (m, n, seed) in [(256, 320, 331), (256, 1024, 335)]:
+        op = as_operands(m, n, seed, geglu=True)
+        ref, s = as_ref(op, ln=1e-5, geglu=True)
+        tag = f"A-stationary LayerNorm + GEGLU {m}x320x{n}"
+        out.append((f"legit fp32, value and gate fp32 until the product {tag}", as_emul(op, ln=1e-5, geglu=True), ref, s, True))
+        out.append((f"legit reversed-K, one-pass statistics {tag}", as_emul(op, ln=1e-5, geglu=True, rev=True, onepass=True), ref, s,
+                    True))
+        pack = (160 if n % 160 == 0 else 128) // 2
+        out.append((f"mutant fused-GEGLU gate and value from different 128-column packs {tag}",
+                    as_emul(op, ln=1e-5, geglu=True, gate_shift=pack), ref, s, False))
+    # Q | K | V^T: 4 samples of 128 rows, the row-major part and the transposed tail budgeted separately
+    op = as_operands(512, 960, 341)
+    ref, s = as_ref(op, bias=False, ln=1e-5)
+    for rev in (False, True):
+        g = as_emul(op, bias=False, ln=1e-5, rev=rev, onepass=rev)
+        nm = "reversed-K, one-pass statistics" if rev else "fp32"
+        out.append((f"legit {nm} Q | K row-major part", g[:, :640], ref[:, :640], s[:, :640], True))
+        out.append((f"legit {nm} V^T tail", vt_tail(g, 640, 128), vt_tail(ref, 640, 128), vt_tail(s, 640, 128), True))
+    gt = vt_tail(as_emul(op, bias=False, ln=1e-5), 640, 128).clone()
+    gt[:-1, :, -1] = gt[1:, :, 0]
+    out.append(("mutant V^T tail: first row of sample s+1 where the last row of sample s belongs", gt, vt_tail(ref, 640, 128),
+                vt_tail(s, 640, 128), False))
+    return out
+
+
+def _gemm_family_cases():
+    return _gemm_cases() + _as_plain_cases()
+
+
+def _chain_res_cases():
+    """The chains with the residual kept (x itself): the output rounding of branch + residual dominates the error."""
+    return _xattn_cases(zero_res=False) + _ff_cases(zero_res=False)
+
+
+FAMILIES = {"gemm": (_gemm_family_cases, UNIT_BF16), "attn": (_attn_cases, UNIT_BF16), "norm": (_norm_cases, UNIT_BF16),
+            "elem": (_elem_cases, UNIT_BF16), "f32x3": (_f32x3_cases, UNIT_F32X3), "xattn": (_xattn_cases, UNIT_BF16),
+            "ff": (_ff_cases, UNIT_BF16), "as": (_as_cases, UNIT_BF16), "chain_res": (_chain_res_cases, UNIT_BF16)}
 
 
 @functools.lru_cache(maxsize=None)
@@ -599,7 +989,18 @@ def test_catalogue_is_complete():
     names = " | ".join(r[0] for fam in FAMILIES for r in _measured(fam) if not r[1])
     for want in ["truncation", "unmasked zero key", "last key dropped", "last 8 of K", "last 32 of K", "bias missing on last 8",
                  "alpha before bias", "tail row copies", "causal mask shifted", "(d+8)^-0.5", "eps swapped", "eps 1e-3",
-                 "n-1 variance", "tanh-gelu", "hi*lo term dropped", "layernorm", "groupnorm"]:
+                 "n-1 variance", "tanh-gelu", "hi*lo term dropped", "layernorm", "groupnorm",
+                 # the fused transformer-block chains
+                 "truncating pack of P", "truncating pack of O", "last key dropped xattn", "keys nk..95 left unmasked",
+                 "softmax scale (d+8)^-0.5 xattn", "LayerNorm eps x 10 xattn", "to_out bias missing on last 8 columns",
+                 "residual of the neighbouring row in a sample's last row", "sample s reads sample s-1's keys",
+                 "channels 32..39 of one head dropped from Q K^T",
+                 "tanh-gelu ff", "truncated hidden state", "value and gate rows of one 32-feature slice swapped",
+                 "b1 missing on one slice", "last 32 hidden features dropped", "b2 missing on last 8 columns", "LayerNorm skipped",
+                 "fused LayerNorm n-1 variance", "fused LayerNorm eps 1e-3",
+                 "fused-GEGLU gate and value from different 128-column packs",
+                 "V^T tail: first row of sample s+1 where the last row of sample s belongs",
+                 "ragged last block: its last row copies its neighbour A-stationary"]:
         assert want in names, want
 
 

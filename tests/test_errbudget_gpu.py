@@ -3,6 +3,7 @@ on the CPU: every case builds a float64 reference from the bf16 operands and its
 toward-zero bias / slope against the family's limits.  Each family also launches its kernel once with one argument perturbed (a
 negative control: an ordinary valid launch) and asserts that the budget REJECTS that result against the unperturbed reference, so
 every test here is shown to be able to fail on the hardware."""
+import functools
 import math
 
 import pytest
@@ -14,8 +15,9 @@ from saspa_aug_amd import ops
 from saspa_aug_amd import weights as W
 from tests.errbudget import (LIMITS, UNIT_BF16, UNIT_F32X3, attn_scale, check_budget, conv_scale, elem_scale, fmt, gemm_scale,
                              geglu_gemm_scale, norm_scale, rejects)
-from tests.test_errbudget import (CFG_COEF, _attn_ref, _gemm_operands, _ln_ref, _norm_inputs, _rand, attn_operands, cfg_ddim_ref,
-                                  gn_kernel_ref, mu_rstd, q)
+from tests.test_errbudget import (CFG_COEF, XA_C, XA_D, _attn_ref, _gemm_operands, _ln_ref, _norm_inputs, _rand, as_operands,
+                                  as_ref, attn_operands, cfg_ddim_ref, ff_operands, ff_ref, gn_kernel_ref, mu_rstd, q, vt_tail,
+                                  xattn_operands, xattn_ref)
 from tests.util import from_nhwc, to_nhwc
 
 pytestmark = pytest.mark.gpu
@@ -279,3 +281,195 @@ def test_cfg_ddim_budget(dev):
         return got[:2, :, :4]
     _check(run(CFG_COEF["gs"]), ref, s, "elem", "cfg + ddim")
     _control(run(7.0), ref, s, "elem", "cfg + ddim guidance 7.0 against 7.5")
+
+
+# ------------------------------------------------------------------ fused transformer-block chains
+# saspa_xattn_block, saspa_ff_block and the A-stationary GEMM's fused forms against the float64 chains of tests/test_errbudget.py
+# (every bf16 hand-off of the kernels restated there with its source line).  Families: "xattn" / "ff" with a zero residual (the
+# branch alone sets the scale), "chain_res" with the residual kept, "as" for the fused LayerNorm / GEGLU / V^T forms; the unfused
+# A-stationary launches stay in "gemm".  References and magnitudes are built once per case (float64 on the CPU).
+def _wide(t, dev, cols, fill):
+    """t [M, C] as a view of a wider [M, cols] buffer filled with `fill`."""
+    buf = torch.full((t.shape[0], cols), fill, device=dev, dtype=BF)
+    buf[:, : t.shape[1]] = t.to(dev, BF)
+    return buf, buf[:, : t.shape[1]]
+
+
+XATTN_CASES = [(2, 256, 77), (3, 256, 1), (2, 512, 31), (2, 256, 32), (2, 256, 33), (2, 256, 64), (2, 256, 65), (1, 512, 96)]
+
+
+@functools.lru_cache(maxsize=None)
+def _xattn_case(nsamp, ntok, nk):
+    op = xattn_operands(nsamp, ntok, nk, 400 + nk)
+    return op, xattn_ref(op, torch.zeros_like(op["x"]))
+
+
+def _xattn_launch(dev, op, *, nk=None, eps_mul=1.0, residual="zero", kf_edit=None, x=None, out=None):
+    nk = op["nk"] if nk is None else nk
+    w, bias = W.pack_xattn_w(op["wq"].float(), op["wo"].float(), op["bo"].float())
+    kf, vf = W.xattn_kv_fragments(op["k"][:, :nk].to(dev, BF), op["v"][:, :nk].to(dev, BF))
+    if kf_edit is not None:
+        kf = kf_edit(kf)
+    xd = op["x"].to(dev, BF) if x is None else x
+    res = torch.zeros_like(op["x"]).to(dev, BF) if residual == "zero" else None
+    got = ops.xattn_block(xd, (op["gamma"].float().to(dev), op["beta"].float().to(dev), op["eps"] * eps_mul), w.to(dev, BF),
+                          bias.to(dev), kf, vf, nk, op["ntok"], residual=res, out=out)
+    return got.float().cpu()
+
+
+@pytest.mark.parametrize("nsamp,ntok,nk", XATTN_CASES)
+def test_xattn_block_budget(dev, nsamp, ntok, nk):
+    op, (ref, s) = _xattn_case(nsamp, ntok, nk)
+    tag = f"xattn_block {nsamp}x{ntok} tokens, {nk} keys"
+    got = _xattn_launch(dev, op)
+    _check(got, ref, s, "xattn", tag)
+    if nk in (33, 77):
+        # the pad slots of kf (keys nk..95; found by packing an indicator through the same function) overwritten with a large key
+        # along the queries' common direction (channel 0 of every head), vf's pad left zero as the header's contract says: only
+        # the kernel's own mask stands between those keys and the softmax level, and the result must not change by a bit
+        ind = torch.zeros(nsamp, 96, XA_C, device=dev, dtype=BF)
+        ind[:, nk:, ::XA_D] = 1.0
+        pad = W.xattn_kv_fragments(ind, torch.zeros_like(ind))[0] == 1.0
+        assert int(pad.sum()) == nsamp * 8 * (96 - nk)
+        poisoned = _xattn_launch(dev, op, kf_edit=lambda kf: torch.where(pad, torch.full_like(kf, 8.0 * math.sqrt(XA_D)), kf))
+        assert torch.equal(poisoned, got), f"{tag}: a poisoned pad key changed the result: the tail mask does not decide alone"
+        print(f"\n[bit-equal] xattn {tag}: pad keys poisoned")
+    if nk > 1:
+        _control(_xattn_launch(dev, op, nk=nk - 1), ref, s, "xattn", f"{tag} with nk - 1")
+        _control(_xattn_launch(dev, op, eps_mul=10.0), ref, s, "xattn", f"{tag} with ln_eps x 10 (low-variance rows)")
+
+
+def test_xattn_block_residual_and_pitches(dev):
+    """residual=None (the kernel re-reads x), and x / out as views of wider buffers: bit-equal to the dense launch, nothing written
+    outside the view."""
+    nsamp, ntok, nk = 2, 256, 77
+    op, (ref0, s0) = _xattn_case(nsamp, ntok, nk)
+    ref, s = xattn_ref(op, None)
+    got = _xattn_launch(dev, op, residual=None)
+    _check(got, ref, s, "chain_res", f"xattn_block {nsamp}x{ntok} tokens, {nk} keys, residual = x")
+    bad = got.clone()
+    last = torch.arange(1, nsamp + 1) * ntok - 1
+    bad[last] += (op["x"][last - 1] - op["x"][last]).float()             # (what reading the neighbour's residual would give)
+    _control(bad, ref, s, "chain_res", "xattn_block residual of the neighbouring row in a sample's last row (host-side)")
+    dense = _xattn_launch(dev, op)
+    xbuf, xv = _wide(op["x"], dev, 384, float("nan"))
+    obuf, ov = _wide(torch.zeros_like(op["x"]), dev, 448, float("nan"))
+    pitched = _xattn_launch(dev, op, x=xv, out=ov)
+    assert torch.equal(pitched, dense)
+    assert torch.isnan(obuf[:, XA_C:]).all() and torch.isnan(xbuf[:, XA_C:]).all()
+    _check(pitched, ref0, s0, "xattn", "xattn_block x pitch 384, out pitch 448")
+
+
+FF_CASES = [(128, 32, True), (128, 64, True), (384, 1280, True), (256, 1280, False)]
+
+
+@functools.lru_cache(maxsize=None)
+def _ff_case(m, f, ln):
+    op = ff_operands(m, f, 500 + f + m)
+    return op, ff_ref(op, torch.zeros_like(op["x"]), ln)
+
+
+def _ff_launch(dev, op, ln, *, eps_mul=1.0, residual="zero", x=None, out=None):
+    w1p, b1p, w2f, b2p = W.pack_ff_block(op["w1"].float(), op["b1"].float(), op["w2"].float(), op["b2"].float())
+    xd = op["x"].to(dev, BF) if x is None else x
+    res = torch.zeros_like(op["x"]).to(dev, BF) if residual == "zero" else None
+    lnp = (op["gamma"].float().to(dev), op["beta"].float().to(dev), op["eps"] * eps_mul) if ln else None
+    got = ops.ff_block(xd, lnp, w1p.to(dev, BF), b1p.to(dev), w2f.to(dev, BF), b2p.to(dev), residual=res, out=out)
+    return got.float().cpu()
+
+
+@pytest.mark.parametrize("ws", ["1", "0"])
+@pytest.mark.parametrize("m,f,ln", FF_CASES)
+def test_ff_block_budget(dev, monkeypatch, m, f, ln, ws):
+    monkeypatch.setenv("SASPA_FF_WS", ws)
+    op, (ref, s) = _ff_case(m, f, ln)
+    tag = f"ff_block {m}x{f}{'' if ln else ' no LayerNorm'} SASPA_FF_WS={ws}"
+    got = _ff_launch(dev, op, ln)
+    _check(got, ref, s, "ff", tag)
+    if ln:
+        _control(_ff_launch(dev, op, ln, eps_mul=10.0), ref, s, "ff", f"{tag} with ln_eps x 10 (low-variance rows)")
+    if ws == "1":
+        monkeypatch.setenv("SASPA_FF_WS", "0")
+        assert torch.equal(_ff_launch(dev, op, ln), got), "the wave-specialised and the four-wave form differ"
+
+
+@pytest.mark.parametrize("ws", ["1", "0"])
+def test_ff_block_residual_and_pitches(dev, monkeypatch, ws):
+    monkeypatch.setenv("SASPA_FF_WS", ws)
+    m, f = 128, 64
+    op, (ref0, s0) = _ff_case(m, f, True)
+    ref, s = ff_ref(op, None, True)
+    _check(_ff_launch(dev, op, True, residual=None), ref, s, "chain_res", f"ff_block {m}x{f} residual = x SASPA_FF_WS={ws}")
+    dense = _ff_launch(dev, op, True)
+    xbuf, xv = _wide(op["x"], dev, 384, float("nan"))
+    obuf, ov = _wide(torch.zeros_like(op["x"]), dev, 448, float("nan"))
+    pitched = _ff_launch(dev, op, True, x=xv, out=ov)
+    assert torch.equal(pitched, dense)
+    assert torch.isnan(obuf[:, XA_C:]).all() and torch.isnan(xbuf[:, XA_C:]).all()
+    _check(pitched, ref0, s0, "ff", f"ff_block x pitch 384, out pitch 448 SASPA_FF_WS={ws}")
+
+
+AS_M = 48897                    # 191 blocks of 256 rows + one row: the smallest size the A-stationary kernel takes, ragged
+
+
+@functools.lru_cache(maxsize=None)
+def _as_ops(m, n, kind="normal", geglu=False):
+    return as_operands(m, n, 600 + n + (m % 7) + len(kind), kind, geglu=geglu)
+
+
+@functools.lru_cache(maxsize=None)
+def _as_case(m, n, kind="normal", **kw):
+    return as_ref(_as_ops(m, n, kind, kw.get("geglu", False)), **kw)
+
+
+def _as_launch(dev, op, *, bias=True, residual=False, ln=None, geglu=False, **kw):
+    w, b = op["w"].float(), op["b"].float()
+    if geglu:
+        w, b = W.pack_geglu(w, b)
+    lnp = None if ln is None else (op["gamma"].float().to(dev), op["beta"].float().to(dev), ln)
+    return ops.linear(op["x"].to(dev, BF), w.to(dev, BF), b.to(dev) if bias else None,
+                      residual=op["res"].to(dev, BF) if residual else None, act=ops.ACT_GEGLU if geglu else ops.ACT_NONE, ln=lnp,
+                      variant=ops.GEMM_AS, **kw)
+
+
+@pytest.mark.parametrize("form", ["plain", "bias", "residual"])
+@pytest.mark.parametrize("n", [64, 320])
+def test_gemm_as_budget(dev, n, form):
+    kw = dict(bias=form != "plain", residual=form == "residual")
+    ref, s = _as_case(AS_M, n, **kw)
+    _check(_as_launch(dev, _as_ops(AS_M, n), **kw).cpu(), ref, s, "gemm", f"A-stationary {form} {AS_M}x320x{n}")
+
+
+@pytest.mark.parametrize("kind", ["normal", "lowvar", "offset", "const"])
+def test_gemm_as_fused_layernorm_budget(dev, kind):
+    m, n = 49152, 320
+    op = _as_ops(m, n, kind)
+    ref, s = _as_case(m, n, kind, ln=1e-5)
+    _check(_as_launch(dev, op, ln=1e-5).cpu(), ref, s, "as", f"A-stationary LayerNorm {m}x320x{n} {kind}")
+    if kind == "lowvar":
+        _control(_as_launch(dev, op, ln=1e-4).cpu(), ref, s, "as", f"A-stationary LayerNorm {m}x320x{n} {kind} with ln_eps x 10")
+
+
+@pytest.mark.parametrize("n", [320, 1024])                  # 160-column and 128-column GEGLU packing
+def test_gemm_as_fused_layernorm_geglu_budget(dev, n):
+    m = 49152
+    op = _as_ops(m, n, "normal", True)
+    ref, s = _as_case(m, n, "normal", ln=1e-5, geglu=True)
+    got = _as_launch(dev, op, ln=1e-5, geglu=True).cpu()
+    assert got.shape == (m, n // 2)
+    _check(got, ref, s, "as", f"A-stationary LayerNorm + GEGLU {m}x320x{n}")
+
+
+def test_gemm_as_qkv_vt_budget(dev):
+    """Q | K row-major and V^T per sample out of one launch (n_split = 640, 12 samples of 4096 rows), budgeted separately."""
+    m, n, n_split, rpb = 49152, 960, 640, 4096
+    op = _as_ops(m, n)
+    ref, s = _as_case(m, n, "normal", bias=False, ln=1e-5)
+    out_t = torch.full((m // rpb, n - n_split, rpb), float("nan"), device=dev, dtype=BF)
+    qk = _as_launch(dev, op, bias=False, ln=1e-5, out_t=out_t, n_split=n_split, rows_per_batch=rpb)
+    assert qk.shape == (m, n_split)
+    _check(qk.cpu(), ref[:, :n_split], s[:, :n_split], "as", "Q | K | V^T: the row-major part")
+    _check(out_t.cpu(), vt_tail(ref, n_split, rpb), vt_tail(s, n_split, rpb), "as", "Q | K | V^T: the transposed tail")
+    bad = out_t.cpu().clone()
+    bad[:-1, :, -1] = bad[1:, :, 0]
+    _control(bad, vt_tail(ref, n_split, rpb), vt_tail(s, n_split, rpb), "as", "V^T tail with a sample boundary off by one (host-side)")

@@ -633,6 +633,32 @@ typedef struct SaspaFfBlockParams {
 int saspa_ff_block(const SaspaFfBlockParams* p, void* stream);
 int saspa_ff_block_eligible(const SaspaFfBlockParams* p);
 
+/* ---- PNG encode on the device: row filters + Huffman-only deflate (opt-in, DESIGN "PNG encode on the device") ----
+ * px: contiguous u8 [n][H][W][C], C = 3 (RGB) or 1 (grey).  Per image a complete ZLIB STREAM of the PNG-filtered rows is written to
+ * streams + i * capacity and its length to sizes[i]: 78 01, deflate blocks, big-endian Adler-32 of the filtered bytes.  The host only
+ * frames it (IHDR, one IDAT with its CRC-32, IEND).
+ *   rowbytes = 1 + W * C (filter type byte + residuals); an image is cut into segments of R = SASPA_PNG_SEG_ROWS(rowbytes) rows (the last
+ *   one may be shorter), one workgroup each, <= 32767 bytes.  Per row the filter (None, Sub, Up, Average, Paeth; bpp = C, zeros above row
+ *   0) with the smallest sum |int8(residual)| is kept, ties to the lowest type; the row above a segment comes from the raw image.
+ *   Per segment ONE dynamic-Huffman block of literals only (no match search): 286 literal/length code lengths sent as 4-bit codes of a
+ *   flat code-length alphabet (header of 1222 bits), lengths from the integer construction of DESIGN.md, canonical codes.  A segment that
+ *   is not the last ends with an empty stored block (000, pad, 00 00 FF FF) so that every segment starts on a byte; a segment whose
+ *   Huffman form would take >= segbytes + 5 bytes is one stored block of exactly segbytes + 5.  Hence
+ *       capacity(H, W, C) = 2 + H * rowbytes + 5 * ceil(H / R) + 4            (saspa_png_capacity; never exceeded)
+ *   A second launch moves the segments to the front of the slot, folds the segments' Adler partial sums and writes sizes[i].
+ * Deterministic: an image's bytes depend on its pixels alone (integer arithmetic; the atomics are integer adds / ors whose result does
+ * not depend on their order), for every batch size and position in the batch.  Nothing outside [i * capacity, i * capacity + the slot's
+ * capacity) is written.
+ * saspa_png_capacity / saspa_png_workspace launch nothing: bytes per slot / of `workspace`, or a SASPA_E* code.
+ * Host-side validation, before any launch: null px / streams / sizes / workspace, n, H, W < 1 -> SASPA_EINVAL; workspace not 16-byte or
+ * sizes not 4-byte aligned -> SASPA_EALIGN; C not 1 or 3, rowbytes > 32767, capacity / workspace_bytes smaller than the two functions
+ * say, a slot of 2 GiB or more -> SASPA_ERANGE. */
+#define SASPA_PNG_SEG_ROWS(rowbytes) (32767 / (rowbytes) < 1 ? 1 : (32767 / (rowbytes) > 16 ? 16 : 32767 / (rowbytes)))
+long long saspa_png_capacity(int H, int W, int C);
+long long saspa_png_workspace(int n, int H, int W, int C);
+int saspa_png_deflate(const uint8_t* px, int n, int H, int W, int C, uint8_t* streams, long long capacity, int* sizes,
+                      void* workspace, long long workspace_bytes, void* stream);
+
 int saspa_abi_version(void);
 const char* saspa_build_arch(void);
 

@@ -165,6 +165,9 @@ SYMBOLS = {
     "saspa_groupnorm_quant_mxfp8": (_I, [C.POINTER(GroupNormParams), _P, _I, _P, _I, _P]),
     "saspa_conv3x3_mxfp8_eligible": (_I, [C.POINTER(ConvMxParams)]),
     "saspa_conv3x3_mxfp8": (_I, [C.POINTER(ConvMxParams), _P]),
+    "saspa_png_capacity": (_LL, [_I, _I, _I]),
+    "saspa_png_workspace": (_LL, [_I, _I, _I, _I]),
+    "saspa_png_deflate": (_I, [_P, _I, _I, _I, _I, _P, _LL, _P, _P, _LL, _P]),
     "saspa_abi_version": (_I, []),
     "saspa_build_arch": (C.c_char_p, []),
 }

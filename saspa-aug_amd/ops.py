@@ -49,7 +49,8 @@ def _launch(kind, flops, call, meta=None):
 
 # library entry points that launch nothing (host-side queries), and the clock probe (a sleeping wave used as a gate / clock
 # sample, not work of the path): never recorded
-_HOST_ONLY = ("eligible", "suggest", "ksplit", "which", "as_auto", "abi_version", "build_arch", "clock_probe")
+_HOST_ONLY = ("eligible", "suggest", "ksplit", "which", "as_auto", "abi_version", "build_arch", "clock_probe",
+              "capacity", "workspace")
 
 
 class _RecordingLib:
@@ -1158,6 +1159,27 @@ def u8_luma(img_u8):
     out = torch.empty_like(img_u8)
     _lib.check(_L().saspa_u8_luma(_ptr(img_u8), _ptr(out), img_u8.numel() // 3, _stream()), "saspa_u8_luma")
     return out
+
+
+def png_deflate(images_u8):
+    """Device u8 [n, H, W, C] (C = 3 or 1; [n, H, W] counts as C = 1) -> (streams u8 [n, capacity], sizes int32 [n]): per image the zlib
+    stream of its PNG-filtered rows in streams[i, :sizes[i]] (saspa_png_deflate: adaptive row filters + Huffman-only deflate; pngenc.frame
+    turns it into the file).  Stream-ordered, nothing here waits for the GPU; the bytes past sizes[i] are unspecified."""
+    _check_dev(images_u8)
+    if images_u8.dim() == 3:
+        images_u8 = images_u8[..., None]
+    if images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or not images_u8.is_contiguous() or images_u8.numel() == 0:
+        raise ValueError("png_deflate expects a contiguous, non-empty u8 [n, H, W, C] tensor")
+    n, h, w, c = images_u8.shape
+    lib = _L()
+    cap, work = int(lib.saspa_png_capacity(h, w, c)), int(lib.saspa_png_workspace(n, h, w, c))
+    _lib.check(min(cap, work, 0), f"saspa_png_capacity / saspa_png_workspace({n}, {h}, {w}, {c})")
+    streams = torch.empty((n, cap), device=images_u8.device, dtype=torch.uint8)
+    sizes = torch.empty((n,), device=images_u8.device, dtype=torch.int32)
+    workspace = torch.empty((work,), device=images_u8.device, dtype=torch.uint8)
+    _lib.check(lib.saspa_png_deflate(_ptr(images_u8), n, h, w, c, _ptr(streams), cap, _ptr(sizes), _ptr(workspace), work, _stream()),
+               "saspa_png_deflate")
+    return streams, sizes
 
 
 def embed_tokens(ids, tok, pos, npos):

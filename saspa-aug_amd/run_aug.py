@@ -68,6 +68,7 @@ class _PngWriters:
         n = int(os.environ.get("SASPA_PNG_PROCS", workers))
         self.procs, self.queues, self.feeders, self.next = [], [], [], 0
         self.threads, self.pending = None, []
+        self.framers, self.framed = None, []         # submit_encoded: streams the device already compressed (PNG_DEVICE)
         self.submitted, self.max_depth = 0, 0        # images handed over / deepest backlog seen at a submit (diagnostics)
         if n <= 0:
             self.threads = ThreadPoolExecutor(max_workers=workers)
@@ -107,7 +108,21 @@ class _PngWriters:
         self.submitted += 1
         self.max_depth = max(self.max_depth, sum(q.qsize() for q in self.queues))
 
+    def submit_encoded(self, zbytes, h, w, c, path):
+        """A file whose zlib stream comes from the device (ops.png_deflate): only the framing -- CRC-32 and the write, both of
+        which release the GIL -- is left, on a small thread pool of this process; no encoder child sees it."""
+        from . import pngenc
+        if self.framers is None:
+            self.framers = ThreadPoolExecutor(max_workers=2)
+        self.framed.append(self.framers.submit(pngenc.write, zbytes, int(h), int(w), int(c), str(path)))
+        self.submitted += 1
+        self.max_depth = max(self.max_depth, sum(q.qsize() for q in self.queues) + sum(not f.done() for f in self.framed[-64:]))
+
     def close(self):
+        if self.framers is not None:
+            for f in self.framed:
+                f.result()
+            self.framers.shutdown()
         if self.threads is not None:
             for f in self.pending:
                 f.result()
@@ -162,6 +177,7 @@ class Settings:
     WEIGHTS_DIR: str = None            # local diffusers-format checkpoints; None -> synthetic weights
     PROMPTS_FILE: str = None
     DATASET_KWARGS: dict = field(default_factory=dict)
+    PNG_DEVICE: bool = False           # generated and source images are filtered + deflated on the device (ops.png_deflate); off: Pillow
     MAX_BATCHES: int = 0               # > 0: stop this rank after that many batches (rehearsals / diagnostics; the rest stays status 0)
 
 
@@ -613,6 +629,19 @@ def make_hed_detector(s: Settings, device):
     return HEDdetector(W.synth_state_dict("hed", HED, 7), HED, device)
 
 
+class _EncodedBatch:
+    """What `finish` returns in place of a pixel array when PNG_DEVICE is on: the batch's zlib streams on the host."""
+
+    def __init__(self, streams, sizes, shape):
+        self.streams, self.sizes, self.shape = streams, sizes, tuple(int(v) for v in shape)      # shape: (h, w, c) of every image
+
+    def __len__(self):
+        return len(self.sizes)
+
+    def stream(self, k):
+        return self.streams[k, :int(self.sizes[k])].tobytes()
+
+
 def hip_batch_generator(pipe, s: Settings):
     """Returns fn(batch_items, noises[list of [1,4,h,w]], source_u8 [B,H,W,3]) -> (images u8
     [B,H,W,3] numpy, control u8 [B,H,W,3] numpy), running Canny + sampling on the device."""
@@ -672,19 +701,40 @@ def hip_batch_generator(pipe, s: Settings):
             ids = np.concatenate([tok(it.prompt) for it in batch])
             out = pipe.generate_batch(ids, neg_ids, ctrl, lat, s.NUM_INFERENCE_STEPS, s.GUIDANCE_SCALE,
                                       s.CONTROLNET_CONDITIONING_SCALE)
+        # PNG_DEVICE: the two sets of files every batch writes are compressed right behind the generation, on the same stream
+        enc = (ops.png_deflate(out), ops.png_deflate(src)) if s.PNG_DEVICE else None
         ev = torch.cuda.Event()
         ev.record()
-        return out, ctrl, ev, src, subs
+        return out, ctrl, ev, src, subs, enc
 
     def finish(handle):
         """Device -> host copies of a batch enqueued earlier, on a side stream that waits for THAT batch only: the next
         batch's launch sequence may already be queued behind it on the main stream and keeps the GPU busy meanwhile.
         -> (images, controls, resized sources, resized subjects | None)."""
-        out, ctrl, ev, src, subs = handle
+        out, ctrl, ev, src, subs, enc = handle
         side.wait_event(ev)
         with torch.cuda.stream(side):
-            for t in (out, src) + ((ctrl,) if ctrl is not None else ()) + tuple(subs or ()):
+            for t in (out, src) + ((ctrl,) if ctrl is not None else ()) + tuple(subs or ()) + tuple(t for e in enc or () for t in e):
                 t.record_stream(side)
+            if enc is not None:
+                # streams and sizes instead of the pixels of `out` / `src`; the control maps and subjects stay pixels (Pillow writers)
+                if os.environ.get("SASPA_HOST_BLOCKING", "1") == "0":
+                    host = [t.cpu() for e in enc for t in e]
+                    c = ctrl.cpu() if ctrl is not None else None
+                    sb = [t.cpu() for t in subs] if subs is not None else None
+                else:
+                    def d2h(t):
+                        h = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+                        h.copy_(t, non_blocking=True)
+                        return h
+                    host = [d2h(t) for e in enc for t in e]
+                    c = d2h(ctrl) if ctrl is not None else None
+                    sb = [d2h(t) for t in subs] if subs is not None else None
+                    done = torch.cuda.Event()
+                    done.record()
+                    ops.sleep_wait(done, 0.002)
+                return (_EncodedBatch(host[0].numpy(), host[1].numpy(), out.shape[1:]), (c.numpy() if c is not None else None),
+                        _EncodedBatch(host[2].numpy(), host[3].numpy(), src.shape[1:]), ([t.numpy() for t in sb] if sb is not None else None))
             if os.environ.get("SASPA_HOST_BLOCKING", "1") == "0":
                 o, sr = out.cpu(), src.cpu()                    # (a synchronous copy spins on the calling thread until the batch is done)
                 c = ctrl.cpu() if ctrl is not None else None
@@ -880,16 +930,22 @@ def _main(s: Settings, ds_utils=None, batch_generator=None, dist=None, pipe=None
         batch_log.append((batch[0].height, batch[0].width, len(batch), _time.time()))
         return True
 
+    def write(arrs, k, path):
+        if isinstance(arrs, _EncodedBatch):                  # PNG_DEVICE: already compressed on the device
+            png.submit_encoded(arrs.stream(k), *arrs.shape, path)
+        else:
+            png.submit(arrs[k], path)
+
     def emit(batch, images, controls, sources, subjects):
         for k, it in enumerate(batch):
             stem40 = it.image_stem[:MAX_FILENAME_LENGTH]
             if first_variant[it.index] == it.order:
-                png.submit(sources[k], os.path.join(output_folder, f"{stem40}_source.png"))
+                write(sources, k, os.path.join(output_folder, f"{stem40}_source.png"))
                 if it.index < 10 and controls is not None:       # :441-442 sits inside `if CONTROLNET:`
                     png.submit(controls[k], f"{output_folder}/{stem40}_control.png")
             if subjects is not None and it.subject_path:     # :453-454 "_subject_{i}.png" (excluded from the JSON by name)
                 png.submit(subjects[k], os.path.join(output_folder, f"{stem40}_subject_{it.i}.png"))
-            png.submit(images[k], it.output_path)
+            write(images, k, it.output_path)
             it.status = 1
 
     import time as _time

@@ -37,6 +37,12 @@ extern "C" {
  * product instead of 2^-24, at several times the rate of the fp32 MFMA.  For the fp32-upcast SDXL VAE
  * (run_aug/run_aug.py:224 `pipe.upcast_vae()`), whose range -- not its last 7 bits -- is why the reference leaves fp16. */
 #define SASPA_F32X3 2
+/* IEEE fp16 storage and MFMA operands (fp32 accumulation): the compute type of libsaspa_hip_f16.so, a second build of the 16-bit kernels
+ * (GEMM / conv, attention, norms, elementwise, the fused transformer-block launches) with the element type swapped -- same entry points,
+ * layouts and schedules; wherever this header says "bf16" of those, read "the library's 16-bit type" (saspa_half_type).  The reference
+ * runs its pipelines in fp16 (run_aug/run_aug.py:323).  That library accepts ONLY this code (SASPA_BF16 / SASPA_F32 / SASPA_F32X3 ->
+ * SASPA_EINVAL); libsaspa_hip.so refuses it the same way.  Stores do not clamp: beyond 65504 the result is inf, as in the reference. */
+#define SASPA_F16 3
 
 #define SASPA_EINVAL (-1) /* null pointer / non-positive size */
 #define SASPA_EALIGN (-2) /* channel count, pitch or pointer not 16-byte compatible */
@@ -660,6 +666,8 @@ int saspa_png_deflate(const uint8_t* px, int n, int H, int W, int C, uint8_t* st
                       void* workspace, long long workspace_bytes, void* stream);
 
 int saspa_abi_version(void);
+/* the dtype code of the library's 16-bit element type: SASPA_BF16 (libsaspa_hip.so) or SASPA_F16 (libsaspa_hip_f16.so) */
+int saspa_half_type(void);
 const char* saspa_build_arch(void);
 
 #ifdef __cplusplus

@@ -9,7 +9,7 @@ model-confidence filters.  Same launch forms as run_aug/run_aug.py:
 
 and the same environment overlays: SASPA_DATASET, SASPA_WEIGHTS_DIR, SASPA_PROMPTS_FILE, SASPA_NUM_INFERENCE_STEPS,
 SASPA_NUM_PER_IMAGE, SASPA_PRECISION, SASPA_BASE_MODEL, SASPA_LPIPS_MIN / SASPA_LPIPS_MAX, SASPA_CLIP_FILTERING (default
-"per_class"; "none" switches the filter off), SASPA_CLIP_FILTERING_DISCOUNT and SASPA_PNG_DEVICE.  The output folder carries the step count and
+"per_class"; "none" switches the filter off), SASPA_CLIP_FILTERING_DISCOUNT, SASPA_PNG_DEVICE and SASPA_FP16 / SASPA_FP16_VAE.  The output folder carries the step count and
 guidance scale after the seed (`..._seed_1_num_inf_steps_50_gs_7.5/images`), as the reference's script names it."""
 import os
 import sys
@@ -49,7 +49,8 @@ def real_guidance_settings(env=None):
         # ---------------------------- this build ----------------------------
         FOLDER_STEPS_GS_SUFFIX=True, BATCH_SIZE=8, PRECISION=env.get("SASPA_PRECISION", "bf16"),
         WEIGHTS_DIR=env.get("SASPA_WEIGHTS_DIR"), PROMPTS_FILE=env.get("SASPA_PROMPTS_FILE"),
-        PNG_DEVICE=env.get("SASPA_PNG_DEVICE", "0") == "1")
+        PNG_DEVICE=env.get("SASPA_PNG_DEVICE", "0") == "1",
+        FP16=env.get("SASPA_FP16", "0") == "1", FP16_VAE=env.get("SASPA_FP16_VAE", "bf16"))
 
 
 if __name__ == "__main__":

@@ -5,8 +5,11 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SASPA_HIP_LIB: load another build of the same ABI (the `make ABLATION=1` diagnostics library of tools/pp_clock.py ...)
 LIB_PATH = os.environ.get("SASPA_HIP_LIB") or os.path.join(_HERE, "libsaspa_hip.so")
+# the fp16 build of the 16-bit kernels (csrc/Makefile, -DSASPA_HALF_F16): opened only when an fp16 tensor reaches ops
+F16_LIB_PATH = os.path.join(_HERE, "libsaspa_hip_f16.so")
 
 SASPA_BF16, SASPA_F32, SASPA_F32X3 = 0, 1, 2
+SASPA_F16 = 3                                              # libsaspa_hip_f16.so only
 SASPA_EINVAL, SASPA_EALIGN, SASPA_ERANGE = -1, -2, -3      # include/saspa_hip.h
 LPIPS_MAX_C, LPIPS_MAX_BLOCKS = 512, 64                    # SASPA_LPIPS_MAX_C / SASPA_LPIPS_MAX_BLOCKS
 CLASS_HEAD_MAX_D, CLASS_HEAD_MAX_C = 2048, 4096            # SASPA_CLASS_HEAD_MAX_D / SASPA_CLASS_HEAD_MAX_C
@@ -169,10 +172,25 @@ SYMBOLS = {
     "saspa_png_workspace": (_LL, [_I, _I, _I, _I]),
     "saspa_png_deflate": (_I, [_P, _I, _I, _I, _I, _P, _LL, _P, _P, _LL, _P]),
     "saspa_abi_version": (_I, []),
+    "saspa_half_type": (_I, []),
     "saspa_build_arch": (C.c_char_p, []),
 }
 
+# what libsaspa_hip_f16.so exports: the entry points of the translation units the fp16 mode needs (GEMM / conv, attention, norms,
+# elementwise and scheduler steps, the fused transformer-block launches); fp8 / MX / halo convs, Canny, image, filter, resize, HED and
+# PNG exist in the default library only
+F16_SYMBOL_NAMES = (
+    "saspa_gemm", "saspa_gemm_suggest_ksplit", "saspa_gemm_as_eligible", "saspa_gemm_as_auto", "saspa_gemm_which",
+    "saspa_ff_block", "saspa_ff_block_eligible", "saspa_xattn_block", "saspa_flash_attn_bf16", "saspa_softmax_rows",
+    "saspa_groupnorm_stats", "saspa_groupnorm_apply", "saspa_groupnorm_onepass_eligible", "saspa_groupnorm_onepass",
+    "saspa_splitk_groupnorm_eligible", "saspa_splitk_groupnorm", "saspa_layernorm", "saspa_geglu", "saspa_activation",
+    "saspa_embed_tokens", "saspa_embed_tokens_ctx", "saspa_cfg_plms_step", "saspa_cfg_plms_step_dev", "saspa_cfg_ddim_step",
+    "saspa_ddim_step", "saspa_ddim_step_dev", "saspa_cfg_unipc_step", "saspa_unipc_step", "saspa_vae_sample_noise", "saspa_scale",
+    "saspa_u8_to_act", "saspa_act_to_u8", "saspa_abi_version", "saspa_half_type", "saspa_build_arch",
+)
+
 _lib = None
+_lib_f16 = None
 
 
 def load():
@@ -200,6 +218,31 @@ def load():
         fn.argtypes = args
     _lib = lib
     return lib
+
+
+def load_f16():
+    """Load the fp16 library (lazily: nothing of it is opened before an fp16 tensor reaches ops); raises, never falls back."""
+    global _lib_f16
+    if _lib_f16 is not None:
+        return _lib_f16
+    if not os.path.exists(F16_LIB_PATH):
+        raise RuntimeError(
+            f"{F16_LIB_PATH} not found: the fp16 build of the gfx950 kernels is missing. Run `make -C saspa-aug_amd/csrc` "
+            "(or __graft_entry__.build()). fp16 tensors are never routed to the bf16 library.")
+    import torch  # noqa: F401      (torch FIRST, as in load(): the library must bind to the HIP runtime torch ships)
+    lib = C.CDLL(F16_LIB_PATH)
+    for name in F16_SYMBOL_NAMES:
+        fn = getattr(lib, name)  # AttributeError if the .so does not export a symbol of its subset
+        fn.restype, fn.argtypes = SYMBOLS[name]
+    if lib.saspa_abi_version() != load().saspa_abi_version() or lib.saspa_half_type() != SASPA_F16:
+        raise RuntimeError(f"{F16_LIB_PATH}: ABI {lib.saspa_abi_version()} / 16-bit type {lib.saspa_half_type()} is not the fp16 "
+                           "build of this tree's kernels; rebuild")
+    _lib_f16 = lib
+    return lib
+
+
+def f16_loaded():
+    return _lib_f16 is not None
 
 
 def check(code, what):

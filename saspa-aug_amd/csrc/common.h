@@ -5,12 +5,33 @@
 
 #include "saspa_hip.h"
 
-typedef __bf16 bf16_t;
+// The 16-bit element type of this build.  The default library computes in bf16; the same sources compiled with
+// -DSASPA_HALF_F16 give libsaspa_hip_f16.so, whose 16-bit type is IEEE fp16 (v_mfma_*_f16, v_cvt_pk_f16_f32, v_dot2_f32_f16).  The
+// kernels only move 16-bit words (buffer loads to LDS, ds_read_b64_tr_b16, swizzles); what the bits MEAN is confined to the
+// helpers below: h16_t / Elem<h16_t>, pack2 / unpack2 / h16_bits_to_f32, kHalfOnes2, half_dot2 and the two MFMA wrappers.
+// fp16 stores do not clamp: a value beyond 65504 becomes inf, as it does in the fp16 arithmetic this mode reproduces.
+#ifdef SASPA_HALF_F16
+typedef _Float16 h16_t;
+#define SASPA_HALF SASPA_F16
+constexpr bool kServesF32 = false;      // SASPA_F32 / SASPA_F32X3 (and SASPA_BF16) are refused on the host: the default library serves them
+constexpr uint32_t kHalfOnes2 = 0x3C003C00u;   // the pair (1.0, 1.0)
+#else
+typedef __bf16 h16_t;
+typedef __bf16 bf16_t;                  // the translation units that exist in the default library only (fp8, MX, halo, filters)
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+#define SASPA_HALF SASPA_BF16
+constexpr bool kServesF32 = true;
+constexpr uint32_t kHalfOnes2 = 0x3F803F80u;
+#endif
+constexpr uint32_t kHalfOne = kHalfOnes2 & 0xffffu;   // 1.0 in the low element of a dword, zero above it
+typedef h16_t h16x8 __attribute__((ext_vector_type(8)));
+typedef h16_t h16x2_t __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2_t __attribute__((ext_vector_type(2)));
 
 #define SASPA_CHECK_LAUNCH()                      \
   do {                                            \
@@ -18,26 +39,46 @@ typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
     if (e__ != hipSuccess) return (int)e__;       \
   } while (0)
 
-__device__ __forceinline__ float bf16_bits_to_f32(uint32_t hi16) { return __builtin_bit_cast(float, hi16 << 16); }
-
-// unpack 8 bf16 (one 16-byte chunk) to fp32
-__device__ __forceinline__ void unpack8(const uint4& u, float* f) {
-  f[0] = __builtin_bit_cast(float, u.x << 16);
-  f[1] = __builtin_bit_cast(float, u.x & 0xffff0000u);
-  f[2] = __builtin_bit_cast(float, u.y << 16);
-  f[3] = __builtin_bit_cast(float, u.y & 0xffff0000u);
-  f[4] = __builtin_bit_cast(float, u.z << 16);
-  f[5] = __builtin_bit_cast(float, u.z & 0xffff0000u);
-  f[6] = __builtin_bit_cast(float, u.w << 16);
-  f[7] = __builtin_bit_cast(float, u.w & 0xffff0000u);
+// one 16-bit element given in the LOW half of `bits` (high half ignored) -> fp32
+__device__ __forceinline__ float h16_bits_to_f32(uint32_t bits) {
+#ifdef SASPA_HALF_F16
+  return (float)__builtin_bit_cast(_Float16, (unsigned short)bits);
+#else
+  return __builtin_bit_cast(float, bits << 16);
+#endif
+}
+// the two elements of one dword -> fp32 (bf16: a shift and a mask; fp16 has no such trick: two v_cvt_f32_f16)
+__device__ __forceinline__ void unpack2(uint32_t w, float& lo, float& hi) {
+#ifdef SASPA_HALF_F16
+  const h16x2_t v = __builtin_bit_cast(h16x2_t, w);
+  lo = (float)v[0];
+  hi = (float)v[1];
+#else
+  lo = __builtin_bit_cast(float, w << 16);
+  hi = __builtin_bit_cast(float, w & 0xffff0000u);
+#endif
 }
 
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
+// unpack 8 elements (one 16-byte chunk) to fp32
+__device__ __forceinline__ void unpack8(const uint4& u, float* f) {
+  unpack2(u.x, f[0], f[1]);
+  unpack2(u.y, f[2], f[3]);
+  unpack2(u.z, f[4], f[5]);
+  unpack2(u.w, f[6], f[7]);
+}
+
 __device__ __forceinline__ uint32_t pack2(float lo, float hi) {
-  // one v_cvt_pk_bf16_f32 (RNE, NaN-preserving); the scalar-cast form costs 2 cvt + an sdwa or
+  // one v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32 (RNE, NaN-preserving); the scalar-cast form costs 2 cvt + an sdwa or
   const f32x2_t v = {lo, hi};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, h16x2_t));
+}
+// x rounded to the 16-bit type, as fp32
+__device__ __forceinline__ float round_h16(float x) {
+#ifdef SASPA_HALF_F16
+  return (float)(_Float16)x;
+#else
+  return __builtin_bit_cast(float, pack2(0.f, x) & 0xffff0000u);
+#endif
 }
 
 __device__ __forceinline__ uint4 pack8(const float* f) {
@@ -49,32 +90,50 @@ __device__ __forceinline__ uint4 pack8(const float* f) {
   return u;
 }
 
+// acc + a.lo * b.lo + a.hi * b.hi on two packed pairs: v_dot2c_f32_bf16 / v_dot2_f32_f16 (products and sum in fp32)
+__device__ __forceinline__ float half_dot2(uint32_t a, uint32_t b, float acc) {
+#ifdef SASPA_HALF_F16
+  return __builtin_amdgcn_fdot2(__builtin_bit_cast(h16x2_t, a), __builtin_bit_cast(h16x2_t, b), acc, false);
+#else
+  return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(h16x2_t, a), __builtin_bit_cast(h16x2_t, b), acc, false);
+#endif
+}
+
+// the two MFMAs of the 16-bit kernels; operands are 16-byte fragments of 8 elements (u32x4), same shapes, C / D and operand lane maps
+// in both element types.  Macros, not inline functions: passed through a function, a C operand such as `s == 0 ? zero : acc` no
+// longer folds into the instruction's inline constant and the attention kernels come out with other register assignments.
+#ifdef SASPA_HALF_F16
+#define MFMA_16X16X32(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h16x8, a), __builtin_bit_cast(h16x8, b), c, 0, 0, 0)
+#define MFMA_32X32X16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h16x8, a), __builtin_bit_cast(h16x8, b), c, 0, 0, 0)
+#else
+#define MFMA_16X16X32(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(h16x8, a), __builtin_bit_cast(h16x8, b), c, 0, 0, 0)
+#define MFMA_32X32X16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(h16x8, a), __builtin_bit_cast(h16x8, b), c, 0, 0, 0)
+#endif
+
 // ---- dtype-generic "vector of V contiguous elements" load/store as fp32 ----
 template <typename T> struct Elem;
-template <> struct Elem<bf16_t> {
+template <> struct Elem<h16_t> {
   static constexpr int EPC = 8;  // elements per 16-byte chunk
-  __device__ static __forceinline__ void load_chunk(const bf16_t* p, float* f) {
+  __device__ static __forceinline__ void load_chunk(const h16_t* p, float* f) {
     uint4 u = *reinterpret_cast<const uint4*>(p);
     unpack8(u, f);
   }
-  __device__ static __forceinline__ void store_chunk(bf16_t* p, const float* f) {
+  __device__ static __forceinline__ void store_chunk(h16_t* p, const float* f) {
     *reinterpret_cast<uint4*>(p) = pack8(f);
   }
-  __device__ static __forceinline__ void load4(const bf16_t* p, float* f) {
+  __device__ static __forceinline__ void load4(const h16_t* p, float* f) {
     uint2 u = *reinterpret_cast<const uint2*>(p);
-    f[0] = __builtin_bit_cast(float, u.x << 16);
-    f[1] = __builtin_bit_cast(float, u.x & 0xffff0000u);
-    f[2] = __builtin_bit_cast(float, u.y << 16);
-    f[3] = __builtin_bit_cast(float, u.y & 0xffff0000u);
+    unpack2(u.x, f[0], f[1]);
+    unpack2(u.y, f[2], f[3]);
   }
-  __device__ static __forceinline__ void store4(bf16_t* p, const float* f) {
+  __device__ static __forceinline__ void store4(h16_t* p, const float* f) {
     uint2 u;
     u.x = pack2(f[0], f[1]);
     u.y = pack2(f[2], f[3]);
     *reinterpret_cast<uint2*>(p) = u;
   }
-  __device__ static __forceinline__ float load1(const bf16_t* p) { return (float)*p; }
-  __device__ static __forceinline__ void store1(bf16_t* p, float f) { *p = (bf16_t)f; }
+  __device__ static __forceinline__ float load1(const h16_t* p) { return (float)*p; }
+  __device__ static __forceinline__ void store1(h16_t* p, float f) { *p = (h16_t)f; }
 };
 template <> struct Elem<float> {
   static constexpr int EPC = 4;
@@ -186,12 +245,12 @@ __device__ __forceinline__ void lds_barrier() {
   __builtin_amdgcn_s_barrier();
 }
 
-// GroupNorm statistics of one block of <= 128 finished output rows held in LDS as bf16 (`ct`: rows of `cp` elements, the
+// GroupNorm statistics of one block of <= 128 finished output rows held in LDS in the 16-bit type (`ct`: rows of `cp` elements, the
 // STORED values): per unit of `unit` consecutive channels (nunits of them, nunits divides NT) the sum and the sum of squares
 // over rows [0, nrows) -> dst[nunits][2].  Fixed summation order (thread (unit, row group) over its interleaved rows, then
 // one thread per value over the row groups): deterministic.  scratch: 2 * NT floats of LDS; ends with the caller's barrier.
 template <int NT>
-__device__ __forceinline__ void gn_tile_stats(const bf16_t* ct, const int cp, const int nrows, const int nunits, const int unit,
+__device__ __forceinline__ void gn_tile_stats(const h16_t* ct, const int cp, const int nrows, const int nunits, const int unit,
                                               float* scratch, float* dst) {
   const int tid = threadIdx.x;
   const int rgs = NT / nunits;
@@ -201,10 +260,10 @@ __device__ __forceinline__ void gn_tile_stats(const bf16_t* ct, const int cp, co
     for (int r = rg; r < nrows; r += rgs) {
       const uint32_t* src = reinterpret_cast<const uint32_t*>(ct + r * cp + u * unit);
       for (int j = 0; j < unit; j += 2) {
-        // two bf16 per dword: v_dot2c_f32_bf16 against (1, 1) and against itself -- 2 VALU per pair instead of 6
-        const bf16x2_t w = __builtin_bit_cast(bf16x2_t, src[j >> 1]);
-        sm = __builtin_amdgcn_fdot2_f32_bf16(w, __builtin_bit_cast(bf16x2_t, 0x3F803F80u), sm, false);
-        sq = __builtin_amdgcn_fdot2_f32_bf16(w, w, sq, false);
+        // two elements per dword: one dot2 against (1, 1) and one against itself -- 2 VALU per pair instead of 6
+        const uint32_t w = src[j >> 1];
+        sm = half_dot2(w, kHalfOnes2, sm);
+        sq = half_dot2(w, w, sq);
       }
     }
     scratch[(rg * nunits + u) * 2] = sm;
@@ -219,4 +278,6 @@ __device__ __forceinline__ void gn_tile_stats(const bf16_t* ct, const int cp, co
   }
 }
 
+// the dtype codes this build's entry points accept (everything else: SASPA_EINVAL before any launch)
+static inline bool dtype_served(int dt) { return dt == SASPA_HALF || (kServesF32 && (dt == SASPA_F32 || dt == SASPA_F32X3)); }
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }

@@ -22,6 +22,16 @@
 
 namespace {
 
+// Headroom of the reference level in the prescaled loops (v2 .. v4 below): after a level update p <= 2^-BIAS.  bf16 has fp32's
+// exponent range, so p ~ 2^-8 costs no precision and updates are rare.  fp16's normal range ends at 2^-14 and it has nothing below
+// 2^-24: the level sits AT the last maximum there (p <= 1 after an update, < 2 between updates -- far from 65504), which keeps every
+// weight within 2^-14 of the largest one at full precision, as the running-maximum loop (v1) does.  More updates, same arithmetic.
+#ifdef SASPA_HALF_F16
+constexpr float kLevelBias = 0.0f;
+#else
+constexpr float kLevelBias = 8.0f;
+#endif
+
 // ---- V ROW-MAJOR (SASPA_ATTN_V_ROWMAJOR, ABI 14) ------------------------------------------------------------------
 // The PV product wants, per lane, 8 consecutive keys of ONE channel (the A operand of O^T += V^T P^T) -- which is why V was
 // only ever materialised transposed, by a separate projection launch.  gfx950's ds_read_b64_tr_b16 delivers exactly that
@@ -79,11 +89,11 @@ __global__ __launch_bounds__(256) void flash_attn_kernel(const SaspaAttnParams p
   const int q0 = xq * 128 + wave * 32;
   const int qi = q0 + r;  // this lane's query
 
-  const bf16_t* Q = reinterpret_cast<const bf16_t*>(p.q) + b * p.sqb + head * D;
-  const bf16_t* Kp = reinterpret_cast<const bf16_t*>(p.k) + b * p.skb + head * D;
-  const bf16_t* VT = RM ? reinterpret_cast<const bf16_t*>(p.vt) + b * p.svb + head * D          // V[b][key][head*D + d]
-                        : reinterpret_cast<const bf16_t*>(p.vt) + b * p.svb + (long long)head * D * p.ldvt;
-  bf16_t* O = reinterpret_cast<bf16_t*>(p.o) + b * p.sob + head * D;
+  const h16_t* Q = reinterpret_cast<const h16_t*>(p.q) + b * p.sqb + head * D;
+  const h16_t* Kp = reinterpret_cast<const h16_t*>(p.k) + b * p.skb + head * D;
+  const h16_t* VT = RM ? reinterpret_cast<const h16_t*>(p.vt) + b * p.svb + head * D          // V[b][key][head*D + d]
+                        : reinterpret_cast<const h16_t*>(p.vt) + b * p.svb + (long long)head * D * p.ldvt;
+  h16_t* O = reinterpret_cast<h16_t*>(p.o) + b * p.sob + head * D;
 
   const u32x4 zero4 = {0u, 0u, 0u, 0u};
 
@@ -97,8 +107,8 @@ __global__ __launch_bounds__(256) void flash_attn_kernel(const SaspaAttnParams p
 
   // ---- staging: bounds-checked buffer loads (an offset >= num_records returns zeros), per-lane
   //      offsets fixed for the whole kernel, the tile advance in a scalar offset ----
-  const __amdgpu_buffer_rsrc_t rsk = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(Kp), (short)0, 0x7fffffff, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsv = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(VT), (short)0, 0x7fffffff, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsk = __builtin_amdgcn_make_buffer_rsrc(const_cast<h16_t*>(Kp), (short)0, 0x7fffffff, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsv = __builtin_amdgcn_make_buffer_rsrc(const_cast<h16_t*>(VT), (short)0, 0x7fffffff, 0x00020000);
   constexpr unsigned kInv = 0x80000000u;
   unsigned koff[NCH_K], voff[NCH_V];
   int k_key[NCH_K], k_lds[NCH_K], v_lds[NCH_V], v_d[NCH_V], v_kc[NCH_V];
@@ -124,7 +134,7 @@ __global__ __launch_bounds__(256) void flash_attn_kernel(const SaspaAttnParams p
     }
     for (int q = tid; q < KT * DCH; q += 256) {
       const int key = q / DCH, ch = q - key * DCH;
-      if (ch >= D8) *reinterpret_cast<u32x4*>(vsm + key * RROW + ch * 16) = u32x4{(ONES && ch == D8) ? 0x00003F80u : 0u, 0u, 0u, 0u};
+      if (ch >= D8) *reinterpret_cast<u32x4*>(vsm + key * RROW + ch * 16) = u32x4{(ONES && ch == D8) ? kHalfOne : 0u, 0u, 0u, 0u};
     }
   } else {
 #pragma unroll
@@ -140,7 +150,7 @@ __global__ __launch_bounds__(256) void flash_attn_kernel(const SaspaAttnParams p
   for (int q = tid; q < DV * VCH; q += 256) {
     const int d = q / VCH, kc = q - d * VCH;
     if (d >= D) {
-      const unsigned fill = (ONES && d == D) ? 0x3F803F80u : 0u;
+      const unsigned fill = (ONES && d == D) ? kHalfOnes2 : 0u;
       u32x2* dst = reinterpret_cast<u32x2*>(vsm + d * VROW + kc * 16);
       dst[0] = u32x2{fill, fill};
       dst[1] = u32x2{fill, fill};
@@ -228,8 +238,7 @@ __global__ __launch_bounds__(256) void flash_attn_kernel(const SaspaAttnParams p
 #pragma unroll
       for (int s = 0; s < KS; ++s) {
         const u32x4 kf = *reinterpret_cast<const u32x4*>(ksm + ((kb * 32 + r) * KSLOTS + 2 * s + h) * 16);
-        acc_s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kf), __builtin_bit_cast(bf16x8, qf[s]),
-                                                            s == 0 ? zero16 : acc_s[kb], 0, 0, 0);   // C = inline 0
+        acc_s[kb] = MFMA_32X32X16(kf, qf[s], s == 0 ? zero16 : acc_s[kb]);   // C = inline 0
       }
     }
     // ---- masks only on the tiles that need them (wave-uniform) ----
@@ -294,8 +303,7 @@ __global__ __launch_bounds__(256) void flash_attn_kernel(const SaspaAttnParams p
           hi = *reinterpret_cast<const u32x2*>(vrow + 16);
         }
         const u32x4 vf = {lo.x, lo.y, hi.x, hi.y};
-        acc_o[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vf),
-                                                            __builtin_bit_cast(bf16x8, pf), acc_o[nb], 0, 0, 0);
+        acc_o[nb] = MFMA_32X32X16(vf, pf, acc_o[nb]);
       }
     }
   }
@@ -324,7 +332,7 @@ __global__ __launch_bounds__(256) void flash_attn_kernel(const SaspaAttnParams p
         if (d < D) {
           float v[4] = {acc_o[nb][4 * g + 0] * inv, acc_o[nb][4 * g + 1] * inv, acc_o[nb][4 * g + 2] * inv,
                         acc_o[nb][4 * g + 3] * inv};
-          Elem<bf16_t>::store4(O + (long long)qi * p.ldo + d, v);
+          Elem<h16_t>::store4(O + (long long)qi * p.ldo + d, v);
         }
       }
   }
@@ -338,7 +346,7 @@ __global__ __launch_bounds__(256) void flash_attn_kernel(const SaspaAttnParams p
 //   * softmax is exact for ANY reference level (it cancels in O / l), it only has to keep exp2 in range.  So m is
 //     not the running maximum but "the maximum seen at the last update + BIAS": p stays <= 2^-BIAS until a logit
 //     exceeds that maximum by BIAS + 1, which the loop detects without a max chain -- p >= 2 <=> bit 14 of its
-//     bf16 pattern, so OR-ing the packed P registers (v_or3_b32, 16 per 128-key tile) and testing 0x40004000
+//     bf16 pattern (and of its fp16 pattern: both put 2.0 at 0x4000), so OR-ing the packed P registers (v_or3_b32, 16 per 128-key tile) and testing 0x40004000
 //     is an exact "some p >= 2.0" (inf / NaN included).  Only then (and on tile 0, which sets the level) the
 //     slow path takes the true row maximum, moves m, rescales O once and re-exponentiates the tile.
 //     bf16 / fp32 keep 8 exponent bits, so p ~ 2^-8 loses no relative precision; l and O are fp32.
@@ -359,7 +367,7 @@ __global__ __launch_bounds__(256) void flash_attn_v2_kernel(const SaspaAttnParam
   constexpr int BUF = K_BYTES + V_BYTES;
   constexpr int NCH_K = (KT * KCH + 255) / 256;
   constexpr int NCH_V = (DV * VCH + 255) / 256;
-  constexpr float BIAS = 8.0f;
+  constexpr float BIAS = kLevelBias;
   __shared__ __attribute__((aligned(16))) unsigned char smem[(DB ? 2 : 1) * BUF];
 
   const int tid = threadIdx.x;
@@ -376,10 +384,10 @@ __global__ __launch_bounds__(256) void flash_attn_v2_kernel(const SaspaAttnParam
   const int q0 = xq * 128 + wave * 32;
   const int qi = q0 + r;
 
-  const bf16_t* Q = reinterpret_cast<const bf16_t*>(p.q) + b * p.sqb + head * D;
-  const bf16_t* Kp = reinterpret_cast<const bf16_t*>(p.k) + b * p.skb + head * D;
-  const bf16_t* VT = reinterpret_cast<const bf16_t*>(p.vt) + b * p.svb + (long long)head * D * p.ldvt;
-  bf16_t* O = reinterpret_cast<bf16_t*>(p.o) + b * p.sob + head * D;
+  const h16_t* Q = reinterpret_cast<const h16_t*>(p.q) + b * p.sqb + head * D;
+  const h16_t* Kp = reinterpret_cast<const h16_t*>(p.k) + b * p.skb + head * D;
+  const h16_t* VT = reinterpret_cast<const h16_t*>(p.vt) + b * p.svb + (long long)head * D * p.ldvt;
+  h16_t* O = reinterpret_cast<h16_t*>(p.o) + b * p.sob + head * D;
 
   const u32x4 zero4 = {0u, 0u, 0u, 0u};
   u32x4 qf[KS];
@@ -389,8 +397,8 @@ __global__ __launch_bounds__(256) void flash_attn_v2_kernel(const SaspaAttnParam
     qf[s] = (qi < p.nq && d < D) ? *reinterpret_cast<const u32x4*>(Q + (long long)qi * p.ldq + d) : zero4;
   }
 
-  const __amdgpu_buffer_rsrc_t rsk = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(Kp), (short)0, 0x7fffffff, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsv = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(VT), (short)0, 0x7fffffff, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsk = __builtin_amdgcn_make_buffer_rsrc(const_cast<h16_t*>(Kp), (short)0, 0x7fffffff, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsv = __builtin_amdgcn_make_buffer_rsrc(const_cast<h16_t*>(VT), (short)0, 0x7fffffff, 0x00020000);
   constexpr unsigned kInv = 0x80000000u;
   unsigned koff[NCH_K], voff[NCH_V];
   int k_key[NCH_K], k_lds[NCH_K], v_lds[NCH_V], v_kc[NCH_V];
@@ -415,7 +423,7 @@ __global__ __launch_bounds__(256) void flash_attn_v2_kernel(const SaspaAttnParam
   for (int q = tid; q < DV * VCH; q += 256) {
     const int d = q / VCH, kc = q - d * VCH;
     if (d >= D) {
-      const unsigned fill = (ONES && d == D) ? 0x3F803F80u : 0u;
+      const unsigned fill = (ONES && d == D) ? kHalfOnes2 : 0u;
 #pragma unroll
       for (int bf = 0; bf < (DB ? 2 : 1); ++bf)
         *reinterpret_cast<u32x4*>(smem + bf * BUF + K_BYTES + d * VROW + kc * 16) = u32x4{fill, fill, fill, fill};
@@ -515,8 +523,7 @@ __global__ __launch_bounds__(256) void flash_attn_v2_kernel(const SaspaAttnParam
       }
 #pragma unroll
       for (int s = 0; s < KS; ++s)
-        acc_s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kf[kb & 1][s]), __builtin_bit_cast(bf16x8, qf[s]),
-                                                            s == 0 ? negm : acc_s[kb], 0, 0, 0);
+        acc_s[kb] = MFMA_32X32X16(kf[kb & 1][s], qf[s], s == 0 ? negm : acc_s[kb]);
     }
     if (key0 + KT > p.nk || p.causal) {
 #pragma unroll
@@ -579,7 +586,7 @@ __global__ __launch_bounds__(256) void flash_attn_v2_kernel(const SaspaAttnParam
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb) {
         const u32x4 vf = *reinterpret_cast<const u32x4*>(vsm + (nb * 32 + r) * VROW + ks * 32 + 16 * h);
-        acc_o[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vf), __builtin_bit_cast(bf16x8, pf), acc_o[nb], 0, 0, 0);
+        acc_o[nb] = MFMA_32X32X16(vf, pf, acc_o[nb]);
       }
     }
     if (DB) __syncthreads();      // tile t consumed by everyone; tile t+1 visible to everyone
@@ -607,7 +614,7 @@ __global__ __launch_bounds__(256) void flash_attn_v2_kernel(const SaspaAttnParam
         if (d < D) {
           float v[4] = {acc_o[nb][4 * g + 0] * inv, acc_o[nb][4 * g + 1] * inv, acc_o[nb][4 * g + 2] * inv,
                         acc_o[nb][4 * g + 3] * inv};
-          Elem<bf16_t>::store4(O + (long long)qi * p.ldo + d, v);
+          Elem<h16_t>::store4(O + (long long)qi * p.ldo + d, v);
         }
       }
   }
@@ -655,7 +662,7 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_attn_v3_kernel(const SaspaAt
   constexpr int BUF = K_BYTES + V_BYTES;
   constexpr int NCH_K = (KT * KCH + NT - 1) / NT;
   constexpr int NCH_V = RM ? (KT * DCH + NT - 1) / NT : (DV * VCH + NT - 1) / NT;
-  constexpr float BIAS = 8.0f;
+  constexpr float BIAS = kLevelBias;
   __shared__ __attribute__((aligned(16))) unsigned char smem[R * BUF];
   auto slot = [](int t) __attribute__((always_inline)) -> int { return R == 4 ? (t & 3) : (int)((unsigned)t % 6u); };
 
@@ -673,11 +680,11 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_attn_v3_kernel(const SaspaAt
   const int q0 = xq * (32 * NW) + wave * 32;
   const int qi = q0 + r;
 
-  const bf16_t* Q = reinterpret_cast<const bf16_t*>(p.q) + b * p.sqb + head * D;
-  const bf16_t* Kp = reinterpret_cast<const bf16_t*>(p.k) + b * p.skb + head * D;
-  const bf16_t* VT = RM ? reinterpret_cast<const bf16_t*>(p.vt) + b * p.svb + head * D
-                        : reinterpret_cast<const bf16_t*>(p.vt) + b * p.svb + (long long)head * D * p.ldvt;
-  bf16_t* O = reinterpret_cast<bf16_t*>(p.o) + b * p.sob + head * D;
+  const h16_t* Q = reinterpret_cast<const h16_t*>(p.q) + b * p.sqb + head * D;
+  const h16_t* Kp = reinterpret_cast<const h16_t*>(p.k) + b * p.skb + head * D;
+  const h16_t* VT = RM ? reinterpret_cast<const h16_t*>(p.vt) + b * p.svb + head * D
+                        : reinterpret_cast<const h16_t*>(p.vt) + b * p.svb + (long long)head * D * p.ldvt;
+  h16_t* O = reinterpret_cast<h16_t*>(p.o) + b * p.sob + head * D;
 
   const u32x4 zero4 = {0u, 0u, 0u, 0u};
   u32x4 qf[KS];
@@ -687,8 +694,8 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_attn_v3_kernel(const SaspaAt
     qf[s] = (qi < p.nq && d < D) ? *reinterpret_cast<const u32x4*>(Q + (long long)qi * p.ldq + d) : zero4;
   }
 
-  const __amdgpu_buffer_rsrc_t rsk = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(Kp), (short)0, 0x7fffffff, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsv = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(VT), (short)0, 0x7fffffff, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsk = __builtin_amdgcn_make_buffer_rsrc(const_cast<h16_t*>(Kp), (short)0, 0x7fffffff, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsv = __builtin_amdgcn_make_buffer_rsrc(const_cast<h16_t*>(VT), (short)0, 0x7fffffff, 0x00020000);
   constexpr unsigned kInv = 0x80000000u;
   unsigned koff[NCH_K], voff[NCH_V];
   int k_key[NCH_K], k_lds[NCH_K], v_lds[NCH_V], v_kc[NCH_V];
@@ -714,7 +721,7 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_attn_v3_kernel(const SaspaAt
       if (ch >= D8) {
 #pragma unroll
         for (int bf = 0; bf < R; ++bf)
-          *reinterpret_cast<u32x4*>(smem + bf * BUF + K_BYTES + key * RROW + ch * 16) = u32x4{(ONES && ch == D8) ? 0x00003F80u : 0u, 0u, 0u, 0u};
+          *reinterpret_cast<u32x4*>(smem + bf * BUF + K_BYTES + key * RROW + ch * 16) = u32x4{(ONES && ch == D8) ? kHalfOne : 0u, 0u, 0u, 0u};
       }
     }
   } else {
@@ -729,7 +736,7 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_attn_v3_kernel(const SaspaAt
   for (int q = tid; q < DV * VCH; q += NT) {
     const int d = q / VCH, kc = q - d * VCH;
     if (d >= D) {
-      const unsigned fill = (ONES && d == D) ? 0x3F803F80u : 0u;
+      const unsigned fill = (ONES && d == D) ? kHalfOnes2 : 0u;
 #pragma unroll
       for (int bf = 0; bf < R; ++bf)
         *reinterpret_cast<u32x4*>(smem + bf * BUF + K_BYTES + d * VROW + kc * 16) = u32x4{fill, fill, fill, fill};
@@ -811,8 +818,7 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_attn_v3_kernel(const SaspaAt
 #pragma unroll
       for (int s = 0; s < KS; ++s) {
         const u32x4 kf = *reinterpret_cast<const u32x4*>(ksm + ((kb * 32 + r) * KSLOTS + 2 * s + h) * 16);
-        S[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kf), __builtin_bit_cast(bf16x8, qf[s]),
-                                                        s == 0 ? negm : S[kb], 0, 0, 0);
+        S[kb] = MFMA_32X32X16(kf, qf[s], s == 0 ? negm : S[kb]);
       }
   };
   auto mask_tail = [&](int t, f32x16 (&S)[NKB]) __attribute__((always_inline)) {
@@ -843,7 +849,7 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_attn_v3_kernel(const SaspaAt
         } else {
           vf = *reinterpret_cast<const u32x4*>(vsm + (nb * 32 + r) * VROW + ks * 32 + 16 * h);
         }
-        acc_o[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vf), __builtin_bit_cast(bf16x8, pf), acc_o[nb], 0, 0, 0);
+        acc_o[nb] = MFMA_32X32X16(vf, pf, acc_o[nb]);
       }
     }
   };
@@ -887,7 +893,7 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_attn_v3_kernel(const SaspaAt
       const unsigned char* vsm = smem + slot(t - 1) * BUF + K_BYTES;
       const unsigned char* ksm = smem + slot(t + 1) * BUF;
       auto frag = [&](int i) __attribute__((always_inline)) -> u32x4 {
-        if (ABL & 4) return u32x4{(unsigned)i, 0x3f803f80u, (unsigned)lane, 0x3f803f80u};
+        if (ABL & 4) return u32x4{(unsigned)i, kHalfOnes2, (unsigned)lane, kHalfOnes2};
         if (i < NPV) {
           if (RM) {
             const unsigned char* blk = vsm + tr_base + (i / NB) * 16 * RROW + (i % NB) * 64;
@@ -912,12 +918,11 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_attn_v3_kernel(const SaspaAt
           const int ks = i / NB, nb = i % NB, kb = ks >> 1, half = ks & 1;
           const u32x4 pf = {Pp[kb][4 * half + 0], Pp[kb][4 * half + 1], Pp[kb][4 * half + 2], Pp[kb][4 * half + 3]};
           if (ABL & 2) { asm volatile("" ::"v"(fr[i % (PF + 1)]), "v"(pf)); }
-          else acc_o[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fr[i % (PF + 1)]), __builtin_bit_cast(bf16x8, pf), acc_o[nb], 0, 0, 0);
+          else acc_o[nb] = MFMA_32X32X16(fr[i % (PF + 1)], pf, acc_o[nb]);
         } else {
           const int q = i - NPV, kb = q / KS, sx = q - kb * KS;
           if (ABL & 2) { asm volatile("" ::"v"(fr[i % (PF + 1)])); if (sx == 0) Sn[kb] = negm; }
-          else Sn[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fr[i % (PF + 1)]), __builtin_bit_cast(bf16x8, qf[sx]),
-                                                                sx == 0 ? negm : Sn[kb], 0, 0, 0);
+          else Sn[kb] = MFMA_32X32X16(fr[i % (PF + 1)], qf[sx], sx == 0 ? negm : Sn[kb]);
         }
         const int nu = NU / NM + (i < NU % NM ? 1 : 0);
 #pragma unroll
@@ -1011,7 +1016,7 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_attn_v3_kernel(const SaspaAt
   else pv_tile(ntiles - 1, P0);
   if ((ABL & 16) && tid == 0) {
     // diagnostics: the tool's output allocation extends 16 bytes per workgroup beyond batch * sob elements
-    unsigned long long* dbg = reinterpret_cast<unsigned long long*>(reinterpret_cast<bf16_t*>(p.o) + (long long)p.batch * p.sob) + 2 * lin;
+    unsigned long long* dbg = reinterpret_cast<unsigned long long*>(reinterpret_cast<h16_t*>(p.o) + (long long)p.batch * p.sob) + 2 * lin;
     dbg[0] = __builtin_amdgcn_s_memtime() - st0;
     dbg[1] = __builtin_amdgcn_s_memrealtime() - sr0;
   }
@@ -1038,7 +1043,7 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_attn_v3_kernel(const SaspaAt
         if (d < D) {
           float v[4] = {acc_o[nb][4 * g + 0] * inv, acc_o[nb][4 * g + 1] * inv, acc_o[nb][4 * g + 2] * inv,
                         acc_o[nb][4 * g + 3] * inv};
-          Elem<bf16_t>::store4(O + (long long)qi * p.ldo + d, v);
+          Elem<h16_t>::store4(O + (long long)qi * p.ldo + d, v);
         }
       }
   }
@@ -1070,7 +1075,7 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_attn_v4_kernel(const SaspaAt
   constexpr int BUF = K_BYTES + V_BYTES;
   constexpr int NCH_K = (KT * KCH + NT - 1) / NT;
   constexpr int NCH_V = (DV * VCH + NT - 1) / NT;
-  constexpr float BIAS = 8.0f;
+  constexpr float BIAS = kLevelBias;
   __shared__ __attribute__((aligned(16))) unsigned char smem[4 * BUF];
 
   const int tid = threadIdx.x;
@@ -1087,10 +1092,10 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_attn_v4_kernel(const SaspaAt
   constexpr int sp = KS - 1, hp = 1;                   // the first pad element of the head dimension: fragment sp, lane half hp
   const int q0 = xq * (64 * NW) + wave * 64;
 
-  const bf16_t* Q = reinterpret_cast<const bf16_t*>(p.q) + b * p.sqb + head * D;
-  const bf16_t* Kp = reinterpret_cast<const bf16_t*>(p.k) + b * p.skb + head * D;
-  const bf16_t* VT = reinterpret_cast<const bf16_t*>(p.vt) + b * p.svb + (long long)head * D * p.ldvt;
-  bf16_t* O = reinterpret_cast<bf16_t*>(p.o) + b * p.sob + head * D;
+  const h16_t* Q = reinterpret_cast<const h16_t*>(p.q) + b * p.sqb + head * D;
+  const h16_t* Kp = reinterpret_cast<const h16_t*>(p.k) + b * p.skb + head * D;
+  const h16_t* VT = reinterpret_cast<const h16_t*>(p.vt) + b * p.svb + (long long)head * D * p.ldvt;
+  h16_t* O = reinterpret_cast<h16_t*>(p.o) + b * p.sob + head * D;
 
   const u32x4 zero4 = {0u, 0u, 0u, 0u};
   u32x4 qf[2][KS];
@@ -1102,8 +1107,8 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_attn_v4_kernel(const SaspaAt
       qf[qb][s] = (qi < p.nq && d < D) ? *reinterpret_cast<const u32x4*>(Q + (long long)qi * p.ldq + d) : zero4;
     }
 
-  const __amdgpu_buffer_rsrc_t rsk = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(Kp), (short)0, 0x7fffffff, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsv = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(VT), (short)0, 0x7fffffff, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsk = __builtin_amdgcn_make_buffer_rsrc(const_cast<h16_t*>(Kp), (short)0, 0x7fffffff, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsv = __builtin_amdgcn_make_buffer_rsrc(const_cast<h16_t*>(VT), (short)0, 0x7fffffff, 0x00020000);
   constexpr unsigned kInv = 0x80000000u;
   unsigned koff[NCH_K], voff[NCH_V];
   int k_key[NCH_K], k_lds[NCH_K], v_lds[NCH_V], v_kc[NCH_V];
@@ -1128,7 +1133,7 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_attn_v4_kernel(const SaspaAt
   for (int q = tid; q < DV * VCH; q += NT) {
     const int d = q / VCH, kc = q - d * VCH;
     if (d >= D) {
-      const unsigned fill = d == D ? 0x3F803F80u : 0u;   // the ones row: O^T row D accumulates the softmax denominator
+      const unsigned fill = d == D ? kHalfOnes2 : 0u;   // the ones row: O^T row D accumulates the softmax denominator
 #pragma unroll
       for (int bf = 0; bf < 4; ++bf)
         *reinterpret_cast<u32x4*>(smem + bf * BUF + K_BYTES + d * VROW + kc * 16) = u32x4{fill, fill, fill, fill};
@@ -1157,7 +1162,7 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_attn_v4_kernel(const SaspaAt
     unsigned char* vsm = buf + K_BYTES;
 #pragma unroll
     for (int i = 0; i < NCH_K; ++i)
-      if (k_lds[i] >= 0) *reinterpret_cast<u32x4*>(ksm + k_lds[i]) = k_one[i] ? u32x4{0x00003F80u, 0u, 0u, 0u} : kreg[i];
+      if (k_lds[i] >= 0) *reinterpret_cast<u32x4*>(ksm + k_lds[i]) = k_one[i] ? u32x4{kHalfOne, 0u, 0u, 0u} : kreg[i];
 #pragma unroll
     for (int i = 0; i < NCH_V; ++i) {
       if (v_lds[i] >= 0) {
@@ -1204,8 +1209,7 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_attn_v4_kernel(const SaspaAt
       const u32x4 kf = kfrag(ht, s);
 #pragma unroll
       for (int qb = 0; qb < 2; ++qb)
-        S[qb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kf), __builtin_bit_cast(bf16x8, qf[qb][s]),
-                                                        s == 0 ? zero16 : S[qb], 0, 0, 0);
+        S[qb] = MFMA_32X32X16(kf, qf[qb][s], s == 0 ? zero16 : S[qb]);
     }
   };
   auto mask_tail = [&](int ht, f32x16 (&S)[2]) __attribute__((always_inline)) {
@@ -1229,7 +1233,7 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_attn_v4_kernel(const SaspaAt
 #pragma unroll
         for (int qb = 0; qb < 2; ++qb) {
           const u32x4 pf = {P[qb][4 * j + 0], P[qb][4 * j + 1], P[qb][4 * j + 2], P[qb][4 * j + 3]};
-          acc_o[qb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vf), __builtin_bit_cast(bf16x8, pf), acc_o[qb][nb], 0, 0, 0);
+          acc_o[qb][nb] = MFMA_32X32X16(vf, pf, acc_o[qb][nb]);
         }
       }
   };
@@ -1270,14 +1274,13 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_attn_v4_kernel(const SaspaAt
 #pragma unroll
           for (int qb = 0; qb < 2; ++qb) {
             const u32x4 pf = {Pp[qb][4 * j + 0], Pp[qb][4 * j + 1], Pp[qb][4 * j + 2], Pp[qb][4 * j + 3]};
-            acc_o[qb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, pf), acc_o[qb][nb], 0, 0, 0);
+            acc_o[qb][nb] = MFMA_32X32X16(a, pf, acc_o[qb][nb]);
           }
         } else {
           const int sx = f - NPV;
 #pragma unroll
           for (int qb = 0; qb < 2; ++qb)
-            Sn[qb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, qf[qb][sx]),
-                                                             sx == 0 ? zero16 : Sn[qb], 0, 0, 0);
+            Sn[qb] = MFMA_32X32X16(a, qf[qb][sx], sx == 0 ? zero16 : Sn[qb]);
         }
         const int nu = NU / NF + (f < NU % NF ? 1 : 0);
 #pragma unroll
@@ -1299,8 +1302,8 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_attn_v4_kernel(const SaspaAt
         for (int i = 1; i < 16; ++i) mx = fmaxf(mx, Sc[qb][i]);
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
         const float want = ht == 0 ? mx + BIAS : fmaxf(mx + BIAS, 0.f);
-        // the new level must be a bf16 number (it travels as an element of Q): round, then move by the EXACT difference
-        const float mnew = __builtin_bit_cast(float, pack2(0.f, mlev[qb] + want) & 0xffff0000u);
+        // the new level must be a number of the 16-bit type (it travels as an element of Q): round, then move by the EXACT difference
+        const float mnew = round_h16(mlev[qb] + want);
         const float delta = mnew - mlev[qb];
         mlev[qb] = mnew;
         if (h == hp) qf[qb][sp].x = pack2(-mnew, 0.f);
@@ -1367,7 +1370,7 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_attn_v4_kernel(const SaspaAt
           if (d < D) {
             float v[4] = {acc_o[qb][nb][4 * g + 0] * inv, acc_o[qb][nb][4 * g + 1] * inv, acc_o[qb][nb][4 * g + 2] * inv,
                           acc_o[qb][nb][4 * g + 3] * inv};
-            Elem<bf16_t>::store4(O + (long long)qi * p.ldo + d, v);
+            Elem<h16_t>::store4(O + (long long)qi * p.ldo + d, v);
           }
         }
     }
@@ -1542,9 +1545,9 @@ extern "C" int saspa_softmax_rows(int dtype, void* x, long long rows, int n, int
   if (causal && rows_per_mat <= 0) return SASPA_EINVAL;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const unsigned grid = (unsigned)((rows + 3) / 4);
-  if (dtype == SASPA_BF16)
-    hipLaunchKernelGGL(softmax_rows_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (bf16_t*)x, rows, n, ld, scale, causal, rows_per_mat);
-  else if (dtype == SASPA_F32)
+  if (dtype == SASPA_HALF)
+    hipLaunchKernelGGL(softmax_rows_kernel<h16_t>, dim3(grid), dim3(256), 0, s, (h16_t*)x, rows, n, ld, scale, causal, rows_per_mat);
+  else if (dtype == SASPA_F32 && kServesF32)
     hipLaunchKernelGGL(softmax_rows_kernel<float>, dim3(grid), dim3(256), 0, s, (float*)x, rows, n, ld, scale, causal, rows_per_mat);
   else
     return SASPA_EINVAL;

@@ -211,9 +211,9 @@ extern "C" int saspa_unipc_step(int dtype, const void* eps, void* x, void* state
     for (int j = 0; j < 12; ++j) rr.v[j] = row[j];
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const unsigned grid = grid_for((long long)nimg * hw);
-  if (dtype == SASPA_BF16)
-    hipLaunchKernelGGL((cfg_unipc_kernel<bf16_t, false>), dim3(grid), dim3(256), 0, s, (const bf16_t*)eps, (bf16_t*)x, (bf16_t*)state, nimg, hw, C, 0.f, rr, table, index);
-  else if (dtype == SASPA_F32)
+  if (dtype == SASPA_HALF)
+    hipLaunchKernelGGL((cfg_unipc_kernel<h16_t, false>), dim3(grid), dim3(256), 0, s, (const h16_t*)eps, (h16_t*)x, (h16_t*)state, nimg, hw, C, 0.f, rr, table, index);
+  else if (dtype == SASPA_F32 && kServesF32)
     hipLaunchKernelGGL((cfg_unipc_kernel<float, false>), dim3(grid), dim3(256), 0, s, (const float*)eps, (float*)x, (float*)state, nimg, hw, C, 0.f, rr, table, index);
   else
     return SASPA_EINVAL;
@@ -231,9 +231,9 @@ extern "C" int saspa_cfg_unipc_step(int dtype, const void* eps, void* x, void* s
     for (int j = 0; j < 12; ++j) rr.v[j] = row[j];
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const unsigned grid = grid_for((long long)nimg * hw);
-  if (dtype == SASPA_BF16)
-    hipLaunchKernelGGL(cfg_unipc_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (const bf16_t*)eps, (bf16_t*)x, (bf16_t*)state, nimg, hw, C, guidance, rr, table, index);
-  else if (dtype == SASPA_F32)
+  if (dtype == SASPA_HALF)
+    hipLaunchKernelGGL(cfg_unipc_kernel<h16_t>, dim3(grid), dim3(256), 0, s, (const h16_t*)eps, (h16_t*)x, (h16_t*)state, nimg, hw, C, guidance, rr, table, index);
+  else if (dtype == SASPA_F32 && kServesF32)
     hipLaunchKernelGGL(cfg_unipc_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)eps, (float*)x, (float*)state, nimg, hw, C, guidance, rr, table, index);
   else
     return SASPA_EINVAL;
@@ -313,9 +313,9 @@ extern "C" int saspa_geglu(int dtype, const void* x, int ldx, void* y, int ldy, 
   if (F % 8 || ldx % 8 || ldy % 8 || !aligned16(x) || !aligned16(y)) return SASPA_EALIGN;
   if (ldx < 2 * F || ldy < F) return SASPA_ERANGE;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == SASPA_BF16)
-    hipLaunchKernelGGL(geglu_kernel<bf16_t>, dim3(grid_for(rows * (F / 8))), dim3(256), 0, s, (const bf16_t*)x, ldx, (bf16_t*)y, ldy, rows, F);
-  else if (dtype == SASPA_F32)
+  if (dtype == SASPA_HALF)
+    hipLaunchKernelGGL(geglu_kernel<h16_t>, dim3(grid_for(rows * (F / 8))), dim3(256), 0, s, (const h16_t*)x, ldx, (h16_t*)y, ldy, rows, F);
+  else if (dtype == SASPA_F32 && kServesF32)
     hipLaunchKernelGGL(geglu_kernel<float>, dim3(grid_for(rows * (F / 8))), dim3(256), 0, s, (const float*)x, ldx, (float*)y, ldy, rows, F);
   else
     return SASPA_EINVAL;
@@ -328,9 +328,9 @@ extern "C" int saspa_activation(int dtype, int act, const void* x, int ldx, void
   if (!x || !y || rows <= 0 || C <= 0 || (act != 1 && act != 2 && act != 4 && act != 5)) return SASPA_EINVAL;
   if (C % 8 || ldx % 8 || ldy % 8 || !aligned16(x) || !aligned16(y)) return SASPA_EALIGN;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == SASPA_BF16)
-    hipLaunchKernelGGL(activation_kernel<bf16_t>, dim3(grid_for(rows * (C / 8))), dim3(256), 0, s, act, (const bf16_t*)x, ldx, (bf16_t*)y, ldy, rows, C);
-  else if (dtype == SASPA_F32)
+  if (dtype == SASPA_HALF)
+    hipLaunchKernelGGL(activation_kernel<h16_t>, dim3(grid_for(rows * (C / 8))), dim3(256), 0, s, act, (const h16_t*)x, ldx, (h16_t*)y, ldy, rows, C);
+  else if (dtype == SASPA_F32 && kServesF32)
     hipLaunchKernelGGL(activation_kernel<float>, dim3(grid_for(rows * (C / 8))), dim3(256), 0, s, act, (const float*)x, ldx, (float*)y, ldy, rows, C);
   else
     return SASPA_EINVAL;
@@ -343,9 +343,9 @@ extern "C" int saspa_embed_tokens(int dtype, const int* ids, int n, int npos, co
   if (!ids || !tok || !pos || !out || n <= 0 || npos <= 0 || C <= 0) return SASPA_EINVAL;
   if (C % 8 || !aligned16(tok) || !aligned16(pos) || !aligned16(out)) return SASPA_EALIGN;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == SASPA_BF16)
-    hipLaunchKernelGGL(embed_tokens_kernel<bf16_t>, dim3(grid_for((long long)n * (C / 8))), dim3(256), 0, s, ids, n, npos, (const bf16_t*)tok, (const bf16_t*)pos, C, (bf16_t*)out);
-  else if (dtype == SASPA_F32)
+  if (dtype == SASPA_HALF)
+    hipLaunchKernelGGL(embed_tokens_kernel<h16_t>, dim3(grid_for((long long)n * (C / 8))), dim3(256), 0, s, ids, n, npos, (const h16_t*)tok, (const h16_t*)pos, C, (h16_t*)out);
+  else if (dtype == SASPA_F32 && kServesF32)
     hipLaunchKernelGGL(embed_tokens_kernel<float>, dim3(grid_for((long long)n * (C / 8))), dim3(256), 0, s, ids, n, npos, (const float*)tok, (const float*)pos, C, (float*)out);
   else
     return SASPA_EINVAL;
@@ -361,9 +361,9 @@ extern "C" int saspa_embed_tokens_ctx(int dtype, const int* ids, int nseq, int n
   if (C % 8 || !aligned16(tok) || !aligned16(pos) || !aligned16(out) || (ctx && !aligned16(ctx))) return SASPA_EALIGN;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const unsigned grid = grid_for((long long)nseq * (ntok + nctx) * (C / 8));
-  if (dtype == SASPA_BF16)
-    hipLaunchKernelGGL(embed_tokens_ctx_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, ids, nseq, ntok, (const bf16_t*)ctx, nctx, ctx_begin, (const bf16_t*)tok, (const bf16_t*)pos, C, (bf16_t*)out);
-  else if (dtype == SASPA_F32)
+  if (dtype == SASPA_HALF)
+    hipLaunchKernelGGL(embed_tokens_ctx_kernel<h16_t>, dim3(grid), dim3(256), 0, s, ids, nseq, ntok, (const h16_t*)ctx, nctx, ctx_begin, (const h16_t*)tok, (const h16_t*)pos, C, (h16_t*)out);
+  else if (dtype == SASPA_F32 && kServesF32)
     hipLaunchKernelGGL(embed_tokens_ctx_kernel<float>, dim3(grid), dim3(256), 0, s, ids, nseq, ntok, (const float*)ctx, nctx, ctx_begin, (const float*)tok, (const float*)pos, C, (float*)out);
   else
     return SASPA_EINVAL;
@@ -379,9 +379,9 @@ extern "C" int saspa_cfg_plms_step(int dtype, const void* eps, void* x, void* hi
   if (!aligned16(eps) || !aligned16(x) || !aligned16(hist) || (sample && !aligned16(sample))) return SASPA_EALIGN;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const unsigned grid = grid_for((long long)nimg * hw);
-  if (dtype == SASPA_BF16)
-    hipLaunchKernelGGL(cfg_plms_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (const bf16_t*)eps, (bf16_t*)x, (bf16_t*)hist, (const bf16_t*)sample, nimg, hw, C, guidance, store_slot, w_cur, w_hist[0], w_hist[1], w_hist[2], w_hist[3], coef_sample, coef_model);
-  else if (dtype == SASPA_F32)
+  if (dtype == SASPA_HALF)
+    hipLaunchKernelGGL(cfg_plms_kernel<h16_t>, dim3(grid), dim3(256), 0, s, (const h16_t*)eps, (h16_t*)x, (h16_t*)hist, (const h16_t*)sample, nimg, hw, C, guidance, store_slot, w_cur, w_hist[0], w_hist[1], w_hist[2], w_hist[3], coef_sample, coef_model);
+  else if (dtype == SASPA_F32 && kServesF32)
     hipLaunchKernelGGL(cfg_plms_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)eps, (float*)x, (float*)hist, (const float*)sample, nimg, hw, C, guidance, store_slot, w_cur, w_hist[0], w_hist[1], w_hist[2], w_hist[3], coef_sample, coef_model);
   else
     return SASPA_EINVAL;
@@ -396,9 +396,9 @@ extern "C" int saspa_cfg_plms_step_dev(int dtype, const void* eps, void* x, void
   if (!aligned16(eps) || !aligned16(x) || !aligned16(hist) || !aligned16(saved)) return SASPA_EALIGN;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const unsigned grid = grid_for((long long)nimg * hw);
-  if (dtype == SASPA_BF16)
-    hipLaunchKernelGGL(cfg_plms_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (const bf16_t*)eps, (bf16_t*)x, (bf16_t*)hist, (const bf16_t*)nullptr, nimg, hw, C, guidance, -1, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, table, index, (bf16_t*)saved);
-  else if (dtype == SASPA_F32)
+  if (dtype == SASPA_HALF)
+    hipLaunchKernelGGL(cfg_plms_kernel<h16_t>, dim3(grid), dim3(256), 0, s, (const h16_t*)eps, (h16_t*)x, (h16_t*)hist, (const h16_t*)nullptr, nimg, hw, C, guidance, -1, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, table, index, (h16_t*)saved);
+  else if (dtype == SASPA_F32 && kServesF32)
     hipLaunchKernelGGL(cfg_plms_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)eps, (float*)x, (float*)hist, (const float*)nullptr, nimg, hw, C, guidance, -1, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, table, index, (float*)saved);
   else
     return SASPA_EINVAL;
@@ -415,9 +415,9 @@ extern "C" int saspa_cfg_ddim_step(int dtype, const void* eps, void* x, int nimg
   if (!(sqrt_a_t > 0.f)) return SASPA_EINVAL;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const unsigned grid = grid_for((long long)nimg * hw);
-  if (dtype == SASPA_BF16)
-    hipLaunchKernelGGL((cfg_ddim_kernel<bf16_t, true>), dim3(grid), dim3(256), 0, s, (const bf16_t*)eps, (bf16_t*)x, nimg, hw, C, guidance, sqrt_a_t, sqrt_1m_a_t, sqrt_a_prev, sqrt_1m_a_prev);
-  else if (dtype == SASPA_F32)
+  if (dtype == SASPA_HALF)
+    hipLaunchKernelGGL((cfg_ddim_kernel<h16_t, true>), dim3(grid), dim3(256), 0, s, (const h16_t*)eps, (h16_t*)x, nimg, hw, C, guidance, sqrt_a_t, sqrt_1m_a_t, sqrt_a_prev, sqrt_1m_a_prev);
+  else if (dtype == SASPA_F32 && kServesF32)
     hipLaunchKernelGGL((cfg_ddim_kernel<float, true>), dim3(grid), dim3(256), 0, s, (const float*)eps, (float*)x, nimg, hw, C, guidance, sqrt_a_t, sqrt_1m_a_t, sqrt_a_prev, sqrt_1m_a_prev);
   else
     return SASPA_EINVAL;
@@ -433,9 +433,9 @@ extern "C" int saspa_ddim_step(int dtype, const void* eps, void* x, int nimg, lo
   if (!(sqrt_a_t > 0.f)) return SASPA_EINVAL;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const unsigned grid = grid_for((long long)nimg * hw);
-  if (dtype == SASPA_BF16)
-    hipLaunchKernelGGL((cfg_ddim_kernel<bf16_t, false>), dim3(grid), dim3(256), 0, s, (const bf16_t*)eps, (bf16_t*)x, nimg, hw, C, 0.f, sqrt_a_t, sqrt_1m_a_t, sqrt_a_prev, sqrt_1m_a_prev);
-  else if (dtype == SASPA_F32)
+  if (dtype == SASPA_HALF)
+    hipLaunchKernelGGL((cfg_ddim_kernel<h16_t, false>), dim3(grid), dim3(256), 0, s, (const h16_t*)eps, (h16_t*)x, nimg, hw, C, 0.f, sqrt_a_t, sqrt_1m_a_t, sqrt_a_prev, sqrt_1m_a_prev);
+  else if (dtype == SASPA_F32 && kServesF32)
     hipLaunchKernelGGL((cfg_ddim_kernel<float, false>), dim3(grid), dim3(256), 0, s, (const float*)eps, (float*)x, nimg, hw, C, 0.f, sqrt_a_t, sqrt_1m_a_t, sqrt_a_prev, sqrt_1m_a_prev);
   else
     return SASPA_EINVAL;
@@ -498,10 +498,10 @@ extern "C" int saspa_ddim_step_dev(int dtype, const void* eps, void* x, int nimg
   if (!aligned16(eps) || !aligned16(x)) return SASPA_EALIGN;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const unsigned grid = grid_for((long long)nimg * hw);
-  if (dtype == SASPA_BF16) {
-    if (cfg) hipLaunchKernelGGL((cfg_ddim_kernel<bf16_t, true>), dim3(grid), dim3(256), 0, s, (const bf16_t*)eps, (bf16_t*)x, nimg, hw, C, guidance, 1.f, 0.f, 1.f, 0.f, coefs, index);
-    else hipLaunchKernelGGL((cfg_ddim_kernel<bf16_t, false>), dim3(grid), dim3(256), 0, s, (const bf16_t*)eps, (bf16_t*)x, nimg, hw, C, 0.f, 1.f, 0.f, 1.f, 0.f, coefs, index);
-  } else if (dtype == SASPA_F32) {
+  if (dtype == SASPA_HALF) {
+    if (cfg) hipLaunchKernelGGL((cfg_ddim_kernel<h16_t, true>), dim3(grid), dim3(256), 0, s, (const h16_t*)eps, (h16_t*)x, nimg, hw, C, guidance, 1.f, 0.f, 1.f, 0.f, coefs, index);
+    else hipLaunchKernelGGL((cfg_ddim_kernel<h16_t, false>), dim3(grid), dim3(256), 0, s, (const h16_t*)eps, (h16_t*)x, nimg, hw, C, 0.f, 1.f, 0.f, 1.f, 0.f, coefs, index);
+  } else if (dtype == SASPA_F32 && kServesF32) {
     if (cfg) hipLaunchKernelGGL((cfg_ddim_kernel<float, true>), dim3(grid), dim3(256), 0, s, (const float*)eps, (float*)x, nimg, hw, C, guidance, 1.f, 0.f, 1.f, 0.f, coefs, index);
     else hipLaunchKernelGGL((cfg_ddim_kernel<float, false>), dim3(grid), dim3(256), 0, s, (const float*)eps, (float*)x, nimg, hw, C, 0.f, 1.f, 0.f, 1.f, 0.f, coefs, index);
   } else {
@@ -537,10 +537,10 @@ extern "C" int saspa_vae_sample_noise(int dtype, const void* moments, const void
   if (!moments || !e1 || !e2 || !out || npix <= 0) return SASPA_EINVAL;
   if (!aligned16(moments) || !aligned16(e1) || !aligned16(e2) || !aligned16(out)) return SASPA_EALIGN;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == SASPA_BF16)
-    hipLaunchKernelGGL(vae_sample_noise_kernel<bf16_t>, dim3(grid_for(npix)), dim3(256), 0, s, (const bf16_t*)moments, (const bf16_t*)e1,
-                       (const bf16_t*)e2, (bf16_t*)out, npix, scaling, sa, s1m);
-  else if (dtype == SASPA_F32)
+  if (dtype == SASPA_HALF)
+    hipLaunchKernelGGL(vae_sample_noise_kernel<h16_t>, dim3(grid_for(npix)), dim3(256), 0, s, (const h16_t*)moments, (const h16_t*)e1,
+                       (const h16_t*)e2, (h16_t*)out, npix, scaling, sa, s1m);
+  else if (dtype == SASPA_F32 && kServesF32)
     hipLaunchKernelGGL(vae_sample_noise_kernel<float>, dim3(grid_for(npix)), dim3(256), 0, s, (const float*)moments, (const float*)e1,
                        (const float*)e2, (float*)out, npix, scaling, sa, s1m);
   else
@@ -553,9 +553,9 @@ extern "C" int saspa_scale(int dtype, const void* x, void* y, long long n, float
   if (!x || !y || n <= 0) return SASPA_EINVAL;
   if (n % 8 || !aligned16(x) || !aligned16(y)) return SASPA_EALIGN;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == SASPA_BF16)
-    hipLaunchKernelGGL(scale_kernel<bf16_t>, dim3(grid_for(n / 8)), dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)y, n / 8, sc);
-  else if (dtype == SASPA_F32)
+  if (dtype == SASPA_HALF)
+    hipLaunchKernelGGL(scale_kernel<h16_t>, dim3(grid_for(n / 8)), dim3(256), 0, s, (const h16_t*)x, (h16_t*)y, n / 8, sc);
+  else if (dtype == SASPA_F32 && kServesF32)
     hipLaunchKernelGGL(scale_kernel<float>, dim3(grid_for(n / 8)), dim3(256), 0, s, (const float*)x, (float*)y, n / 8, sc);
   else
     return SASPA_EINVAL;
@@ -567,9 +567,9 @@ extern "C" int saspa_u8_to_act(int dtype, const uint8_t* src, void* dst, long lo
   if (!src || !dst || npix <= 0) return SASPA_EINVAL;
   if (!aligned16(dst)) return SASPA_EALIGN;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == SASPA_BF16)
-    hipLaunchKernelGGL(u8_to_act_kernel<bf16_t>, dim3(grid_for(npix)), dim3(256), 0, s, src, (bf16_t*)dst, npix);
-  else if (dtype == SASPA_F32)
+  if (dtype == SASPA_HALF)
+    hipLaunchKernelGGL(u8_to_act_kernel<h16_t>, dim3(grid_for(npix)), dim3(256), 0, s, src, (h16_t*)dst, npix);
+  else if (dtype == SASPA_F32 && kServesF32)
     hipLaunchKernelGGL(u8_to_act_kernel<float>, dim3(grid_for(npix)), dim3(256), 0, s, src, (float*)dst, npix);
   else
     return SASPA_EINVAL;
@@ -581,9 +581,9 @@ extern "C" int saspa_act_to_u8(int dtype, const void* x, int ldx, uint8_t* dst, 
   if (!x || !dst || npix <= 0) return SASPA_EINVAL;
   if (ldx % 4 || ldx < 4 || !aligned16(x)) return SASPA_EALIGN;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == SASPA_BF16)
-    hipLaunchKernelGGL(act_to_u8_kernel<bf16_t>, dim3(grid_for(npix)), dim3(256), 0, s, (const bf16_t*)x, ldx, dst, npix);
-  else if (dtype == SASPA_F32)
+  if (dtype == SASPA_HALF)
+    hipLaunchKernelGGL(act_to_u8_kernel<h16_t>, dim3(grid_for(npix)), dim3(256), 0, s, (const h16_t*)x, ldx, dst, npix);
+  else if (dtype == SASPA_F32 && kServesF32)
     hipLaunchKernelGGL(act_to_u8_kernel<float>, dim3(grid_for(npix)), dim3(256), 0, s, (const float*)x, ldx, dst, npix);
   else
     return SASPA_EINVAL;
@@ -592,4 +592,5 @@ extern "C" int saspa_act_to_u8(int dtype, const void* x, int ldx, uint8_t* dst, 
 }
 
 extern "C" int saspa_abi_version(void) { return 20; }
+extern "C" int saspa_half_type(void) { return SASPA_HALF; }
 extern "C" const char* saspa_build_arch(void) { return "gfx950"; }

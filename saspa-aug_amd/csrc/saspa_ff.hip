@@ -54,7 +54,7 @@ __device__ __forceinline__ void ff_unpack_opaque(const u32x4& a, float* v) {
 }
 
 __device__ __forceinline__ f32x16 ffmfma(const u32x4& a, const u32x4& b, const f32x16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+  return MFMA_32X32X16(a, b, c);
 }
 
 template <int abl>

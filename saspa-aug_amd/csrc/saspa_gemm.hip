@@ -31,10 +31,9 @@
 namespace {
 
 template <typename T> struct Mma;
-template <> struct Mma<bf16_t> {
+template <> struct Mma<h16_t> {
   __device__ static __forceinline__ void run(const u32x4& wf, const u32x4& xf, f32x4& acc) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf), __builtin_bit_cast(bf16x8, xf),
-                                                  acc, 0, 0, 0);
+    acc = MFMA_16X16X32(wf, xf, acc);
   }
 };
 template <> struct Mma<float> {
@@ -54,6 +53,7 @@ template <> struct Mma<float> {
 };
 
 template <> struct Mma<f32x3_t> {
+  // (bf16 by construction -- hi / lo halves of an fp32 value; the fp16 build refuses SASPA_F32X3 and never instantiates a launch of it)
   // per-chunk form (generic loader kernel, fp32 parity of odd shapes): the exact fp32 chain
   __device__ static __forceinline__ void run(const u32x4& wf, const u32x4& xf, f32x4& acc) { Mma<float>::run(wf, xf, acc); }
   // 8 fp32 values of one lane (its two 16-byte chunks of the K-tile) -> 8 bf16 "hi" + 8 bf16 "lo" (round to nearest)
@@ -71,9 +71,9 @@ template <> struct Mma<f32x3_t> {
     lo = u32x4{l[0], l[1], l[2], l[3]};
   }
   __device__ static __forceinline__ void run3(const u32x4& wh, const u32x4& wl, const u32x4& xh, const u32x4& xl, f32x4& acc) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wl), __builtin_bit_cast(bf16x8, xh), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wh), __builtin_bit_cast(bf16x8, xl), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wh), __builtin_bit_cast(bf16x8, xh), acc, 0, 0, 0);
+    acc = MFMA_16X16X32(wl, xh, acc);
+    acc = MFMA_16X16X32(wh, xl, acc);
+    acc = MFMA_16X16X32(wh, xh, acc);
   }
 };
 template <typename T> struct is_x3 { static constexpr bool value = false; };
@@ -178,7 +178,7 @@ __device__ __forceinline__ void gemm_epilogue(const SaspaGemmParams& p, f32x4 (&
           }
           if (res) {
             float b[8];
-            Elem<bf16_t>::load_chunk(reinterpret_cast<const bf16_t*>(res) + (long long)m * p.ldr + n, b);
+            Elem<h16_t>::load_chunk(reinterpret_cast<const h16_t*>(res) + (long long)m * p.ldr + n, b);
 #pragma unroll
             for (int e = 0; e < 8; ++e) a[e] += b[e];
           }
@@ -202,7 +202,7 @@ __device__ __forceinline__ void gemm_epilogue(const SaspaGemmParams& p, f32x4 (&
           const int r0 = hb * 128;
           const int nrows = min(128, min(BM, p.M - cbm * BM) - r0);
           if (nrows > 0)
-            gn_tile_stats<NT>(reinterpret_cast<const bf16_t*>(ct) + r0 * CP, CP, nrows, nunits, p.gn_unit, scratch,
+            gn_tile_stats<NT>(reinterpret_cast<const h16_t*>(ct) + r0 * CP, CP, nrows, nunits, p.gn_unit, scratch,
                               p.gn_stats + (((long long)(cbm * BM + r0) / 128) * (p.N / p.gn_unit) + (cbn * BN) / p.gn_unit) * 2);
           if (hb + 1 < (BM + 127) / 128) __syncthreads();
         }
@@ -788,9 +788,9 @@ __global__ __launch_bounds__(64 * NWM * NWN, (NWM * NWN == 4 && NSTAGE > 2) ? 1 
       u32x4 xa[WM], wb[WN];
       if (abl & 8) {
 #pragma unroll
-        for (int i = 0; i < WM; ++i) xa[i] = u32x4{(unsigned)chunk, (unsigned)i, 0x3f803f80u, 0x3f803f80u};
+        for (int i = 0; i < WM; ++i) xa[i] = u32x4{(unsigned)chunk, (unsigned)i, kHalfOnes2, kHalfOnes2};
 #pragma unroll
-        for (int j = 0; j < WN; ++j) wb[j] = u32x4{(unsigned)j, (unsigned)stage, 0x3f803f80u, 0x3f803f80u};
+        for (int j = 0; j < WN; ++j) wb[j] = u32x4{(unsigned)j, (unsigned)stage, kHalfOnes2, kHalfOnes2};
       } else {
 #pragma unroll
       for (int i = 0; i < WM; ++i) {
@@ -908,13 +908,13 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const SaspaGemmParam
 // the finished bf16 slab is staged in LDS like a GEMM tile and gn_tile_stats reads it.  bf16 only.
 __global__ __launch_bounds__(256) void splitk_reduce_stats_kernel(const SaspaGemmParams p, int ksplit) {
   constexpr int BR = 128, BC = 80, CP = BC + 8, C4 = BC / 4, U = 4;
-  __shared__ __attribute__((aligned(16))) bf16_t ct[BR * CP + 4 * 256];
+  __shared__ __attribute__((aligned(16))) h16_t ct[BR * CP + 4 * 256];
   const int tid = threadIdx.x;
   const int rb = blockIdx.x, cs = blockIdx.y;
   const long long slab = (long long)p.M * p.N;
   const int hw = p.hout * p.wout;
-  bf16_t* out = reinterpret_cast<bf16_t*>(p.out);
-  const bf16_t* res = reinterpret_cast<const bf16_t*>(p.residual);
+  h16_t* out = reinterpret_cast<h16_t*>(p.out);
+  const h16_t* res = reinterpret_cast<const h16_t*>(p.residual);
   const int nrows = min(BR, p.M - rb * BR);
   const int total = nrows * C4;
   for (int q0 = tid; q0 < total; q0 += U * 256) {
@@ -951,14 +951,14 @@ __global__ __launch_bounds__(256) void splitk_reduce_stats_kernel(const SaspaGem
       for (int r = 0; r < 4; ++r) v[r] = act_pre(p.act, v[r] * p.alpha);
       if (res) {
         float rr[4];
-        Elem<bf16_t>::load4(res + (long long)m * p.ldr + n, rr);
+        Elem<h16_t>::load4(res + (long long)m * p.ldr + n, rr);
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] += rr[r];
       }
 #pragma unroll
       for (int r = 0; r < 4; ++r) v[r] = act_post(p.act, v[r]);
-      Elem<bf16_t>::store4(out + (long long)m * p.ldo + n, v);
-      Elem<bf16_t>::store4(ct + row[u] * CP + c4[u] * 4, v);
+      Elem<h16_t>::store4(out + (long long)m * p.ldo + n, v);
+      Elem<h16_t>::store4(ct + row[u] * CP + c4[u] * 4, v);
     }
   }
   __syncthreads();
@@ -969,7 +969,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_stats_kernel(const SaspaGem
 // The DMA loaders (LDS-DMA kernels of both tile widths) need a K-tile inside one tap of one source; a nearest-x2 input also needs
 // pad <= 1 and the packed 16-bit window corner of gemm_dma_kernel
 bool dma_loader_ok(const SaspaGemmParams& p) {
-  const int bk = p.dtype == SASPA_BF16 ? 64 : 32;
+  const int bk = p.dtype == SASPA_HALF ? 64 : 32;
   const int ctot = p.c0 + p.c1;
   return (ctot % bk) == 0 && (p.c1 == 0 || (p.c0 % bk) == 0) && (!p.upsample || (p.pad <= 1 && p.hin < 16000 && p.win < 16000));
 }
@@ -1127,7 +1127,7 @@ int plan_tiled(const SaspaGemmParams& p, int tile, int ksplit, GemmPlan& g) {
 
 // p: validated by check_gemm
 int plan_gemm(const SaspaGemmParams& p, GemmPlan& g) {
-  const bool bf16 = p.dtype == SASPA_BF16;
+  const bool bf16 = p.dtype == SASPA_HALF;
   const long long nb = (long long)p.nb1 * p.nb2;
   const bool pp_ok = nb == 1 && saspa_gemm_pp_eligible(p);     // bf16 only
   const bool ws_ok = saspa_gemm_ws_eligible(p);                // bf16, unbatched only
@@ -1202,11 +1202,11 @@ int check_gemm(const SaspaGemmParams* pp, SaspaGemmParams& p) {
   if (p.nb2 <= 0) p.nb2 = 1;
   if (!p.a0 || !p.w || !p.out) return SASPA_EINVAL;
   if (p.M <= 0 || p.N <= 0 || p.K <= 0 || p.batch <= 0) return SASPA_EINVAL;
-  if (p.dtype != SASPA_BF16 && p.dtype != SASPA_F32 && p.dtype != SASPA_F32X3) return SASPA_EINVAL;
+  if (!dtype_served(p.dtype)) return SASPA_EINVAL;
   if (p.kh <= 0 || p.kw <= 0 || p.stride <= 0 || p.pad < 0) return SASPA_EINVAL;
   if (p.c1 > 0 && !p.a1) return SASPA_EINVAL;
   if (p.c1 < 0 || p.c0 <= 0) return SASPA_EINVAL;
-  const int epc = p.dtype == SASPA_BF16 ? 8 : 4;
+  const int epc = p.dtype == SASPA_HALF ? 8 : 4;
   if (p.c0 % epc || p.c1 % epc || p.lda0 % epc || (p.c1 > 0 && p.lda1 % epc) || p.ldw % epc) return SASPA_EALIGN;
   if (p.ldo % 4 || (p.residual && p.ldr % 4)) return SASPA_EALIGN;
   if (!aligned16(p.a0) || !aligned16(p.w) || !aligned16(p.out) || (p.a1 && !aligned16(p.a1)) ||
@@ -1230,10 +1230,10 @@ int check_gemm(const SaspaGemmParams* pp, SaspaGemmParams& p) {
     if ((p.hout - 1) * p.stride - p.pad >= hv || (p.wout - 1) * p.stride - p.pad >= wv) return SASPA_ERANGE;
   }
   if ((long long)p.batch * p.hin * p.win >= (1ll << 31)) return SASPA_ERANGE;
-  const int bk = p.dtype == SASPA_BF16 ? 64 : 32;
+  const int bk = p.dtype == SASPA_HALF ? 64 : 32;
   {
     // buffer loads address every operand with 32-bit byte offsets below 2 GiB
-    const long long esz = p.dtype == SASPA_BF16 ? 2 : 4;
+    const long long esz = p.dtype == SASPA_HALF ? 2 : 4;
     const long long a0b = (long long)p.batch * p.hin * p.win * p.lda0 * esz;
     const long long a1b = p.c1 > 0 ? (long long)p.batch * p.hin * p.win * p.lda1 * esz : 0;
     const long long wb = (long long)p.N * p.ldw * esz;
@@ -1250,7 +1250,7 @@ int check_gemm(const SaspaGemmParams* pp, SaspaGemmParams& p) {
   if (p.act == SASPA_ACT_GEGLU) {
     // fused GEGLU: bf16 only, whole tiles, weights pre-interleaved per tile (see header)
     const int bn = (p.N % 160) == 0 ? 160 : 128;
-    if (p.dtype != SASPA_BF16 || p.N % bn || p.residual || p.ldo % 8 || p.ldo < p.N / 2) return SASPA_ERANGE;
+    if (p.dtype != SASPA_HALF || p.N % bn || p.residual || p.ldo % 8 || p.ldo < p.N / 2) return SASPA_ERANGE;
     p.ksplit = 1;
   } else if (p.act != SASPA_ACT_NONE && p.act != SASPA_ACT_SILU && p.act != SASPA_ACT_RELU && p.act != SASPA_ACT_ADD_RELU) {
     return SASPA_EINVAL;
@@ -1258,7 +1258,7 @@ int check_gemm(const SaspaGemmParams* pp, SaspaGemmParams& p) {
   if (p.ksplit > 1 && p.workspace && !aligned16(p.workspace)) return SASPA_EALIGN;
   if (p.gn_stats) {
     // epilogue GroupNorm statistics (ABI 12): bf16, whole 160-column tiles whose first column is a multiple of the unit
-    if (p.dtype != SASPA_BF16 || p.act == SASPA_ACT_GEGLU || (long long)p.nb1 * p.nb2 != 1) return SASPA_ERANGE;
+    if (p.dtype != SASPA_HALF || p.act == SASPA_ACT_GEGLU || (long long)p.nb1 * p.nb2 != 1) return SASPA_ERANGE;
     if (p.gn_unit < 2 || p.gn_unit > 16 || (p.gn_unit & 1) || (80 % p.gn_unit) != 0 || (p.N % 160) != 0) return SASPA_ERANGE;
     if ((p.ldo % 8) != 0 || (p.residual && (p.ldr % 8) != 0)) return SASPA_ERANGE;
   }
@@ -1274,16 +1274,16 @@ extern "C" int saspa_gemm_suggest_ksplit(const SaspaGemmParams* pp) {
   if (!pp) return 1;
   const SaspaGemmParams& p = *pp;
   if (p.M <= 0 || p.N <= 0 || p.K <= 0 || (long long)p.nb1 * p.nb2 > 1 || p.N % 4 || p.act == SASPA_ACT_GEGLU) return 1;
-  const int bk = p.dtype == SASPA_BF16 ? 64 : 32;
+  const int bk = p.dtype == SASPA_HALF ? 64 : 32;
   const int ktiles = (p.K + bk - 1) / bk;
   // one round of 128-row tiles on a pointwise layer: the wave-specialised kernel without K slices beats the wide kernel on K slices
   // ((4096, 1280, 5120): 52 vs 76 us, and no slabs) -- not beside a twin launch with long K, where two slices on the wide kernel
   // win (pair times 124 vs 146 us at (4096, 1280, 5120) + residual, tools/twin_sweep.py)
-  if (!(p.sharing && p.K >= kLongK) && !p.gn_stats && p.dtype == SASPA_BF16 && p.variant == SASPA_GEMM_AUTO && p.kh == 1 && p.kw == 1 &&
+  if (!(p.sharing && p.K >= kLongK) && !p.gn_stats && p.dtype == SASPA_HALF && p.variant == SASPA_GEMM_AUTO && p.kh == 1 && p.kw == 1 &&
       ws_one_round(tiles128(p)) && saspa_gemm_ws_eligible(p))
     return 1;
   const int fn = wide_fn(p);
-  if (p.dtype == SASPA_BF16 && p.K >= kLongK && fn && saspa_gemm_pp_eligible(p)) {
+  if (p.dtype == SASPA_HALF && p.K >= kLongK && fn && saspa_gemm_pp_eligible(p)) {
     const long long t = wide_tiles(p, fn);
     if (t >= kWideSplitMinTiles) {
       // a twin launch beside it (sharing) counts on half the chip; one slice only where plan_gemm really takes the wide kernel
@@ -1311,7 +1311,7 @@ extern "C" int saspa_gemm_as_auto(const SaspaGemmParams* pp) { return pp && as_a
 int saspa_gemm_npart8(const SaspaGemmParams& p, int BM, int BN, int G, int tiles) {
   const int nbn = (p.N + BN - 1) / BN, nbm = (p.M + BM - 1) / BM;
   if ((long long)p.nb1 * p.nb2 != 1 || (nbn & 7) || (G & 7) || G <= 0 || tiles % G || p.N % BN) return 0;
-  const double esz = p.dtype == SASPA_BF16 ? 2.0 : 4.0;
+  const double esz = p.dtype == SASPA_HALF ? 2.0 : 4.0;
   const double a = (double)p.batch * p.hin * p.win * (p.c0 + p.c1) * esz;     // the input tensor (taps re-read from L2)
   const double w = (double)p.N * p.K * esz;
   const double l2 = 3.8 * (1 << 20);                                            // of the 4 MiB per XCD
@@ -1330,8 +1330,10 @@ int saspa_gemm_splitk_reduce(const SaspaGemmParams& p, hipStream_t s, int ksplit
   }
   long long blocks = ((long long)p.M * (p.N / 4) + 255) / 256;
   if (blocks > 4096) blocks = 4096;
-  if (p.dtype == SASPA_BF16) hipLaunchKernelGGL((splitk_reduce_kernel<bf16_t>), dim3((unsigned)blocks), dim3(256), 0, s, p, ksplit);
+  if (p.dtype == SASPA_HALF) hipLaunchKernelGGL((splitk_reduce_kernel<h16_t>), dim3((unsigned)blocks), dim3(256), 0, s, p, ksplit);
+#ifndef SASPA_HALF_F16
   else hipLaunchKernelGGL((splitk_reduce_kernel<float>), dim3((unsigned)blocks), dim3(256), 0, s, p, ksplit);
+#endif
   SASPA_CHECK_LAUNCH();
   return 0;
 }
@@ -1359,7 +1361,11 @@ extern "C" int saspa_gemm(const SaspaGemmParams* pp, void* stream) {
     case SASPA_GEMM_WS: return saspa_gemm_ws_launch(p, s);
     case SASPA_GEMM_WIDE: return saspa_gemm_pp_launch(p, s, g.ksplit, g.tile);
   }
-  if (p.dtype == SASPA_BF16) return launch_tiled<bf16_t>(p, s, g);
+  if (p.dtype == SASPA_HALF) return launch_tiled<h16_t>(p, s, g);
+#ifndef SASPA_HALF_F16       // the fp16 library holds no fp32 tiles: check_gemm refused those dtype codes
   if (p.dtype == SASPA_F32X3) return launch_tiled<f32x3_t>(p, s, g);
   return launch_tiled<float>(p, s, g);
+#else
+  return SASPA_EINVAL;
+#endif
 }

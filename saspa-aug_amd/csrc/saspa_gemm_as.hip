@@ -289,7 +289,7 @@ __global__ __launch_bounds__(512, 1) void gemm_as_kernel(const SaspaGemmParams p
       for (int j = 0; j < 4; ++j) {
         const int sx = 2 * gi + (j >> 1), nb = j & 1;
         if (abl & 2) asm volatile("" ::"v"(wf[gi % 3][j]), "v"(af[sx]));
-        else acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wf[gi % 3][j]), __builtin_bit_cast(bf16x8, af[sx]), acc[nb], 0, 0, 0);
+        else acc[nb] = MFMA_32X32X16(wf[gi % 3][j], af[sx], acc[nb]);
       }
       between(gi);
       __builtin_amdgcn_sched_barrier(0);
@@ -459,7 +459,7 @@ __global__ __launch_bounds__(512, 1) void gemm_as_kernel(const SaspaGemmParams p
 }  // namespace
 
 bool saspa_gemm_as_ok(const SaspaGemmParams& p) {
-  if (p.dtype != SASPA_BF16) return false;
+  if (p.dtype != SASPA_HALF) return false;
   if (p.kh != 1 || p.kw != 1 || p.stride != 1 || p.pad != 0 || p.upsample || p.c1 != 0 || p.a1) return false;
   if (p.c0 != AS_K || p.K != AS_K || p.lda0 % 8 || p.ldw % 8 || p.ldw < AS_K) return false;
   if ((long long)p.nb1 * p.nb2 > 1 || (p.ksplit > 1 && p.workspace) || p.gn_stats || p.rowvec || p.alpha != 1.0f) return false;

@@ -45,10 +45,10 @@
 
 namespace {
 
-typedef bf16_t T;
+typedef h16_t T;
 
 __device__ __forceinline__ void mma(const u32x4& wf, const u32x4& xf, f32x4& acc) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf), __builtin_bit_cast(bf16x8, xf), acc, 0, 0, 0);
+  acc = MFMA_16X16X32(wf, xf, acc);
 }
 
 template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
@@ -322,9 +322,9 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const SaspaGemmParams p, c
   int dbgv[4] = {0, 0, 0, 0};                          // ablation bit 32 only
 #if defined(SASPA_GEMM_ABLATION) || SASPA_PP_CT_ABL
 #pragma unroll
-  for (int j = 0; j < FN; ++j) wb[j][0] = wb[j][1] = u32x4{(unsigned)j, 0u, 0x3f803f80u, 0x3f803f80u};
+  for (int j = 0; j < FN; ++j) wb[j][0] = wb[j][1] = u32x4{(unsigned)j, 0u, kHalfOnes2, kHalfOnes2};
 #pragma unroll
-  for (int i = 0; i < 2; ++i) xa[i][0] = xa[i][1] = u32x4{(unsigned)i, 1u, 0x3f803f80u, 0x3f803f80u};
+  for (int i = 0; i < 2; ++i) xa[i][0] = xa[i][1] = u32x4{(unsigned)i, 1u, kHalfOnes2, kHalfOnes2};
 #endif
 
   // one phase of the tile in `cur`: fragment reads of slice P (+ all B fragments in phase 0), DMA issue of
@@ -923,10 +923,10 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const SaspaGemmParams p, c
             for (int r = grg; r < nrows; r += rgs) {
               const uint32_t* src = reinterpret_cast<const uint32_t*>(ctg + r * CP + gu * gunit);
               for (int j = 0; j < gunit; j += 2) {
-                // two bf16 per dword: v_dot2c_f32_bf16 against (1, 1) and against itself (as gn_tile_stats)
-                const bf16x2_t w2 = __builtin_bit_cast(bf16x2_t, src[j >> 1]);
-                gsm = __builtin_amdgcn_fdot2_f32_bf16(w2, __builtin_bit_cast(bf16x2_t, 0x3F803F80u), gsm, false);
-                gsq = __builtin_amdgcn_fdot2_f32_bf16(w2, w2, gsq, false);
+                // two elements per dword: one dot2 against (1, 1) and one against itself (as gn_tile_stats)
+                const uint32_t w2 = src[j >> 1];
+                gsm = half_dot2(w2, kHalfOnes2, gsm);
+                gsq = half_dot2(w2, w2, gsq);
               }
             }
           }
@@ -1008,7 +1008,7 @@ int launch_pp(const SaspaGemmParams& p, hipStream_t s, int ksplit) {
 
 bool saspa_gemm_pp_eligible(const SaspaGemmParams& p) {
   const int ctot = p.c0 + p.c1;
-  if (p.dtype != SASPA_BF16) return false;
+  if (p.dtype != SASPA_HALF) return false;
   // fused GEGLU: whole 320-column tiles of the per-160 packing, no residual, no K slices (the caller passes ksplit 1)
   if (p.act == SASPA_ACT_GEGLU && ((p.N % 320) != 0 || p.residual || p.alpha != 1.0f)) return false;
   if ((ctot % 64) != 0 || (p.c1 > 0 && (p.c0 % 64) != 0)) return false;        // a K-tile lies in one tap of one source

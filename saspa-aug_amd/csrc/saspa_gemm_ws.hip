@@ -36,7 +36,7 @@
 
 namespace {
 
-typedef bf16_t T;
+typedef h16_t T;
 
 template <int WN, bool PW, bool GEGLU>
 __global__ __launch_bounds__(768) void gemm_ws_kernel(const SaspaGemmParams p, const int ntiles_abl) {
@@ -159,8 +159,7 @@ __global__ __launch_bounds__(768) void gemm_ws_kernel(const SaspaGemmParams p, c
         for (int i = 0; i < WM; ++i)
 #pragma unroll
           for (int j = 0; j < WN; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wb[j]), __builtin_bit_cast(bf16x8, xa[i]),
-                                                                acc[i][j], 0, 0, 0);
+            acc[i][j] = MFMA_16X16X32(wb[j], xa[i], acc[i][j]);
       }
       if (++kt == nk) {
         // ---- end of output tile ti: park it (bias + row vector, alpha, bf16) in the staging area ----
@@ -395,7 +394,7 @@ __global__ __launch_bounds__(768) void gemm_ws_kernel(const SaspaGemmParams p, c
           }
           if (res) {
             float bq[8];
-            Elem<bf16_t>::load_chunk(res + (long long)m * p.ldr + n, bq);
+            Elem<h16_t>::load_chunk(res + (long long)m * p.ldr + n, bq);
 #pragma unroll
             for (int e = 0; e < 8; ++e) a[e] += bq[e];
           }
@@ -452,7 +451,7 @@ __global__ __launch_bounds__(768) void gemm_ws_kernel(const SaspaGemmParams p, c
 
 bool saspa_gemm_ws_eligible(const SaspaGemmParams& p) {
   const int ctot = p.c0 + p.c1;
-  if (p.dtype != SASPA_BF16 || (long long)p.nb1 * p.nb2 != 1 || p.upsample) return false;
+  if (p.dtype != SASPA_HALF || (long long)p.nb1 * p.nb2 != 1 || p.upsample) return false;
   if ((ctot % 64) != 0 || (p.c1 > 0 && (p.c0 % 64) != 0)) return false;
   if ((p.N % 8) != 0 || (p.ldo % 8) != 0 || (p.residual && (p.ldr % 8) != 0)) return false;
   if (p.act == SASPA_ACT_GEGLU && (p.N % ((p.N % 160) == 0 ? 160 : 128)) != 0) return false;

@@ -274,6 +274,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const SaspaGroupNormParam
   for (; px < pend; px += rows) one(px);
 }
 
+#ifndef SASPA_HALF_F16   // the fp8 quantiser reads bf16 activations: default library only (fp8 is not combined with fp16 compute)
 // ---- GroupNorm(+SiLU) quantised to MX-fp8 (saspa_groupnorm_quant_mxfp8) ---------------------------------------------------
 // grid = (nblk, batch), the block's items are [blockIdx.x * ipb, +ipb) of image b's hw x C/8 chunks in pixel-major order.  The
 // apply pass's prologue (the same mean / rstd per group), then scale / shift of every channel into LDS; one chunk of 8 channels
@@ -328,9 +329,9 @@ __global__ __launch_bounds__(256) void gn_quant_mx_kernel(const SaspaGroupNormPa
       if (i0 + u * 256 < end) {
         const int ch = cku[u] * 8;
         const long long pix = (long long)b * p.hw + pxu[u];
-        const bf16_t* src = ch < p.c0 ? reinterpret_cast<const bf16_t*>(p.x0) + pix * p.ldx0 + ch
-                                       : reinterpret_cast<const bf16_t*>(p.x1) + pix * p.ldx1 + (ch - p.c0);
-        Elem<bf16_t>::load_chunk(src, v[u]);
+        const h16_t* src = ch < p.c0 ? reinterpret_cast<const h16_t*>(p.x0) + pix * p.ldx0 + ch
+                                       : reinterpret_cast<const h16_t*>(p.x1) + pix * p.ldx1 + (ch - p.c0);
+        Elem<h16_t>::load_chunk(src, v[u]);
       } else {
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[u][j] = 0.f;
@@ -369,6 +370,8 @@ __global__ __launch_bounds__(256) void gn_quant_mx_kernel(const SaspaGroupNormPa
     }
   }
 }
+
+#endif  // !SASPA_HALF_F16
 
 // ---- LayerNorm: LPR lanes per row (64 / LPR rows per wave), NCH chunks of 8 channels per lane, two-pass in registers.
 // Narrow rows (320 / 640 channels = 40 / 80 chunks) take 16 / 32 lanes x 3 chunks, so a wave has 4 / 2 rows' loads in flight
@@ -464,7 +467,7 @@ int check_gn(const SaspaGroupNormParams& p) {
   }
   if (p.batch <= 0 || p.hw <= 0 || p.groups <= 0 || (p.nsplit <= 0 && !p.stats0) || p.c0 <= 0 || p.c1 < 0) return SASPA_EINVAL;
   if (p.c1 > 0 && !p.x1) return SASPA_EINVAL;
-  if (p.dtype != SASPA_BF16 && p.dtype != SASPA_F32) return SASPA_EINVAL;
+  if (p.dtype != SASPA_HALF && !(kServesF32 && p.dtype == SASPA_F32)) return SASPA_EINVAL;
   const int C = p.c0 + p.c1;
   if (p.c0 % 8 || p.c1 % 8 || p.ldx0 % 8 || (p.c1 > 0 && p.ldx1 % 8)) return SASPA_EALIGN;
   if (C % p.groups || p.groups > 256) return SASPA_ERANGE;
@@ -610,8 +613,7 @@ __global__ __launch_bounds__(256) void splitk_gn_kernel(const SaspaGemmParams gp
       for (int j = 0; j < 4; ++j) {
         float x = t[j] * gp.alpha;
         if constexpr (sizeof(T) == 2) {            // the value the unfused path stores (and its GroupNorm reads back): bf16
-          const unsigned w2 = pack2(x, 0.f);
-          x = __builtin_bit_cast(float, w2 << 16);
+          x = h16_bits_to_f32(pack2(x, 0.f));
         }
         v[i][j] = x;
         sm += x;
@@ -673,13 +675,13 @@ extern "C" int saspa_groupnorm_onepass(const SaspaGroupNormParams* pp, void* str
   const SaspaGroupNormParams& p = *pp;
   if (!p.x0 || !p.gamma || !p.beta || !p.y || p.batch <= 0 || p.hw <= 0 || p.groups <= 0) return SASPA_EINVAL;
   if (p.c1 > 0 && !p.x1) return SASPA_EINVAL;
-  if (p.dtype != SASPA_BF16 && p.dtype != SASPA_F32) return SASPA_EINVAL;
+  if (p.dtype != SASPA_HALF && !(kServesF32 && p.dtype == SASPA_F32)) return SASPA_EINVAL;
   if (p.c0 % 8 || p.c1 % 8 || p.ldx0 % 8 || (p.c1 > 0 && p.ldx1 % 8) || p.ldy % 8) return SASPA_EALIGN;
   if (!aligned16(p.x0) || (p.x1 && !aligned16(p.x1)) || !aligned16(p.y)) return SASPA_EALIGN;
   if (p.batch > 65535 || !saspa_groupnorm_onepass_eligible(pp)) return SASPA_ERANGE;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   dim3 grid(p.groups, p.batch);
-  if (p.dtype == SASPA_BF16) hipLaunchKernelGGL(gn_onepass_kernel<bf16_t>, grid, dim3(256), 0, s, p);
+  if (p.dtype == SASPA_HALF) hipLaunchKernelGGL(gn_onepass_kernel<h16_t>, grid, dim3(256), 0, s, p);
   else hipLaunchKernelGGL(gn_onepass_kernel<float>, grid, dim3(256), 0, s, p);
   SASPA_CHECK_LAUNCH();
   return 0;
@@ -694,7 +696,7 @@ extern "C" int saspa_splitk_groupnorm_eligible(const SaspaGemmParams* gp, const 
   if (cpg % 4 || (long long)p.hw * cpg > 256LL * SKGN_ITEMS * 4 || (long long)g.M * g.N >= (1LL << 31)) return 0;
   if (g.residual || g.act != SASPA_ACT_NONE || (long long)g.nb1 * g.nb2 > 1 || g.gn_stats) return 0;
   if ((long long)p.batch * p.hw != g.M || p.hw != g.hout * g.wout || p.c0 != g.N || p.c1 != 0) return 0;
-  if (g.dtype != SASPA_BF16 && g.dtype != SASPA_F32) return 0;
+  if (g.dtype != SASPA_HALF && !(kServesF32 && g.dtype == SASPA_F32)) return 0;
   return 1;
 }
 
@@ -713,7 +715,7 @@ extern "C" int saspa_splitk_groupnorm(const SaspaGemmParams* gp, const SaspaGrou
   if (p.batch > 65535) return SASPA_ERANGE;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   dim3 grid(p.groups, p.batch);
-  if (g.dtype == SASPA_BF16) hipLaunchKernelGGL(splitk_gn_kernel<bf16_t>, grid, dim3(256), 0, s, g, p);
+  if (g.dtype == SASPA_HALF) hipLaunchKernelGGL(splitk_gn_kernel<h16_t>, grid, dim3(256), 0, s, g, p);
   else hipLaunchKernelGGL(splitk_gn_kernel<float>, grid, dim3(256), 0, s, g, p);
   SASPA_CHECK_LAUNCH();
   return 0;
@@ -730,7 +732,7 @@ extern "C" int saspa_groupnorm_stats(const SaspaGroupNormParams* pp, void* strea
   const GnGeom ge = gn_geometry((p.c0 + p.c1) / 8);
   const int pps = (p.hw + p.nsplit - 1) / p.nsplit;
   dim3 grid(p.nsplit, p.batch, ge.slabs);
-  if (p.dtype == SASPA_BF16) hipLaunchKernelGGL(gn_partial_kernel<bf16_t>, grid, dim3(256), 0, s, p, ge.cxw, pps);
+  if (p.dtype == SASPA_HALF) hipLaunchKernelGGL(gn_partial_kernel<h16_t>, grid, dim3(256), 0, s, p, ge.cxw, pps);
   else hipLaunchKernelGGL(gn_partial_kernel<float>, grid, dim3(256), 0, s, p, ge.cxw, pps);
   SASPA_CHECK_LAUNCH();
   return 0;
@@ -752,19 +754,20 @@ extern "C" int saspa_groupnorm_apply(const SaspaGroupNormParams* pp, void* strea
   const int ppb = (p.hw + nblk - 1) / nblk;
   nblk = (p.hw + ppb - 1) / ppb;
   dim3 grid(nblk, p.batch, ge.slabs);
-  if (p.dtype == SASPA_BF16) hipLaunchKernelGGL(gn_apply_kernel<bf16_t>, grid, dim3(256), 0, s, p, ge.cxw, ge.slabs, ppb);
+  if (p.dtype == SASPA_HALF) hipLaunchKernelGGL(gn_apply_kernel<h16_t>, grid, dim3(256), 0, s, p, ge.cxw, ge.slabs, ppb);
   else hipLaunchKernelGGL(gn_apply_kernel<float>, grid, dim3(256), 0, s, p, ge.cxw, ge.slabs, ppb);
   SASPA_CHECK_LAUNCH();
   return 0;
 }
 
+#ifndef SASPA_HALF_F16
 extern "C" int saspa_groupnorm_quant_mxfp8(const SaspaGroupNormParams* pp, void* q, int ldq, void* qs, int ldqs, void* stream) {
   if (!pp || !q || !qs) return SASPA_EINVAL;
   const SaspaGroupNormParams& p = *pp;
   if (int e = check_gn(p)) return e;
   if (p.act != SASPA_ACT_NONE && p.act != SASPA_ACT_SILU) return SASPA_EINVAL;
   const int C = p.c0 + p.c1;
-  if (p.dtype != SASPA_BF16 || C % 32 || C > kQuantMaxC) return SASPA_ERANGE;
+  if (p.dtype != SASPA_HALF || C % 32 || C > kQuantMaxC) return SASPA_ERANGE;
   if (ldq % 16 || ldq < C || !aligned16(q) || ldqs < C / 32) return SASPA_EALIGN;
   const int C8 = C / 8;
   if ((long long)p.hw * C8 >= (1ll << 30)) return SASPA_ERANGE;
@@ -782,15 +785,17 @@ extern "C" int saspa_groupnorm_quant_mxfp8(const SaspaGroupNormParams* pp, void*
   return 0;
 }
 
+#endif
+
 extern "C" int saspa_layernorm(int dtype, const void* x, int ldx, void* y, int ldy, long long rows, int C,
                                const float* gamma, const float* beta, float eps, void* stream) {
   if (!x || !y || !gamma || !beta || rows <= 0 || C <= 0) return SASPA_EINVAL;
   if (C % 8 || ldx % 8 || ldy % 8 || !aligned16(x) || !aligned16(y)) return SASPA_EALIGN;
   if (C > 2048) return SASPA_ERANGE;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == SASPA_BF16)
-    launch_layernorm<bf16_t>(s, (const bf16_t*)x, ldx, (bf16_t*)y, ldy, rows, C, gamma, beta, eps);
-  else if (dtype == SASPA_F32)
+  if (dtype == SASPA_HALF)
+    launch_layernorm<h16_t>(s, (const h16_t*)x, ldx, (h16_t*)y, ldy, rows, C, gamma, beta, eps);
+  else if (dtype == SASPA_F32 && kServesF32)
     launch_layernorm<float>(s, (const float*)x, ldx, (float*)y, ldy, rows, C, gamma, beta, eps);
   else
     return SASPA_EINVAL;

@@ -64,7 +64,7 @@ __device__ __forceinline__ void xunpack_opaque(const u32x4& a, float* v) {
 }
 
 __device__ __forceinline__ f32x16 xmfma(const u32x4& a, const u32x4& b, const f32x16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+  return MFMA_32X32X16(a, b, c);
 }
 
 __global__ __launch_bounds__(512, 1) void xattn_block_kernel(const SaspaXattnBlockParams p, const int abl) {

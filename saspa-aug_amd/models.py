@@ -29,6 +29,11 @@ from . import weights as W
 SILU = ops.ACT_SILU
 
 
+def _is_half(dtype):
+    """The 16-bit compute type (bf16, or fp16 on the fp16 build of the kernels): every fused path is taken for both."""
+    return dtype in (torch.bfloat16, torch.float16)
+
+
 def _f32(t, dev):
     return t.detach().to(dev, torch.float32).contiguous()
 
@@ -161,7 +166,7 @@ def attention_core(q, k, vt, heads, nq, nk, causal=False, prescaled=False, v_row
     d = c // heads
     out = torch.empty((b, nq, c), device=q.device, dtype=q.dtype)
     scale = d ** -0.5
-    if q.dtype == torch.bfloat16 and d <= 160:
+    if ops.is_half(q) and d <= 160:
         return ops.flash_attn(q, k, vt, out, heads, d, nq, nk, scale, causal, prescaled=prescaled, v_rowmajor=v_rowmajor)
     assert not prescaled and not v_rowmajor, "prescaled queries / row-major V exist for the flash path only"
     lds = ops.round8(nk)
@@ -198,6 +203,8 @@ class _Net:
         self.cfg, self.dev, self.dtype = cfg, dev, dtype
         # fp8: the LayerNorm-fed projections of the transformer blocks (attn2.to_q, ff.net.0.proj) run W8A8 on
         # saspa_gemm_fp8 (bf16 networks only; blocks whose width is not a multiple of 128 stay bf16)
+        if fp8 and dtype == torch.float16:
+            raise ValueError("fp8 projections quantise bf16 activations: fp8 together with fp16 compute is not supported")
         self.fp8 = bool(fp8) and dtype == torch.bfloat16
         # fp8_conv (needs fp8): ResnetBlock2D conv1 / conv2 as quantising GroupNorm -> MX-fp8 conv (saspa_groupnorm_quant_mxfp8 +
         # saspa_conv3x3_mxfp8) where the library accepts the shape and mxfp8_conv_takes(M, N); weights quantised at pack time
@@ -213,7 +220,7 @@ class _Net:
         self.temb_tables = {}
         # GroupNorm statistics out of the producers' epilogues (ops.conv(..., gn_unit=...)): every GroupNorm of the network
         # has groups of a multiple of block_out[0] / groups channels (10 for SD-1.5 / SDXL), also across a skip concat
-        self.gn_unit = cfg["block_out"][0] // cfg["groups"] if dtype == torch.bfloat16 else None
+        self.gn_unit = cfg["block_out"][0] // cfg["groups"] if _is_half(dtype) else None
 
     # ---- packing helpers ----
     def _pack_resnet(self, pfx, split=None):
@@ -251,7 +258,7 @@ class _Net:
                 pk.norm(f"{t}.{n}")
             # bf16 networks with flash-sized heads: softmax scale * log2(e) folded into the to_q rows
             c = pk.sd[t + ".norm1.weight"].numel()
-            qs = (c // heads) ** -0.5 * ATTN_LOG2E if (self.dtype == torch.bfloat16 and c // heads <= 160) else None
+            qs = (c // heads) ** -0.5 * ATTN_LOG2E if (_is_half(self.dtype) and c // heads <= 160) else None
             pk.attn(t + ".attn1", True, qscale=qs)
             pk.attn(t + ".attn2", False, qscale=qs)
             if qs is not None:
@@ -263,7 +270,7 @@ class _Net:
                                         pk.sd[t + ".attn2.to_out.0.bias"].float())
                 self.p[t + ".attn2.xw"], self.p[t + ".attn2.xb"] = xw.to(self.dev, self.dtype), _f32(xb, self.dev)
                 self.xattn_blocks.add(t)
-            if self.dtype == torch.bfloat16 and c // heads <= 160 and (t + ".attn1.qk.b") not in self.p:
+            if _is_half(self.dtype) and c // heads <= 160 and (t + ".attn1.qk.b") not in self.p:
                 # [to_q; to_k; to_v] in one matrix: at level 0 for the A-stationary kernel (LayerNorm fused, V^T written
                 # transposed by the same launch: ops.linear(ln=, out_t=)), elsewhere for ONE projection launch whose V
                 # columns the flash kernel reads row-major (SASPA_ATTN_V_ROWMAJOR) -- no transposed value projection
@@ -276,7 +283,7 @@ class _Net:
                     # views of the fused buffer (0.9 GB less for the 90 SDXL blocks)
                     self.p[t + ".attn1.qk.w"], self.p[t + ".attn1.v.w"] = wqkv[:2 * c], wqkv[2 * c:]
             packed = W.pack_geglu(pk.sd[t + ".ff.net.0.proj.weight"], pk.sd[t + ".ff.net.0.proj.bias"]) \
-                if self.dtype == torch.bfloat16 else None
+                if _is_half(self.dtype) else None
             if packed is not None:          # bf16: GEGLU fused into the projection's epilogue
                 self.p[t + ".ff.net.0.proj.w"] = packed[0].to(self.dev, self.dtype)
                 self.p[t + ".ff.net.0.proj.b"] = _f32(packed[1], self.dev)
@@ -775,7 +782,7 @@ class VAEDecoder:
         an operand with 32-bit byte offsets (< 2 GiB): the widest full-resolution activation (block_out[1] channels)
         bounds the images per launch sequence -- 8 at 512x512 in bf16, 3 in fp32 (upcast VAE), 1 at 1024x1024 fp32."""
         b, h, w, _ = z.shape
-        esz = 2 if self.dtype == torch.bfloat16 else 4
+        esz = 2 if _is_half(self.dtype) else 4
         per_img = 64 * h * w * self.cfg["block_out"][min(1, len(self.cfg["block_out"]) - 1)] * esz
         chunk = max(1, ((1 << 31) - 1) // per_img)
         with ops.f32_gemm_mode(self.f32_gemm):

@@ -78,8 +78,16 @@ class _RecordingLib:
         return wrapped
 
 
-def _L():
-    lib = _lib.load()
+def is_half(t):
+    """The 16-bit compute type: bf16 (libsaspa_hip.so) or fp16 (libsaspa_hip_f16.so) -- the same kernels, layouts and fused paths."""
+    return t.dtype == torch.bfloat16 or t.dtype == torch.float16
+
+
+def _L(t=None):
+    """The library that serves the activation tensor `t` (or the dtype code of a filled-in parameter struct): fp16 goes to the fp16
+    build, everything else -- fp32 always -- to the default library."""
+    f16 = t is not None and (t.dtype == torch.float16 if isinstance(t, torch.Tensor) else int(t) == _lib.SASPA_F16)
+    lib = _lib.load_f16() if f16 else _lib.load()
     return lib if _RECORDER is None else _RecordingLib(lib)
 
 
@@ -95,7 +103,7 @@ def _meta_kernel(p, meta):
     (saspa_gemm_which) -- to the launch's meta tuple, so that per-launch timings can be grouped by the kernel that really ran."""
     if _RECORDER is None or meta is None:
         return meta
-    w = int(_L().saspa_gemm_which(C.byref(p)))
+    w = int(_L(p.dtype).saspa_gemm_which(C.byref(p)))
     return tuple(meta) + ((w & 0xff, w >> 8) if w > 0 else (0, 1))
 
 
@@ -123,6 +131,8 @@ def _probe_launch(kind, flops, call, meta=None):
 def _dt(t):
     if t.dtype == torch.bfloat16:
         return _lib.SASPA_BF16
+    if t.dtype == torch.float16:
+        return _lib.SASPA_F16
     if t.dtype == torch.float32:
         return _lib.SASPA_F32
     raise TypeError(f"unsupported activation dtype {t.dtype}")
@@ -165,6 +175,14 @@ def _check_dev(*ts):
     for t in ts:
         if t is not None and not t.is_cuda:
             raise RuntimeError("saspa_aug_amd ops run on the GPU only (tensor is on %s)" % t.device)
+
+
+def _same_dtype(what, x, **ts):
+    """Operands of one launch share its element type: the library reads them all as `_dt(x)`, and with two 16-bit types a mismatch
+    would no longer show as a size error."""
+    for name, t in ts.items():
+        if t is not None and t.dtype != x.dtype:
+            raise ValueError(f"{what}: {name} is {t.dtype}, the activations are {x.dtype}")
 
 
 _SIDE_STREAMS = {}
@@ -254,7 +272,7 @@ def _set_splitk(p, m, n, k, t, force=None):
     filled in) or the caller's override; allocates the fp32 slab workspace."""
     p.ksplit, p.workspace = 1, None
     p.sharing = 1 if _TWIN[0] else 0
-    ks = _L().saspa_gemm_suggest_ksplit(C.byref(p)) if force is None else int(force)
+    ks = _L(t).saspa_gemm_suggest_ksplit(C.byref(p)) if force is None else int(force)
     if ks > 1:
         ws = torch.empty((ks * m * n,), device=t.device, dtype=torch.float32)
         p.ksplit, p.workspace = ks, C.c_void_p(ws.data_ptr())
@@ -288,7 +306,7 @@ def _gn_stats_for(p, out, gn_unit, b, hw, n):
     shape allows it: bf16, whole 128-row blocks per image, whole 160-column tiles, dense output rows."""
     if hasattr(out, "saspa_gn"):
         del out.saspa_gn                  # a reused `out=`: statistics of an earlier launch must not outlive this one
-    if not gn_unit or not gn_fusion_enabled() or out.dtype != torch.bfloat16:
+    if not gn_unit or not gn_fusion_enabled() or not is_half(out):
         return None
     if hw % 128 or n % 160 or 80 % gn_unit or gn_unit % 2 or gn_unit > 16 or out.shape[-1] != n or p.ldo % 8 or (p.residual and p.ldr % 8):
         return None
@@ -313,7 +331,7 @@ def conv(x, w, bias=None, *, kh=1, kw=1, stride=1, pad=0, upsample=False, x2=Non
     (the 8x8 / 16x16 levels) the reduce launch, the statistics and the apply pass are one launch (saspa_splitk_groupnorm, ABI
     18: the un-normalised output is never written); otherwise the conv runs as usual and `groupnorm` follows."""
     _check_dev(x, w, bias, x2, rowvec, residual, out)
-    lib = _L()
+    lib = _L(x)
     b, h, wd, c0 = x.shape
     c1 = 0 if x2 is None else x2.shape[3]
     hv, wv = (2 * h, 2 * wd) if upsample else (h, wd)
@@ -369,7 +387,7 @@ def conv(x, w, bias=None, *, kh=1, kw=1, stride=1, pad=0, upsample=False, x2=Non
     # a level-0 pointwise layer the A-stationary kernel takes on whole rounds (Transformer2DModel.proj_out): that kernel has no
     # statistics epilogue, and A-stationary + the consumer's own statistics pass (27 + 12 us) beats the tiled kernel with the
     # statistics in its epilogue (53 us); SASPA_GEMM_AS_OVER_STATS=0 keeps the statistics
-    if gn_unit and kh == 1 and kw == 1 and c1 == 0 and x.dtype == torch.bfloat16 and _as_over_stats() and \
+    if gn_unit and kh == 1 and kw == 1 and c1 == 0 and is_half(x) and _as_over_stats() and \
             lib.saspa_gemm_as_auto(C.byref(p)) == 1:
         gn_unit = None
     meta = (p.M, p.N, p.K, kh, stride, int(upsample), c1 > 0, residual is not None, n // 2 if act == ACT_GEGLU else n)
@@ -572,7 +590,7 @@ def _linear_params(x2, w, bias, r2, o2, alpha, act, rowvec, variant, m, n, k):
 def linear_ln_fusable(x, w, *, act=ACT_NONE, n_out=None):
     """Non-zero (2) if `linear(x, w, ..., ln=...)` / `out_t=` can run: the A-stationary kernel takes the problem
     (saspa_gemm_as_eligible: bf16, K = 320, N % 64 == 0, >= 192 blocks of 256 rows).  Use it as a boolean."""
-    if not x.is_cuda or x.dtype != torch.bfloat16:
+    if not x.is_cuda or not is_half(x):
         return 0
     k = x.shape[-1]
     x2 = x.reshape(-1, k) if x.dim() != 2 else x
@@ -580,7 +598,7 @@ def linear_ln_fusable(x, w, *, act=ACT_NONE, n_out=None):
     nc = (n // 2 if act == ACT_GEGLU else n) if n_out is None else n_out
     p = _linear_params(x2, w, None, None, x2, 1.0, act, None, 0, m, n, k)
     p.ldo = round8(nc)                    # the output a call would allocate (only its pitch / alignment are looked at)
-    return int(_L().saspa_gemm_as_eligible(C.byref(p)))
+    return int(_L(x).saspa_gemm_as_eligible(C.byref(p)))
 
 
 def linear(x, w, bias=None, *, residual=None, alpha=1.0, act=ACT_NONE, out=None, rowvec=None, variant=0, ksplit=None,
@@ -591,7 +609,8 @@ def linear(x, w, bias=None, *, residual=None, alpha=1.0, act=ACT_NONE, out=None,
     out_t [B, N - n_split, ld] with n_split, rows_per_batch: output columns >= n_split are written transposed per batch of
     rows_per_batch rows (the V^T operand of flash_attn next to Q | K); the returned tensor then has n_split columns."""
     _check_dev(x, w, bias, residual, out, out_t)
-    lib = _L()
+    _same_dtype("linear", x, w=w, residual=residual, out=out)
+    lib = _L(x)
     k = x.shape[-1]
     x2 = x.reshape(-1, k) if x.dim() != 2 else x
     m = x2.shape[0]
@@ -630,11 +649,12 @@ def xattn_block(x, ln, w, bias, kf, vf, nk, rows_per_sample, residual=None, out=
     out = residual + to_out(softmax(to_q(LayerNorm(x)) K^T) V) + bias.  x [..., 320] bf16 (uniform row pitch), ln = (gamma, beta,
     eps), w / bias from weights.pack_xattn_w, kf / vf [B, ...] from weights.xattn_kv_fragments, residual defaults to x."""
     _check_dev(x, w, bias, kf, vf, residual, out)
-    lib = _L()
+    _same_dtype("xattn_block", x, w=w, kf=kf, vf=vf, residual=residual, out=out)
+    lib = _L(x)
     c = x.shape[-1]
     x2 = x.reshape(-1, c) if x.dim() != 2 else x
     m = x2.shape[0]
-    if x.dtype != torch.bfloat16 or c != 320:
+    if not is_half(x) or c != 320:
         raise ValueError("xattn_block: bf16 rows of 320 channels")
     r2 = x2 if residual is None else (residual.reshape(-1, c) if residual.dim() != 2 else residual)
     if out is None:
@@ -666,7 +686,8 @@ def gemm_batched(a, lda, sa, w, ldw, sw, out, ldo, so, m, n, k, nb1, nb2, alpha=
     """Raw batched GEMM out[z] = act(alpha * a[z] @ w[z]^T) (+ residual[z], same batch strides as out); s* = (stride1,
     stride2) in elements.  ``a``/``w``/``out``/``residual`` are tensors whose data_ptr is the z=0 origin."""
     _check_dev(a, w, out, residual)
-    lib = _L()
+    _same_dtype("gemm_batched", a, w=w, out=out, residual=residual)
+    lib = _L(a)
     p = _lib.GemmParams()
     p.dtype = _gemm_dt(a)
     p.a0, p.a1, p.c0, p.c1, p.lda0, p.lda1 = _ptr(a), None, k, 0, lda, 0
@@ -709,11 +730,11 @@ def _ff_params(x, ln, w1p, b1p, w2f, b2, residual, out):
 
 def ff_block_eligible(x, w1p, w2f):
     """Can `ff_block` take these tokens (bf16, 320 channels, rows % 128 == 0 ...)?  Host-side, launches nothing."""
-    if not x.is_cuda or x.dtype != torch.bfloat16 or x.shape[-1] != 320 or w1p.dtype != torch.bfloat16 or w2f.dtype != torch.bfloat16:
+    if not x.is_cuda or not is_half(x) or x.shape[-1] != 320 or w1p.dtype != x.dtype or w2f.dtype != x.dtype:
         return False
     p, x2, _, m, _ = _ff_params(x, None, w1p, w1p, w2f, w1p, None, None)
     p.out, p.ldo = p.x, p.ldx
-    return bool(_lib.load().saspa_ff_block_eligible(C.byref(p)))
+    return bool(_L(x).saspa_ff_block_eligible(C.byref(p)))
 
 
 def ff_block(x, ln, w1p, b1p, w2f, b2, residual=None, out=None):
@@ -721,7 +742,7 @@ def ff_block(x, ln, w1p, b1p, w2f, b2, residual=None, out=None):
     out = residual + W2 (v * gelu(g)) + b2, [v ; g] = W1 LayerNorm(x) + b1.  x [..., 320] bf16 (uniform row pitch), ln = (gamma, beta,
     eps) or None, w1p / b1p / w2f / b2 from weights.pack_ff_block (bf16 / fp32 / bf16 / fp32), residual defaults to x."""
     _check_dev(x, w1p, b1p, w2f, b2, residual, out)
-    if x.dtype != torch.bfloat16 or w1p.dtype != torch.bfloat16 or w2f.dtype != torch.bfloat16:
+    if not is_half(x) or w1p.dtype != x.dtype or w2f.dtype != x.dtype:
         raise TypeError("ff_block: bf16 activations / weights")
     if out is None:
         out = torch.empty(x.shape, device=x.device, dtype=x.dtype)
@@ -729,7 +750,7 @@ def ff_block(x, ln, w1p, b1p, w2f, b2, residual=None, out=None):
     f = p.F
     # algorithmic work: the two projections (2 M C 2F + 2 M F C)
     flops = 2.0 * m * c * 2 * f + 2.0 * m * f * c
-    _launch("gemm", flops, lambda: _lib.check(_L().saspa_ff_block(C.byref(p), _stream()), "saspa_ff_block"),
+    _launch("gemm", flops, lambda: _lib.check(_L(x).saspa_ff_block(C.byref(p), _stream()), "saspa_ff_block"),
             (m, 3 * f, c, 0, 1, 0, False, True, c) + ((GEMM_FAMILY_FF_BLOCK, 1) if _RECORDER is not None else ()))
     return out
 
@@ -741,8 +762,9 @@ def flash_attn(q, k, vt, out, heads, d, nq, nk, scale, causal=False, prescaled=F
     v_rowmajor: `vt` is V itself, [B, nk, >=heads*d] like k (a view into a fused Q | K | V projection) ->
     SASPA_ATTN_V_ROWMAJOR: the kernel transposes between LDS and the MFMA, no V^T projection is needed."""
     _check_dev(q, k, vt, out)
-    lib = _L()
-    if q.dtype != torch.bfloat16:
+    _same_dtype("flash_attn", q, k=k, v=vt, out=out)
+    lib = _L(q)
+    if not is_half(q):
         raise TypeError("flash_attn is the bf16 path; fp32 uses the unfused GEMM+softmax path")
     p = _lib.AttnParams()
     p.q, p.ldq, p.sqb = _ptr(q), q.stride(1), q.stride(0)
@@ -760,7 +782,7 @@ def flash_attn(q, k, vt, out, heads, d, nq, nk, scale, causal=False, prescaled=F
 def softmax_rows(x, n, scale, causal=False, rows_per_mat=1):
     """In-place softmax(scale*x) over the first n columns of [rows, ld]; pad columns zeroed."""
     _check_dev(x)
-    lib = _L()
+    lib = _L(x)
     x2 = x.view(-1, x.shape[-1])
     _lib.check(lib.saspa_softmax_rows(_dt(x), _ptr(x2), x2.shape[0], n, x2.stride(0), float(scale), int(causal),
                                       int(rows_per_mat), _stream()), "saspa_softmax_rows")
@@ -795,7 +817,7 @@ def _epilogue_stats(x, x2, groups):
 def groupnorm(x, gamma, beta, groups, eps, act=ACT_NONE, x2=None, out=None):
     """GroupNorm(+SiLU) over channels-last x (optionally concatenated with x2) -> [B,H,W,C]."""
     _check_dev(x, gamma, beta, x2, out)
-    lib = _L()
+    lib = _L(x)
     b, h, w, c0 = x.shape
     c1 = 0 if x2 is None else x2.shape[3]
     ctot = c0 + c1
@@ -950,7 +972,7 @@ def conv3x3_mxfp8(q, qs, w8, sw, bias=None, rowvec=None, residual=None, gn_unit=
 
 def layernorm(x, gamma, beta, eps=1e-5, out=None):
     _check_dev(x, gamma, beta, out)
-    lib = _L()
+    lib = _L(x)
     c = x.shape[-1]
     x2 = x.reshape(-1, c)
     if out is None:
@@ -1029,7 +1051,7 @@ def fp8_pow2_scale(amax, margin=16.0):
 def geglu(x, out=None):
     """x: [..., 2F] -> [..., F] = x[..., :F] * gelu_erf(x[..., F:])"""
     _check_dev(x, out)
-    lib = _L()
+    lib = _L(x)
     f = x.shape[-1] // 2
     x2 = x.reshape(-1, 2 * f)
     if out is None:
@@ -1042,7 +1064,7 @@ def geglu(x, out=None):
 
 def activation(x, act, out=None):
     _check_dev(x, out)
-    lib = _L()
+    lib = _L(x)
     c = x.shape[-1]
     x2 = x.reshape(-1, c)
     if out is None:
@@ -1184,7 +1206,7 @@ def png_deflate(images_u8):
 
 def embed_tokens(ids, tok, pos, npos):
     _check_dev(ids, tok, pos)
-    lib = _L()
+    lib = _L(tok)
     n = ids.numel()
     c = tok.shape[1]
     out = torch.empty((n, c), device=tok.device, dtype=tok.dtype)
@@ -1198,7 +1220,7 @@ def embed_tokens_ctx(ids, ctx, ctx_begin, tok, pos):
     """ids [B, ntok] prompt tokens, ctx [B, nctx, C] (or None) spliced in at `ctx_begin`
     -> [B, ntok + nctx, C] = token embeddings + position embeddings (ContextCLIPTextEmbeddings)."""
     _check_dev(ids, ctx, tok, pos)
-    lib = _L()
+    lib = _L(tok)
     b, ntok = ids.shape
     c = tok.shape[1]
     nctx = 0 if ctx is None else ctx.shape[1]
@@ -1219,7 +1241,7 @@ def cfg_plms_step(eps, x, hist, sample, nimg, hw, c, guidance, store_slot, w_cur
     """eps, x: [2*nimg, hw, 8]; hist: [4, nimg, hw, 8] history of CFG-combined outputs; sample: [nimg, hw, 8] or None.
     One PNDM/PLMS update (see saspa_cfg_plms_step); updates x (both CFG halves) and hist[store_slot] in place."""
     _check_dev(eps, x, hist, sample)
-    lib = _L()
+    lib = _L(x)
     wh = (C.c_float * 4)(*[float(v) for v in w_hist])
     _lib.check(lib.saspa_cfg_plms_step(_dt(x), _ptr(eps), _ptr(x), _ptr(hist), _ptr(sample), nimg, hw, c, 8, float(guidance),
                                        int(store_slot), float(w_cur), wh, float(coef_sample), float(coef_model), _stream()),
@@ -1230,7 +1252,7 @@ def cfg_plms_step(eps, x, hist, sample, nimg, hw, c, guidance, store_slot, w_cur
 def cfg_ddim_step(eps, x, nimg, hw, c, guidance, sa_t, s1m_t, sa_p, s1m_p):
     """eps, x: [2*nimg, hw, 8]; updates x (both CFG halves) in place."""
     _check_dev(eps, x)
-    lib = _L()
+    lib = _L(x)
     _lib.check(lib.saspa_cfg_ddim_step(_dt(x), _ptr(eps), _ptr(x), nimg, hw, c, 8, float(guidance), float(sa_t),
                                        float(s1m_t), float(sa_p), float(s1m_p), _stream()), "saspa_cfg_ddim_step")
     return x
@@ -1239,7 +1261,7 @@ def cfg_ddim_step(eps, x, nimg, hw, c, guidance, sa_t, s1m_t, sa_p, s1m_p):
 def ddim_step(eps, x, nimg, hw, c, sa_t, s1m_t, sa_p, s1m_p):
     """eps, x: [nimg, hw, 8]; DDIM update without CFG (SDXL-Turbo, guidance off), x in place."""
     _check_dev(eps, x)
-    lib = _L()
+    lib = _L(x)
     _lib.check(lib.saspa_ddim_step(_dt(x), _ptr(eps), _ptr(x), nimg, hw, c, 8, float(sa_t), float(s1m_t), float(sa_p),
                                    float(s1m_p), _stream()), "saspa_ddim_step")
     return x
@@ -1260,7 +1282,7 @@ def gather_row(table, index, dst):
 def ddim_step_dev(eps, x, nimg, hw, c, guidance, coefs, index, cfg=True):
     """(CFG +) DDIM update with the coefficients of row index[0] of the device table coefs [steps, 4]."""
     _check_dev(eps, x, coefs, index)
-    lib = _L()
+    lib = _L(x)
     if coefs.dtype != torch.float32 or coefs.dim() != 2 or coefs.shape[1] != 4 or not coefs.is_contiguous() or index.dtype != torch.int32:
         raise ValueError("ddim_step_dev: coefs fp32 [steps, 4], int32 index")
     _lib.check(lib.saspa_ddim_step_dev(_dt(x), _ptr(eps), _ptr(x), nimg, hw, c, 8, int(bool(cfg)), float(guidance), _ptr(coefs),
@@ -1273,7 +1295,7 @@ def cfg_plms_step_dev(eps, x, hist, saved, nimg, hw, c, guidance, table, index):
     _check_dev(eps, x, hist, saved, table, index)
     if table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] != 10 or not table.is_contiguous() or index.dtype != torch.int32:
         raise ValueError("cfg_plms_step_dev: table fp32 [evaluations, 10], int32 index")
-    _lib.check(_L().saspa_cfg_plms_step_dev(_dt(x), _ptr(eps), _ptr(x), _ptr(hist), _ptr(saved), nimg, hw, c, 8, float(guidance),
+    _lib.check(_L(x).saspa_cfg_plms_step_dev(_dt(x), _ptr(eps), _ptr(x), _ptr(hist), _ptr(saved), nimg, hw, c, 8, float(guidance),
                                                    _ptr(table), _ptr(index), _stream()), "saspa_cfg_plms_step_dev")
     return x
 
@@ -1286,7 +1308,7 @@ def cfg_unipc_step(eps, x, state, nimg, hw, c, guidance, row=None, table=None, i
                               or index is None or index.dtype != torch.int32):
         raise ValueError("cfg_unipc_step: table fp32 [steps, 12], int32 index")
     r = None if row is None else (C.c_float * 12)(*[float(v) for v in row])
-    _lib.check(_L().saspa_cfg_unipc_step(_dt(x), _ptr(eps), _ptr(x), _ptr(state), nimg, hw, c, 8, float(guidance), r,
+    _lib.check(_L(x).saspa_cfg_unipc_step(_dt(x), _ptr(eps), _ptr(x), _ptr(state), nimg, hw, c, 8, float(guidance), r,
                                                 _ptr(table), _ptr(index), _stream()), "saspa_cfg_unipc_step")
     return x
 
@@ -1298,7 +1320,7 @@ def unipc_step(eps, x, state, nimg, hw, c, row=None, table=None, index=None):
                               or index is None or index.dtype != torch.int32):
         raise ValueError("unipc_step: table fp32 [steps, 12], int32 index")
     r = None if row is None else (C.c_float * 12)(*[float(v) for v in row])
-    _lib.check(_L().saspa_unipc_step(_dt(x), _ptr(eps), _ptr(x), _ptr(state), nimg, hw, c, 8, r, _ptr(table), _ptr(index),
+    _lib.check(_L(x).saspa_unipc_step(_dt(x), _ptr(eps), _ptr(x), _ptr(state), nimg, hw, c, 8, r, _ptr(table), _ptr(index),
                                             _stream()), "saspa_unipc_step")
     return x
 
@@ -1324,7 +1346,7 @@ def vae_sample_noise(moments, e1, e2, scaling, sa, s1m):
     _check_dev(moments, e1, e2)
     out = torch.empty_like(moments)
     npix = moments.numel() // 8
-    _lib.check(_L().saspa_vae_sample_noise(_dt(moments), _ptr(moments.contiguous()), _ptr(e1.contiguous()), _ptr(e2.contiguous()),
+    _lib.check(_L(moments).saspa_vae_sample_noise(_dt(moments), _ptr(moments.contiguous()), _ptr(e1.contiguous()), _ptr(e2.contiguous()),
                                                   _ptr(out), npix, float(scaling), float(sa), float(s1m), _stream()),
                "saspa_vae_sample_noise")
     return out
@@ -1332,7 +1354,7 @@ def vae_sample_noise(moments, e1, e2, scaling, sa, s1m):
 
 def scale(x, s, out=None):
     _check_dev(x, out)
-    lib = _L()
+    lib = _L(x)
     if out is None:
         out = torch.empty_like(x)
     _lib.check(lib.saspa_scale(_dt(x), _ptr(x), _ptr(out), x.numel(), float(s), _stream()), "saspa_scale")
@@ -1342,9 +1364,9 @@ def scale(x, s, out=None):
 def u8_to_act(img_u8, dtype):
     """u8 [n,H,W,3] -> [n,H,W,8] in [0,1]"""
     _check_dev(img_u8)
-    lib = _L()
     n, h, w, _ = img_u8.shape
     out = torch.empty((n, h, w, 8), device=img_u8.device, dtype=dtype)
+    lib = _L(out)
     _lib.check(lib.saspa_u8_to_act(_dt(out), _ptr(img_u8), _ptr(out), n * h * w, _stream()), "saspa_u8_to_act")
     return out
 
@@ -1352,7 +1374,7 @@ def u8_to_act(img_u8, dtype):
 def act_to_u8(x):
     """[n,H,W,>=4] (3 live channels) -> u8 [n,H,W,3]"""
     _check_dev(x)
-    lib = _L()
+    lib = _L(x)
     n, h, w, _ = x.shape
     out = torch.empty((n, h, w, 3), device=x.device, dtype=torch.uint8)
     _lib.check(lib.saspa_act_to_u8(_dt(x), _ptr(x), _pitch4(x), _ptr(out), n * h * w, _stream()), "saspa_act_to_u8")

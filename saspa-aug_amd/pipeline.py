@@ -14,7 +14,10 @@ launch sequence, CFG doubles it) that run_aug and bench.py drive.
 Precision: `.to(device, torch.float16)` / `torch.bfloat16` selects the bf16 MFMA path (the
 MI355X counterpart of the reference's fp16 CUDA path; bf16 also avoids the SD-VAE fp16
 overflow); `.to(device, torch.float32)` selects the exact-fp32 MFMA path used for the
-end-to-end parity gate against the CPU oracle."""
+end-to-end parity gate against the CPU oracle.  `pipe.enable_fp16()` before `.to()` (or
+SASPA_FP16=1) makes `torch.float16` mean IEEE fp16 for the text tower, UNet, ControlNet and
+scheduler steps (the f16-MFMA build of the kernels); the VAE and the safety checker stay out
+of fp16 (`enable_fp16` docstring).  Off by default."""
 import os
 
 import numpy as np
@@ -218,6 +221,7 @@ class _StepGraph:
 
 class StableDiffusionControlNetPipeline:
     HAS_CONTROLNET = True
+    SUPPORTS_FP16 = True              # enable_fp16(): built for the SD-1.5 pipelines (the BLIP-Diffusion and SDXL subclasses refuse it)
 
     def __init__(self, state_dicts, cfgs=SD15, tokenizer=None, scheduler=None):
         self._state_dicts = state_dicts
@@ -232,6 +236,8 @@ class StableDiffusionControlNetPipeline:
         self.safety_checker = None        # built by .to() when the family ships one; assign None to disable (diffusers idiom)
         self.last_nsfw = None
         self._neg_cache = {}
+        self._fp16 = False                # enable_fp16(): fp16 compute for text tower / UNet / ControlNet / scheduler steps
+        self._fp16_vae = "bf16"
 
     # ---- construction -------------------------------------------------------------------
     @classmethod
@@ -268,12 +274,25 @@ class StableDiffusionControlNetPipeline:
             raise RuntimeError("saspa_aug_amd pipelines run on an MI355X only (no CPU path); got device %s" % device)
         if not torch.cuda.is_available():
             raise RuntimeError("no HIP device visible")
+        fp16 = self._fp16 or os.environ.get("SASPA_FP16", "0") == "1"
+        fp16_vae = self._fp16_vae if self._fp16 else os.environ.get("SASPA_FP16_VAE", "bf16")
         if dtype in (None, torch.float16, torch.bfloat16):
             cdt, ndt = torch.bfloat16, torch.float16   # noise is drawn in the reference's pipeline dtype
+            if fp16:                                   # opt-in (enable_fp16 / SASPA_FP16=1): the reference's own arithmetic
+                if not self.SUPPORTS_FP16:
+                    raise NotImplementedError(f"fp16 compute (SASPA_FP16=1) is built for the SD-1.5 pipelines, not {type(self).__name__}")
+                if fp16_vae not in ("bf16", "x3"):
+                    raise ValueError(f"SASPA_FP16_VAE must be 'bf16' or 'x3', got {fp16_vae!r}")
+                cdt = torch.float16
         elif dtype == torch.float32:
             cdt, ndt = torch.float32, torch.float32
         else:
             raise TypeError(f"unsupported pipeline dtype {dtype}")
+        # fp16 compute keeps the VAE (its activations overflow fp16) and the safety checker out of fp16: the VAE stays bf16, or runs
+        # on fp32 storage with SASPA_F32X3 GEMMs (vae="x3"); the hand-offs are explicit casts outside the captured step
+        vdt = cdt if cdt != torch.float16 else (torch.float32 if fp16_vae == "x3" else torch.bfloat16)
+        self._vae_dtype = vdt
+        self._safety_dtype = cdt if cdt != torch.float16 else torch.bfloat16
         self.device, self.dtype, self.noise_dtype = device, cdt, ndt
         # the kernels launch on the CURRENT HIP device / torch's current stream of it: make the pipeline's device current
         # (the reference's idiom is editing DEVICE = "cuda:1"; without this tensors would live on GPU 1, launches on GPU 0)
@@ -284,10 +303,13 @@ class StableDiffusionControlNetPipeline:
         sd, cf = self._state_dicts, self.cfgs
         fp8 = getattr(self, "_fp8", False) or os.environ.get("SASPA_FP8", "0") == "1"
         fp8_conv = fp8 and (getattr(self, "_fp8_conv", False) or os.environ.get("SASPA_FP8_CONV", "0") == "1")
+        if fp8 and cdt == torch.float16:
+            raise ValueError("fp8 together with fp16 compute is not supported: the fp8 projections quantise bf16 activations")
         self.unet = models.UNet(sd["unet"], cf["unet"], device, cdt, fp8=fp8, fp8_conv=fp8_conv)
         self.controlnet = (models.ControlNet(sd["controlnet"], cf["controlnet"], device, cdt, fp8=fp8, fp8_conv=fp8_conv)
                            if self.HAS_CONTROLNET else None)
-        self.vae = models.VAEDecoder(sd["vae"], cf["vae"], device, cdt)
+        self.vae = models.VAEDecoder(sd["vae"], cf["vae"], device, vdt,
+                                     f32_gemm="x3" if (cdt == torch.float16 and vdt == torch.float32) else "exact")
         self.text_encoder = models.CLIPText(sd["text"], cf["text"], device, cdt)
         self._build_extra(sd, cf, device, cdt)
         self._neg_cache = {}
@@ -297,7 +319,26 @@ class StableDiffusionControlNetPipeline:
     def _build_extra(self, sd, cf, device, cdt):
         # StableDiffusionSafetyChecker of the SD-1.5 repo: the reference never passes safety_checker=None
         if "safety" in sd and "safety" in cf:
-            self.safety_checker = models.SafetyChecker(sd["safety"], cf["safety"], device, cdt)
+            self.safety_checker = models.SafetyChecker(sd["safety"], cf["safety"], device, self._safety_dtype)
+
+    def enable_fp16(self, on=True, vae="bf16"):
+        """Call BEFORE `.to()`: `.to(dev, torch.float16)` / `.to(dev)` then computes the text tower, UNet, ControlNet and the scheduler
+        steps in IEEE fp16 -- the reference's own arithmetic (run_aug/run_aug.py:323) -- on the fp16 build of the kernels
+        (libsaspa_hip_f16.so: f16 MFMAs, same schedules); the latents are fp16 too.  SASPA_FP16=1 (+ SASPA_FP16_VAE) does the same.
+        Without it nothing changes: torch.float16 selects bf16.  The VAE and the safety checker do not run in fp16 (the SD VAE
+        overflows there): vae="bf16" keeps them as they are, vae="x3" runs the VAE on fp32 storage with SASPA_F32X3 GEMMs (the form to
+        use when the decoded image's parity is the point).  Not together with fp8."""
+        if not self.SUPPORTS_FP16:
+            raise NotImplementedError(f"enable_fp16() is built for the SD-1.5 pipelines (ControlNet, ControlNet img2img, img2img), "
+                                      f"not for {type(self).__name__}")
+        if self.unet is not None:
+            raise RuntimeError("enable_fp16() must be called before .to(): the weights are packed in the compute dtype")
+        if vae not in ("bf16", "x3"):
+            raise ValueError(f"vae must be 'bf16' or 'x3', got {vae!r}")
+        if on and getattr(self, "_fp8", False):
+            raise ValueError("fp8 together with fp16 compute is not supported: the fp8 projections quantise bf16 activations")
+        self._fp16, self._fp16_vae = bool(on), vae
+        return self
 
     def enable_fp8(self, on=True, convs=False):
         """Call BEFORE `.to()`: the LayerNorm-fed projections of the UNet / ControlNet transformer blocks (cross-attention
@@ -309,6 +350,8 @@ class StableDiffusionControlNetPipeline:
             raise RuntimeError("enable_fp8() must be called before .to(): the weights are quantised at pack time")
         if convs and not on:
             raise ValueError("fp8 convs need fp8 on: enable_fp8(True, convs=True)")
+        if on and self._fp16:
+            raise ValueError("fp8 together with fp16 compute is not supported: the fp8 projections quantise bf16 activations")
         self._fp8 = bool(on)
         self._fp8_conv = bool(convs)
         return self
@@ -493,7 +536,7 @@ class StableDiffusionControlNetPipeline:
         h8, w8 = hh // 8, ww // 8
         self._sample(x2, b, h8 * w8, ctx, cemb2, num_inference_steps, guidance_scale, controlnet_conditioning_scale)
         z = ops.scale(x2[:b], 1.0 / self.cfgs["vae"]["scaling_factor"])
-        img = self.vae.decode(z)
+        img = self.vae.decode(z.to(self.vae.dtype))          # (fp16 compute: the hand-off to the bf16 / fp32 VAE; a no-op otherwise)
         out, self.last_nsfw = self.run_safety_checker(ops.act_to_u8(img))
         if return_latents:
             return out, x2[:b], img
@@ -535,7 +578,7 @@ class StableDiffusionControlNetImg2ImgPipeline(StableDiffusionControlNetPipeline
         super()._build_extra(sd, cf, device, cdt)
         if "encoder.conv_in.weight" not in sd["vae"]:
             raise KeyError("the VAE checkpoint has no encoder half: img2img (SDEdit) needs vae/encoder.* and quant_conv")
-        self.vae_encoder = models.VAEEncoder(sd["vae"], cf["vae"], device, cdt)
+        self.vae_encoder = models.VAEEncoder(sd["vae"], cf["vae"], device, self._vae_dtype)
 
     @staticmethod
     def kept_steps(num_inference_steps, strength):
@@ -570,8 +613,10 @@ class StableDiffusionControlNetImg2ImgPipeline(StableDiffusionControlNetPipeline
         if hh % mult or ww % mult:
             raise ValueError(f"image sides must be multiples of {mult} (got {hh}x{ww})")
         from . import imageproc
-        px = imageproc.normalize_u8(src, dt, (0.5, 0.5, 0.5), (0.5, 0.5, 0.5))          # VaeImageProcessor: [0,255] -> [-1,1]
-        moments = self.vae_encoder.encode(px)
+        vdt = self.vae_encoder.dtype                   # == dt unless fp16 compute is on (the VAE stays bf16 / fp32 then)
+        px = imageproc.normalize_u8(src, vdt, (0.5, 0.5, 0.5), (0.5, 0.5, 0.5))         # VaeImageProcessor: [0,255] -> [-1,1]
+        with ops.f32_gemm_mode(self.vae.f32_gemm):
+            moments = self.vae_encoder.encode(px).to(dt)
         sch = self.scheduler
         ts = list(sch.set_timesteps(num_inference_steps))
         a_t = float(sch.alphas_cumprod[int(ts[t_start])])
@@ -590,7 +635,7 @@ class StableDiffusionControlNetImg2ImgPipeline(StableDiffusionControlNetPipeline
         x2 = torch.cat([x, x], 0).contiguous()
         self._sample(x2, b, (hh // 8) * (ww // 8), ctx, cemb2, num_inference_steps, guidance_scale,
                      controlnet_conditioning_scale, t_start=t_start)
-        img = self.vae.decode(ops.scale(x2[:b], 1.0 / self.cfgs["vae"]["scaling_factor"]))
+        img = self.vae.decode(ops.scale(x2[:b], 1.0 / self.cfgs["vae"]["scaling_factor"]).to(self.vae.dtype))
         out, self.last_nsfw = self.run_safety_checker(ops.act_to_u8(img))
         if return_latents:
             return out, x2[:b], img
@@ -667,6 +712,7 @@ class StableDiffusionImg2ImgPipeline(StableDiffusionControlNetImg2ImgPipeline):
 
 
 class BlipDiffusionControlNetPipeline(StableDiffusionControlNetPipeline):
+    SUPPORTS_FP16 = False
     """Drop-in for diffusers' `BlipDiffusionControlNetPipeline` as the reference builds and calls it for every dataset
     but planes (run_aug/run_aug.py:181, :211, :243-250, :262-265, :521; SURVEY 8a a8):
 
@@ -768,6 +814,7 @@ class BlipDiffusionControlNetPipeline(StableDiffusionControlNetPipeline):
 
 
 class StableDiffusionXLControlNetPipeline(StableDiffusionControlNetPipeline):
+    SUPPORTS_FP16 = False
     """Drop-in for diffusers' `StableDiffusionXLControlNetPipeline` as the reference builds and calls it for
     `BASE_MODEL = "sd_xl-turbo"` (its choice for CUB; run_aug/run_aug.py:189-201, :223-228, :564-571; SURVEY 8a a9):
 

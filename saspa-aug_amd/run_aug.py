@@ -178,6 +178,8 @@ class Settings:
     PROMPTS_FILE: str = None
     DATASET_KWARGS: dict = field(default_factory=dict)
     PNG_DEVICE: bool = False           # generated and source images are filtered + deflated on the device (ops.png_deflate); off: Pillow
+    FP16: bool = False                 # IEEE fp16 compute (pipe.enable_fp16) for the SD-1.5 pipelines with PRECISION "bf16"; off: bf16
+    FP16_VAE: str = "bf16"             # with FP16: "bf16" keeps the VAE as it is, "x3" runs it on fp32 storage with SASPA_F32X3 GEMMs
     MAX_BATCHES: int = 0               # > 0: stop this rank after that many batches (rehearsals / diagnostics; the rest stays status 0)
 
 
@@ -883,6 +885,8 @@ def _main(s: Settings, ds_utils=None, batch_generator=None, dist=None, pipe=None
     if batch_generator is None:
         if pipe is None:
             pipe = init_pipeline(s.BASE_MODEL, s.CONTROLNET, s.SDEDIT, weights_dir=s.WEIGHTS_DIR)
+            if s.FP16 and s.PRECISION != "fp32":
+                pipe.enable_fp16(True, vae=s.FP16_VAE)          # (raises on the BLIP-Diffusion / SDXL pipelines)
             pipe = pipe.to(s.DEVICE, torch.float32 if s.PRECISION == "fp32" else torch.float16)
         batch_generator = hip_batch_generator(pipe, s)
         noise_dtype = pipe.noise_dtype

@@ -644,8 +644,8 @@ def pack_conv_split(w, c0, c0_pad, c1, c1_pad):
 
 
 def ktile(dtype):
-    """Elements of one K-tile of the implicit GEMM (128 bytes per row): 64 bf16 / 32 fp32."""
-    return 64 if dtype == torch.bfloat16 else 32
+    """Elements of one K-tile of the implicit GEMM (128 bytes per row): 64 of the 16-bit compute type (bf16 / fp16) / 32 fp32."""
+    return 64 if dtype in (torch.bfloat16, torch.float16) else 32
 
 
 def chunk_major_ok(kh, kw, c0_pad, c1_pad, dtype):

@@ -595,6 +595,13 @@ typedef struct SaspaXattnBlockParams {
   int ldo;
 } SaspaXattnBlockParams;
 int saspa_xattn_block(const SaspaXattnBlockParams* p, void* stream);
+/* The same launch reading a SHARED x / residual of x_rows rows (the parameter struct is unchanged): output row r reads x / residual
+ * row r % x_rows, its keys are those of sample r / rows_per_sample as above; out, kf and vf cover M rows.  Under classifier-free
+ * guidance the unconditional and the conditional half of a batch share the hidden states up to the first cross-attention and differ
+ * in the text keys only: x_rows = M / 2 lets that prefix run once per image (models._Net.encode(cfg_pair=True)).
+ * x_rows > 0 (SASPA_EINVAL), x_rows % rows_per_sample == 0 and M % x_rows == 0 (SASPA_ERANGE); the 32-bit offset limit holds for
+ * x / residual over x_rows rows and for out over M rows.  x_rows == M is saspa_xattn_block, which is a call of this function. */
+int saspa_xattn_block_bcast(const SaspaXattnBlockParams* p, long long x_rows, void* stream);
 
 /* ---- measurement aid (ABI 20): effective shader clock under load ------------------------------------------------------
  * One sleeping wave measures s_memtime (shader clocks) against s_memrealtime (constant 100 MHz) over iters x s_sleep 127

@@ -158,6 +158,7 @@ SYMBOLS = {
     "saspa_cfg_unipc_step": (_I, [_I, _P, _P, _P, _I, _LL, _I, _I, _F, C.POINTER(C.c_float), _P, _P, _P]),
     "saspa_unipc_step": (_I, [_I, _P, _P, _P, _I, _LL, _I, _I, C.POINTER(C.c_float), _P, _P, _P]),
     "saspa_xattn_block": (_I, [C.POINTER(XattnBlockParams), _P]),
+    "saspa_xattn_block_bcast": (_I, [C.POINTER(XattnBlockParams), _LL, _P]),
     "saspa_groupnorm_onepass_eligible": (_I, [C.POINTER(GroupNormParams)]),
     "saspa_groupnorm_onepass": (_I, [C.POINTER(GroupNormParams), _P]),
     "saspa_splitk_groupnorm_eligible": (_I, [C.POINTER(GemmParams), C.POINTER(GroupNormParams)]),
@@ -181,7 +182,8 @@ SYMBOLS = {
 # PNG exist in the default library only
 F16_SYMBOL_NAMES = (
     "saspa_gemm", "saspa_gemm_suggest_ksplit", "saspa_gemm_as_eligible", "saspa_gemm_as_auto", "saspa_gemm_which",
-    "saspa_ff_block", "saspa_ff_block_eligible", "saspa_xattn_block", "saspa_flash_attn_bf16", "saspa_softmax_rows",
+    "saspa_ff_block", "saspa_ff_block_eligible", "saspa_xattn_block", "saspa_xattn_block_bcast", "saspa_flash_attn_bf16",
+    "saspa_softmax_rows",
     "saspa_groupnorm_stats", "saspa_groupnorm_apply", "saspa_groupnorm_onepass_eligible", "saspa_groupnorm_onepass",
     "saspa_splitk_groupnorm_eligible", "saspa_splitk_groupnorm", "saspa_layernorm", "saspa_geglu", "saspa_activation",
     "saspa_embed_tokens", "saspa_embed_tokens_ctx", "saspa_cfg_plms_step", "saspa_cfg_plms_step_dev", "saspa_cfg_ddim_step",

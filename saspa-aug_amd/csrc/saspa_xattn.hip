@@ -21,6 +21,11 @@
 //      (SaspaXattnBlockParams.kf / vf: time-invariant, built once per generation) straight from L2 into registers.
 //   4. O^T / denominator -> bf16 -> the B operand of Y^T = Wo' O^T (K order of Wo' = the order the fragments come out in), five
 //      more slices through the same ring; epilogue = bias + residual through the wave-private staging tile, 16-byte stores.
+// Shared prefix (saspa_xattn_block_bcast): under classifier-free guidance the two halves of a batch reach this launch with the
+// same hidden states and different text keys.  x / residual then hold x_rows < M rows and a workgroup loads its A fragments and
+// its residual from block blockIdx.x mod (x_rows / 256) while its keys and its output stay those of block blockIdx.x -- the
+// first launch of a network that runs at all M rows.  Same vector-memory instructions in the same order: the vmcnt bookkeeping
+// does not change, and a row's arithmetic is that of the un-shared launch on duplicated rows, bit for bit.
 #include <cstdlib>
 
 #include "common.h"
@@ -67,13 +72,17 @@ __device__ __forceinline__ f32x16 xmfma(const u32x4& a, const u32x4& b, const f3
   return MFMA_32X32X16(a, b, c);
 }
 
-__global__ __launch_bounds__(512, 1) void xattn_block_kernel(const SaspaXattnBlockParams p, const int abl) {
+__global__ __launch_bounds__(512, 1) void xattn_block_kernel(const SaspaXattnBlockParams p, const int abl, const int xblocks) {
   __shared__ u32x4 lds[XA_RING * XA_STAGE + XA_STG_CHUNKS];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int m = lane & 31, h = lane >> 5;
-  const long long row = (long long)blockIdx.x * XA_BM + wave * 32 + m;      // < M: the host checks M % 256 == 0
+  // the 256-row block of x / residual this workgroup reads: its own, wrapped into the xblocks blocks x holds (saspa_xattn_block_bcast;
+  // xblocks = gridDim.x: no wrap).  Wave-uniform scalar arithmetic; the host checks M % x_rows == 0, so the loop ends on a whole block
+  int xblk = (int)blockIdx.x;
+  while (xblk >= xblocks) xblk -= xblocks;
+  const long long row = (long long)xblk * XA_BM + wave * 32 + m;             // < x_rows: the host checks x_rows % 256 == 0
 
   // ---- this lane's half of its row: channels 16 s + 8 h .. + 8 ----
   const rsrc_t rsa = make_rsrc(p.x);
@@ -355,13 +364,14 @@ __global__ __launch_bounds__(512, 1) void xattn_block_kernel(const SaspaXattnBlo
   const rsrc_t rsr = make_rsrc(p.residual);
   const rsrc_t rso = make_rsrc(p.out);
   unsigned char* stg = reinterpret_cast<unsigned char*>(lds + XA_RING * XA_STAGE) + wave * XA_STG_WAVE;
-  const long long row0 = (long long)blockIdx.x * XA_BM + wave * 32;
+  const long long row0 = (long long)blockIdx.x * XA_BM + wave * 32;          // output rows: the workgroup's own block
+  const long long rrow0 = (long long)xblk * XA_BM + wave * 32;               // residual rows: the wrapped block, as x
   unsigned so_off[NST], sr_off[NST];
 #pragma unroll
   for (int i = 0; i < NST; ++i) {
-    const long long r = row0 + RPI * i + lane / LPR;
-    so_off[i] = (unsigned)(r * p.ldo * 2 + (lane % LPR) * 16);
-    sr_off[i] = (unsigned)(r * p.ldr * 2 + (lane % LPR) * 16);
+    const int ri = RPI * i + lane / LPR;
+    so_off[i] = (unsigned)((row0 + ri) * p.ldo * 2 + (lane % LPR) * 16);
+    sr_off[i] = (unsigned)((rrow0 + ri) * p.ldr * 2 + (lane % LPR) * 16);
   }
   const unsigned char* stg_rd = stg + (lane / LPR) * SPITCH + (lane % LPR) * 16;
   unsigned char* stg_wr = stg + m * SPITCH + h * 8;
@@ -429,24 +439,32 @@ __global__ __launch_bounds__(512, 1) void xattn_block_kernel(const SaspaXattnBlo
 
 }  // namespace
 
-extern "C" int saspa_xattn_block(const SaspaXattnBlockParams* pp, void* stream) {
+extern "C" int saspa_xattn_block_bcast(const SaspaXattnBlockParams* pp, long long x_rows, void* stream) {
   if (!pp) return SASPA_EINVAL;
   const SaspaXattnBlockParams& p = *pp;
   if (!p.x || !p.residual || !p.out || !p.w || !p.bias || !p.kf || !p.vf || !p.ln_gamma || !p.ln_beta) return SASPA_EINVAL;
-  if (p.M <= 0 || p.rows_per_sample <= 0 || p.nk <= 0) return SASPA_EINVAL;
+  if (p.M <= 0 || p.rows_per_sample <= 0 || p.nk <= 0 || x_rows <= 0) return SASPA_EINVAL;
   if (p.M % XA_BM || p.rows_per_sample % XA_BM || p.M % p.rows_per_sample || p.nk > 96) return SASPA_ERANGE;
+  if (x_rows % p.rows_per_sample || p.M % x_rows) return SASPA_ERANGE;      // x holds whole samples, the output whole copies of x
   if (p.ldx < XA_K || p.ldr < XA_K || p.ldo < XA_K || p.ldw < XA_K) return SASPA_ERANGE;
   if (p.ldx % 8 || p.ldr % 8 || p.ldo % 8 || p.ldw % 8) return SASPA_EALIGN;
   if (!aligned16(p.x) || !aligned16(p.residual) || !aligned16(p.out) || !aligned16(p.w) || !aligned16(p.bias) || !aligned16(p.kf) ||
       !aligned16(p.vf) || !aligned16(p.ln_gamma) || !aligned16(p.ln_beta))
     return SASPA_EALIGN;
-  const long long ld = p.ldx > p.ldo ? (p.ldx > p.ldr ? p.ldx : p.ldr) : (p.ldo > p.ldr ? p.ldo : p.ldr);
-  if ((long long)p.M * ld * 2 >= 0x7fffffffLL) return SASPA_ERANGE;                       // 32-bit buffer offsets
+  // 32-bit buffer offsets: x / residual over the x_rows rows they hold, out over all M
+  const long long ldxr = p.ldx > p.ldr ? p.ldx : p.ldr;
+  if (x_rows * ldxr * 2 >= 0x7fffffffLL || (long long)p.M * p.ldo * 2 >= 0x7fffffffLL) return SASPA_ERANGE;
   const long long nsamp = p.M / p.rows_per_sample;
   if (p.kf_stride < 8 * XA_KF_HEAD || p.vf_stride < 8 * XA_VF_HEAD || p.kf_stride % 16 || p.vf_stride % 16) return SASPA_ERANGE;
   if (nsamp * p.kf_stride >= 0x7fffffffLL || nsamp * p.vf_stride >= 0x7fffffffLL) return SASPA_ERANGE;
   static const int abl = getenv("SASPA_XATTN_ABLATE") ? atoi(getenv("SASPA_XATTN_ABLATE")) : 0;      // diagnostics only
-  hipLaunchKernelGGL(xattn_block_kernel, dim3((unsigned)(p.M / XA_BM)), dim3(512), 0, reinterpret_cast<hipStream_t>(stream), p, abl);
+  hipLaunchKernelGGL(xattn_block_kernel, dim3((unsigned)(p.M / XA_BM)), dim3(512), 0, reinterpret_cast<hipStream_t>(stream), p, abl,
+                     (int)(x_rows / XA_BM));
   SASPA_CHECK_LAUNCH();
   return 0;
+}
+
+extern "C" int saspa_xattn_block(const SaspaXattnBlockParams* pp, void* stream) {
+  if (!pp) return SASPA_EINVAL;
+  return saspa_xattn_block_bcast(pp, pp->M, stream);      // M <= 0 is refused there (x_rows <= 0)
 }

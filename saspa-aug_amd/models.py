@@ -478,7 +478,11 @@ class _Net:
             p[t + ".ff.scale"] = torch.ones(1, device=self.dev, dtype=torch.float32)
             self.fp8_ffout[t] = False          # -> True once the scale has been calibrated (first execution of the block)
 
-    def transformer(self, pfx, x):
+    def transformer(self, pfx, x, cfg_pair=False):
+        """Transformer2DModel.  cfg_pair: x holds the B rows both CFG halves share and the cached context 2B samples (uncond
+        first).  GroupNorm, proj_in and the first block's self-attention run once at B rows; the rows double where the context
+        enters -- in the fused cross-attention launch itself (ops.xattn_block(x_rows=...)) or by one copy in front of the
+        existing code -- and the result has 2B rows."""
         p, g = self.p, self.cfg["groups"]
         heads, depth = self.tr_info[pfx]
         b, hh, ww, c = x.shape
@@ -490,8 +494,11 @@ class _Net:
             # self-attention.  Level 0 of a full-size batch: LayerNorm + Q | K + V^T in ONE launch of the A-stationary kernel
             # (saspa_gemm_as.hip) instead of three launches that each re-read the tokens
             wqkv = p.get(t + ".attn1.qkv.w")
-            fuse = wqkv is not None and c == 320 and t not in self.fp8_blocks and n % 32 == 0 and \
-                ops.linear_ln_fusable(h, wqkv, n_out=2 * c)
+
+            def fusable(rows):
+                return wqkv is not None and c == 320 and t not in self.fp8_blocks and n % 32 == 0 and \
+                    ops.linear_ln_fusable(rows, wqkv, n_out=2 * c)
+            fuse = fusable(h)
             pre = t in self.qscaled
             if t in self.fp8_qkv:
                 # W8A8 (round 6): LayerNorm + per-token quantisation in one pass, ONE e4m3 projection launch for Q | K | V
@@ -513,6 +520,24 @@ class _Net:
                 vt = project_vt(n1, p[t + ".attn1.v.w"], n)
                 o = attention_core(qk[:, :, :c], qk[:, :, c:], vt, heads, n, n, prescaled=pre)
             h = ops.linear(o, p[t + ".attn1.o.w"], p[t + ".attn1.o.b"], residual=h)
+            if cfg_pair and d == 0:
+                # the two CFG halves part here: everything above ran once on the rows they share
+                kv = self.ctx_kv[t]
+                if kv[0].shape[0] != 2 * b:
+                    raise ValueError(f"cfg_pair: {b} shared samples need a context of {2 * b} samples, not {kv[0].shape[0]}")
+                if _is_half(h.dtype) and c == 320 and len(kv) == 5 and n % 256 == 0 and kv[2] <= 96 and t not in self.fp8_blocks:
+                    # LayerNorm + to_q + attention + to_out + residual of BOTH halves in one launch that reads the shared rows
+                    # (a condition of its own: `fuse` asks for row blocks that half a batch does not have)
+                    h = ops.xattn_block(h, (p[t + ".norm2.g"], p[t + ".norm2.b"], 1e-5), p[t + ".attn2.xw"], p[t + ".attn2.xb"],
+                                        kv[3], kv[4], kv[2], n, x_rows=b * n).view(2 * b, n, c)
+                    shared_xattn = True
+                else:
+                    h = ops.dup_rows(h)         # every other form: one copy, then the existing code at 2B rows
+                    shared_xattn = False
+                b *= 2
+                fuse = fusable(h)
+            else:
+                shared_xattn = False
             if t in self.fp8_blocks:
                 # W8A8: LayerNorm + per-token quantisation in one pass, e4m3 x e4m3 MFMA, scales applied in the epilogue
                 q8, s8 = ops.layernorm_quant_fp8(h, p[t + ".norm2.g"], p[t + ".norm2.b"])
@@ -544,7 +569,9 @@ class _Net:
                 continue
             # cross-attention against the cached text K / V^T
             kv = self.ctx_kv[t]
-            if fuse and len(kv) == 5 and n % 256 == 0 and kv[2] <= 96:
+            if shared_xattn:
+                pass
+            elif fuse and len(kv) == 5 and n % 256 == 0 and kv[2] <= 96:
                 # level 0 of a full-size batch: LayerNorm + to_q + attention + to_out + residual in one launch
                 h = ops.xattn_block(h, (p[t + ".norm2.g"], p[t + ".norm2.b"], 1e-5), p[t + ".attn2.xw"], p[t + ".attn2.xb"], kv[3], kv[4],
                                     kv[2], n)
@@ -573,19 +600,32 @@ class _Net:
                 else:
                     ff = ops.geglu(ops.linear(n3, p[t + ".ff.net.0.proj.w"], p[t + ".ff.net.0.proj.b"]))
             h = ops.linear(ff, p[t + ".ff.net.2.w"], p[t + ".ff.net.2.b"], residual=h)
+        if cfg_pair:
+            x = ops.dup_rows(x)                 # the proj_out residual, at 2B rows like h
         return ops.conv(h.view(b, hh, ww, c), p[pfx + ".proj_out.w"], p[pfx + ".proj_out.b"], residual=x, gn_unit=self.gn_unit)
 
-    def encode(self, sample, step, conv_in_residual=None):
-        """conv_in + down blocks + mid block.  Returns (mid, [skips])."""
+    def encode(self, sample, step, conv_in_residual=None, cfg_pair=False):
+        """conv_in + down blocks + mid block.  Returns (mid, [skips]).
+        cfg_pair: `sample` / `conv_in_residual` hold the B rows that the two halves of a classifier-free-guidance batch share
+        and the context (prepare_context) 2B samples, uncond first.  What comes before the context's first use -- conv_in,
+        down_blocks.0.resnets.0, the first transformer up to its self-attention -- runs once at B rows; `mid` and the skips come
+        back at 2B rows as from encode(cat([sample, sample])), except skips[0] (conv_in's output), which stays at B rows
+        (ControlNet.zero_convs(cfg_pair=True) / ops.dup_rows).  Only for networks whose time-embedding row is one for the whole
+        batch (prepare_timesteps without added conditioning)."""
         cfg, p = self.cfg, self.p
+        if cfg_pair and "add_embed" in cfg:
+            raise ValueError("cfg_pair: the added conditioning gives the two halves different time embeddings (SDXL)")
         s = ops.conv(sample, p["conv_in.w"], p["conv_in.b"], kh=3, kw=3, pad=1, residual=conv_in_residual, gn_unit=self.gn_unit)
         skips = [s]
         n_lvl = len(cfg["block_out"])
         for i in range(n_lvl):
             for j in range(cfg["layers"]):
                 s = self.resnet(f"down_blocks.{i}.resnets.{j}", s, step, 1e-5)
+                first = cfg_pair and i == 0 and j == 0
                 if cfg["attn"][i]:
-                    s = self.transformer(f"down_blocks.{i}.attentions.{j}", s)
+                    s = self.transformer(f"down_blocks.{i}.attentions.{j}", s, cfg_pair=first)
+                elif first:
+                    s = ops.dup_rows(s)         # no attention at level 0: the halves part behind the first resnet
                 skips.append(s)
             if i != n_lvl - 1:
                 d = f"down_blocks.{i}.downsamplers.0.conv"
@@ -683,21 +723,24 @@ class ControlNet(_Net):
                          act=SILU)
         return ops.conv(h, p[e + ".conv_out.w"], p[e + ".conv_out.b"], kh=3, kw=3, pad=1)
 
-    def forward(self, sample, step, cond_emb, scale, unet_skips=None, unet_mid=None):
+    def forward(self, sample, step, cond_emb, scale, unet_skips=None, unet_mid=None, cfg_pair=False):
         """Returns ([12 residuals], mid residual), each scale*(zero_conv(feature)) and, when the
-        UNet encoder outputs are given, already summed with them (fused epilogue)."""
-        mid, feats = self.encode(sample, step, conv_in_residual=cond_emb)
-        return self.zero_convs(mid, feats, scale, unet_skips, unet_mid)
+        UNet encoder outputs are given, already summed with them (fused epilogue).  cfg_pair: as encode() / zero_convs()."""
+        mid, feats = self.encode(sample, step, conv_in_residual=cond_emb, cfg_pair=cfg_pair)
+        return self.zero_convs(mid, feats, scale, unet_skips, unet_mid, cfg_pair=cfg_pair)
 
-    def zero_convs(self, mid, feats, scale, unet_skips=None, unet_mid=None):
+    def zero_convs(self, mid, feats, scale, unet_skips=None, unet_mid=None, cfg_pair=False):
         """The 12 + 1 zero convolutions on the encoder features (x conditioning scale, + the UNet's own skips / mid when
-        given): the point where the ControlNet branch joins the UNet."""
+        given): the point where the ControlNet branch joins the UNet.  cfg_pair: feats[0] and unet_skips[0] are the B-row
+        outputs of encode(cfg_pair=True); zero conv 0 runs at B rows and its result is duplicated for the decoder."""
         p = self.p
         outs = []
         for i, f in enumerate(feats):
             r = None if unet_skips is None else unet_skips[i]
             outs.append(ops.conv(f, p[f"controlnet_down_blocks.{i}.w"], p[f"controlnet_down_blocks.{i}.b"], alpha=scale,
                                  residual=r, gn_unit=self.gn_unit))
+            if cfg_pair and i == 0:
+                outs[0] = ops.dup_rows(outs[0])
         m = ops.conv(mid, p["controlnet_mid_block.w"], p["controlnet_mid_block.b"], alpha=scale, residual=unet_mid,
                      gn_unit=self.gn_unit)
         return outs, m

@@ -644,10 +644,20 @@ def linear(x, w, bias=None, *, residual=None, alpha=1.0, act=ACT_NONE, out=None,
     return out
 
 
-def xattn_block(x, ln, w, bias, kf, vf, nk, rows_per_sample, residual=None, out=None):
+def dup_rows(x):
+    """[B, ...] -> [2B, ...] = cat([x, x]) in ONE launch (a broadcast copy into a [2, B, ...] view): the point where a CFG-shared
+    prefix becomes the two halves of the batch (models._Net.encode(cfg_pair=True))."""
+    out = torch.empty((2,) + tuple(x.shape), device=x.device, dtype=x.dtype)
+    out.copy_(x.unsqueeze(0).expand_as(out))
+    return out.view((2 * x.shape[0],) + tuple(x.shape[1:]))
+
+
+def xattn_block(x, ln, w, bias, kf, vf, nk, rows_per_sample, residual=None, out=None, x_rows=None):
     """The cross-attention half of a level-0 transformer block in one launch (saspa_xattn_block, include/saspa_hip.h):
     out = residual + to_out(softmax(to_q(LayerNorm(x)) K^T) V) + bias.  x [..., 320] bf16 (uniform row pitch), ln = (gamma, beta,
-    eps), w / bias from weights.pack_xattn_w, kf / vf [B, ...] from weights.xattn_kv_fragments, residual defaults to x."""
+    eps), w / bias from weights.pack_xattn_w, kf / vf [B, ...] from weights.xattn_kv_fragments, residual defaults to x.
+    x_rows (saspa_xattn_block_bcast): x / residual hold x_rows rows that every group of x_rows output rows reads again, the
+    output has kf.shape[0] * rows_per_sample rows -- the two CFG halves of a shared prefix, each against its own keys."""
     _check_dev(x, w, bias, kf, vf, residual, out)
     _same_dtype("xattn_block", x, w=w, kf=kf, vf=vf, residual=residual, out=out)
     lib = _L(x)
@@ -657,6 +667,10 @@ def xattn_block(x, ln, w, bias, kf, vf, nk, rows_per_sample, residual=None, out=
     if not is_half(x) or c != 320:
         raise ValueError("xattn_block: bf16 rows of 320 channels")
     r2 = x2 if residual is None else (residual.reshape(-1, c) if residual.dim() != 2 else residual)
+    if x_rows is not None:
+        if int(x_rows) != m or r2.shape[0] != m:
+            raise ValueError(f"xattn_block: x_rows = {x_rows}, x holds {m} rows and the residual {r2.shape[0]}")
+        m = kf.shape[0] * int(rows_per_sample)
     if out is None:
         out = torch.empty((m, c), device=x.device, dtype=x.dtype)
     o2 = out.view(-1, c) if out.dim() != 2 else out
@@ -675,9 +689,12 @@ def xattn_block(x, ln, w, bias, kf, vf, nk, rows_per_sample, residual=None, out=
         raise ValueError(f"xattn_block: {kf.shape[0]} samples of {rows_per_sample} rows do not make {m} rows")
     # algorithmic work: to_q + to_out (2 x 2 M C^2) and the two attention products over the nk keys (2 x 2 M nk C)
     flops = 4.0 * m * c * c + 4.0 * m * nk * c
-    _launch("gemm", flops, lambda: _lib.check(lib.saspa_xattn_block(C.byref(p), _stream()), "saspa_xattn_block"),
-            (m, 2 * c + 2 * nk, c, 0, 1, 0, False, True, c))
-    if x.dim() != 2 and out.dim() == 2:
+    if x_rows is None:
+        call = lambda: _lib.check(lib.saspa_xattn_block(C.byref(p), _stream()), "saspa_xattn_block")  # noqa: E731
+    else:
+        call = lambda: _lib.check(lib.saspa_xattn_block_bcast(C.byref(p), int(x_rows), _stream()), "saspa_xattn_block_bcast")  # noqa: E731
+    _launch("gemm", flops, call, (m, 2 * c + 2 * nk, c, 0, 1, 0, False, True, c))
+    if x_rows is None and x.dim() != 2 and out.dim() == 2:
         return out.reshape(*x.shape[:-1], c)
     return out
 

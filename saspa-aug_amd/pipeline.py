@@ -49,6 +49,13 @@ def fork_enabled():
     return os.environ.get("SASPA_FORK", "1") != "0"
 
 
+def cfg_prefix_enabled():
+    """Classifier-free guidance evaluates the rows the two halves of the batch share -- conv_in, the first resnet, the first
+    transformer up to its self-attention, in the UNet and in the ControlNet -- once per image (models._Net.encode(cfg_pair=True)).
+    SASPA_CFG_PREFIX=0 evaluates them for both halves, as cat([x, x])."""
+    return os.environ.get("SASPA_CFG_PREFIX", "1") != "0"
+
+
 def replay_queue_depth():
     """Replays of the step graph the host keeps outstanding before it sleeps until the oldest has finished (see _StepGraph.run;
     0 = unthrottled)."""
@@ -68,9 +75,10 @@ class _StepGraph:
     Everything a step reads lives in static buffers owned by this object; what changes from step to step is read on the
     device through a step counter (time-embedding rows: ops.gather_row; DDIM coefficients: ops.ddim_step_dev)."""
 
-    def __init__(self, pipe, x_shape, cemb_shape, steps, cfg, guidance, cscale):
+    def __init__(self, pipe, x_shape, cemb_shape, steps, cfg, guidance, cscale, cfg_pair=False):
         dev, dt = pipe.device, pipe.dtype
         self.pipe, self.steps, self.cfg, self.guidance, self.cscale = pipe, steps, cfg, guidance, cscale
+        self.cfg_pair = bool(cfg and cfg_pair)      # the encoders' shared prefix once per image (cfg_prefix_enabled)
         self.x = torch.zeros(x_shape, device=dev, dtype=dt)
         self.eps = torch.zeros(x_shape, device=dev, dtype=dt)
         self.cemb = torch.zeros(cemb_shape, device=dev, dtype=dt)
@@ -143,8 +151,14 @@ class _StepGraph:
         pipe, x = self.pipe, self.x
         for net, tab, cur in zip(self.nets, self.tables, self.curs):
             ops.gather_row(tab, self.idx, cur)
+        pair = self.cfg_pair
+        # (pair: the encoders take the B rows the two CFG halves share -- the halves of x are equal, the update keeps them so)
+        xe = x[:x.shape[0] // 2] if pair else x
+        ce = self.cemb[:self.cemb.shape[0] // 2] if pair and pipe.controlnet is not None else self.cemb
         if pipe.controlnet is None:
-            mid2, skips2 = pipe.unet.encode(x, None)
+            mid2, skips2 = pipe.unet.encode(xe, None, cfg_pair=pair)
+            if pair:
+                skips2[0] = ops.dup_rows(skips2[0])
         elif fork_enabled():
             # the UNet encoder and the ControlNet encoder are independent until the zero convs add the two: two
             # branches of the captured graph.  Same kernels on the same inputs -> bit-identical to the single-stream order; what
@@ -155,13 +169,13 @@ class _StepGraph:
             self.side.wait_stream(main)
             with ops.twin_branch(ops._RECORDER is None):   # both encoders walk the same shapes side by side: half the K slices each
                 with torch.cuda.stream(self.side):
-                    cmid, cfeats = pipe.controlnet.encode(x, None, conv_in_residual=self.cemb)
-                mid, skips = pipe.unet.encode(x, None)
+                    cmid, cfeats = pipe.controlnet.encode(xe, None, conv_in_residual=ce, cfg_pair=pair)
+                mid, skips = pipe.unet.encode(xe, None, cfg_pair=pair)
             main.wait_stream(self.side)
-            skips2, mid2 = pipe.controlnet.zero_convs(cmid, cfeats, self.cscale, skips, mid)
+            skips2, mid2 = pipe.controlnet.zero_convs(cmid, cfeats, self.cscale, skips, mid, cfg_pair=pair)
         else:
-            mid, skips = pipe.unet.encode(x, None)
-            skips2, mid2 = pipe.controlnet.forward(x, None, self.cemb, self.cscale, skips, mid)
+            mid, skips = pipe.unet.encode(xe, None, cfg_pair=pair)
+            skips2, mid2 = pipe.controlnet.forward(xe, None, ce, self.cscale, skips, mid, cfg_pair=pair)
         pipe.unet.decode(mid2, skips2, None, out=self.eps)
         nimg = x.shape[0] // 2 if self.cfg else x.shape[0]
         nc, hw = pipe.cfgs["unet"]["out_channels"], x.shape[1] * x.shape[2]
@@ -221,6 +235,7 @@ class _StepGraph:
 
 class StableDiffusionControlNetPipeline:
     HAS_CONTROLNET = True
+    CFG_PREFIX = True                 # _sample() evaluates the CFG-shared encoder prefix once per image (cfg_prefix_enabled)
     SUPPORTS_FP16 = True              # enable_fp16(): built for the SD-1.5 pipelines (the BLIP-Diffusion and SDXL subclasses refuse it)
 
     def __init__(self, state_dicts, cfgs=SD15, tokenizer=None, scheduler=None):
@@ -399,6 +414,7 @@ class StableDiffusionControlNetPipeline:
         timesteps from index t_start of the `steps`-step schedule run (DDIM only)."""
         sch = self.scheduler
         nc = self.cfgs["unet"]["out_channels"]
+        pair = self.CFG_PREFIX and cfg_prefix_enabled()
         if t_start and isinstance(sch, PNDMScheduler):
             raise NotImplementedError("img2img runs on DDIM / UniPC (the reference switches non-BLIP pipelines away from PNDM)")
         if graphs_enabled():
@@ -412,7 +428,8 @@ class StableDiffusionControlNetPipeline:
                 ts, plan = [t for t, _ in plan], [r for _, r in plan]
             else:
                 ts, plan = list(sch.set_timesteps(steps))[t_start:], None
-            x2.copy_(self._step_graph(x2, cemb2, ctx, len(ts) if t_start else steps, True, guidance_scale, cscale, ts).run_on(x2, cemb2, ctx, ts, plan=plan))
+            x2.copy_(self._step_graph(x2, cemb2, ctx, len(ts) if t_start else steps, True, guidance_scale, cscale, ts,
+                                      cfg_pair=pair).run_on(x2, cemb2, ctx, ts, plan=plan))
             return
         nets = [self.unet] + ([self.controlnet] if self.controlnet is not None else [])
         for net in nets:
@@ -423,9 +440,15 @@ class StableDiffusionControlNetPipeline:
         twin_rec = rec is not None and getattr(rec, "twin", False) and self.controlnet is not None and fork_enabled()
         gate = torch.zeros(2, dtype=torch.int64, device=x2.device) if twin_rec else None
 
+        # (pair: the same launches as _StepGraph._step -- the encoders take the B rows the two CFG halves share)
+        xe = x2[:b] if pair else x2
+        ce = cemb2[:b] if pair and self.controlnet is not None else cemb2
+
         def evaluate(i):
             if self.controlnet is None:
-                mid, skips = self.unet.encode(x2, i)
+                mid, skips = self.unet.encode(xe, i, cfg_pair=pair)
+                if pair:
+                    skips[0] = ops.dup_rows(skips[0])
             elif twin_rec:
                 # a launch recorder that wants the TIMED path's dispatch (bench.Recorder(twin=True)): the two encoders on two streams
                 # with the shared-chip hint, as the captured step runs them.  Both streams are held behind one sleeping wave
@@ -436,21 +459,21 @@ class StableDiffusionControlNetPipeline:
                 rec.begin_twin()
                 with ops.twin_branch(True):
                     with torch.cuda.stream(side):
-                        cmid, cfeats = self.controlnet.encode(x2, i, conv_in_residual=cemb2)
-                    mid, skips = self.unet.encode(x2, i)
+                        cmid, cfeats = self.controlnet.encode(xe, i, conv_in_residual=ce, cfg_pair=pair)
+                    mid, skips = self.unet.encode(xe, i, cfg_pair=pair)
                 rec.end_twin()
                 main.wait_stream(side)
                 for t in (cmid, *cfeats):
                     t.record_stream(main)
-                skips, mid = self.controlnet.zero_convs(cmid, cfeats, cscale, skips, mid)
+                skips, mid = self.controlnet.zero_convs(cmid, cfeats, cscale, skips, mid, cfg_pair=pair)
             else:
                 # the same launches, with the same dispatch decisions, as the two-branch graph step (_StepGraph._step): the
                 # split-K of the paired encoders is sized for two concurrent branches (ops.twin_branch) -- except under a
                 # launch recorder, which times every launch ALONE and therefore gets the full-chip dispatch
                 with ops.twin_branch(fork_enabled() and ops._RECORDER is None):
-                    cmid, cfeats = self.controlnet.encode(x2, i, conv_in_residual=cemb2)
-                    mid, skips = self.unet.encode(x2, i)
-                skips, mid = self.controlnet.zero_convs(cmid, cfeats, cscale, skips, mid)
+                    cmid, cfeats = self.controlnet.encode(xe, i, conv_in_residual=ce, cfg_pair=pair)
+                    mid, skips = self.unet.encode(xe, i, cfg_pair=pair)
+                skips, mid = self.controlnet.zero_convs(cmid, cfeats, cscale, skips, mid, cfg_pair=pair)
             self.unet.decode(mid, skips, i, out=eps)
 
         if isinstance(sch, PNDMScheduler):
@@ -485,15 +508,15 @@ class StableDiffusionControlNetPipeline:
                 evaluate(i)
                 ops.cfg_ddim_step(eps, x2, b, hw, nc, guidance_scale, *sch.step_coefficients(t))
 
-    def _step_graph(self, x, cemb, ctx, steps, cfg, guidance, cscale, ts):
+    def _step_graph(self, x, cemb, ctx, steps, cfg, guidance, cscale, ts, cfg_pair=False):
         # the timesteps are part of the key: the cached time tables / coefficients follow the scheduler's configuration
         key = (tuple(x.shape), tuple(cemb.shape), tuple(ctx.shape), int(steps), bool(cfg), float(guidance), float(cscale), x.dtype,
-               type(self.scheduler).__name__, tuple(int(t) for t in ts))
+               type(self.scheduler).__name__, tuple(int(t) for t in ts), bool(cfg_pair))
         g = self._graphs.pop(key, None)
         if g is None:
             while len(self._graphs) >= 3:                   # each graph keeps one step's activations resident
                 self._graphs.pop(next(iter(self._graphs)))
-            g = _StepGraph(self, x.shape, cemb.shape, steps, cfg, guidance, cscale)
+            g = _StepGraph(self, x.shape, cemb.shape, steps, cfg, guidance, cscale, cfg_pair)
         self._graphs[key] = g                               # most recently used last
         return g
 
@@ -713,6 +736,7 @@ class StableDiffusionImg2ImgPipeline(StableDiffusionControlNetImg2ImgPipeline):
 
 class BlipDiffusionControlNetPipeline(StableDiffusionControlNetPipeline):
     SUPPORTS_FP16 = False
+    CFG_PREFIX = False                # (the multimodal context keeps today's evaluation)
     """Drop-in for diffusers' `BlipDiffusionControlNetPipeline` as the reference builds and calls it for every dataset
     but planes (run_aug/run_aug.py:181, :211, :243-250, :262-265, :521; SURVEY 8a a8):
 
@@ -815,6 +839,7 @@ class BlipDiffusionControlNetPipeline(StableDiffusionControlNetPipeline):
 
 class StableDiffusionXLControlNetPipeline(StableDiffusionControlNetPipeline):
     SUPPORTS_FP16 = False
+    CFG_PREFIX = False                # (with guidance the added conditioning differs between the halves)
     """Drop-in for diffusers' `StableDiffusionXLControlNetPipeline` as the reference builds and calls it for
     `BASE_MODEL = "sd_xl-turbo"` (its choice for CUB; run_aug/run_aug.py:189-201, :223-228, :564-571; SURVEY 8a a9):
 

@@ -345,6 +345,17 @@ int saspa_gather_row_f32(const float* table, long long row_elems, const int* ind
 int saspa_ddim_step_dev(int dtype, const void* eps, void* x, int nimg, long long hw, int C, int ldc, int cfg, float guidance,
                         const float* coefs, const int* index, void* stream);
 int saspa_index_add(int* index, int delta, void* stream);
+/* three-branch guidance + DDIM step (eta=0), fused: the InstructPix2Pix update.  eps, x: [3*nimg][hw][ldc] in the groups
+ * (uncond | image | text); x carries the noisy latents in channels c < C (C <= 4) and the image latents (zeros in group 0) above.
+ *   e = e0 + g (e2 - e1) + ig (e1 - e0); x0 = (x - sqrt(1-a_t) e)/sqrt(a_t); x' = sqrt(a_p) x0 + sqrt(1-a_p) e
+ * x is read from group 0; x' is written to channels c < C of all three groups, channels C..ldc-1 keep their bits.
+ * Errors before any launch: null pointer SASPA_EINVAL, alignment SASPA_EALIGN, ldc != 8 / C > 4 / nimg < 1 SASPA_ERANGE.
+ * _dev: the four coefficients come from row *index of coefs[steps][4], as saspa_ddim_step_dev. */
+int saspa_cfg3_ddim_step(int dtype, const void* eps, void* x, int nimg, long long hw, int C, int ldc, float guidance,
+                         float image_guidance, float sqrt_a_t, float sqrt_1m_a_t, float sqrt_a_prev, float sqrt_1m_a_prev,
+                         void* stream);
+int saspa_cfg3_ddim_step_dev(int dtype, const void* eps, void* x, int nimg, long long hw, int C, int ldc, float guidance,
+                             float image_guidance, const float* coefs, const int* index, void* stream);
 /* saspa_cfg_plms_step with its per-evaluation parameters read from row *index of table[evaluations][10] =
  * (store_slot, w_cur, w_hist[4], coef_sample, coef_model, save_sample, use_saved): the evaluation with save_sample copies
  * x into `saved` ([nimg][hw][ldc]) before the update, the one with use_saved reads it instead of x. */

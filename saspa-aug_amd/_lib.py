@@ -135,6 +135,8 @@ SYMBOLS = {
     "saspa_gather_row_f32": (_I, [_P, _LL, _P, _P, _LL, _P]),
     "saspa_ddim_step_dev": (_I, [_I, _P, _P, _I, _LL, _I, _I, _I, _F, _P, _P, _P]),
     "saspa_index_add": (_I, [_P, _I, _P]),
+    "saspa_cfg3_ddim_step": (_I, [_I, _P, _P, _I, _LL, _I, _I, _F, _F, _F, _F, _F, _F, _P]),
+    "saspa_cfg3_ddim_step_dev": (_I, [_I, _P, _P, _I, _LL, _I, _I, _F, _F, _P, _P, _P]),
     "saspa_clock_probe": (_I, [_P, _I, _P]),
     "saspa_cfg_plms_step_dev": (_I, [_I, _P, _P, _P, _P, _I, _LL, _I, _I, _F, _P, _P, _P]),
     "saspa_scale": (_I, [_I, _P, _P, _LL, _F, _P]),
@@ -187,8 +189,9 @@ F16_SYMBOL_NAMES = (
     "saspa_groupnorm_stats", "saspa_groupnorm_apply", "saspa_groupnorm_onepass_eligible", "saspa_groupnorm_onepass",
     "saspa_splitk_groupnorm_eligible", "saspa_splitk_groupnorm", "saspa_layernorm", "saspa_geglu", "saspa_activation",
     "saspa_embed_tokens", "saspa_embed_tokens_ctx", "saspa_cfg_plms_step", "saspa_cfg_plms_step_dev", "saspa_cfg_ddim_step",
-    "saspa_ddim_step", "saspa_ddim_step_dev", "saspa_cfg_unipc_step", "saspa_unipc_step", "saspa_vae_sample_noise", "saspa_scale",
-    "saspa_u8_to_act", "saspa_act_to_u8", "saspa_abi_version", "saspa_half_type", "saspa_build_arch",
+    "saspa_ddim_step", "saspa_ddim_step_dev", "saspa_cfg3_ddim_step", "saspa_cfg3_ddim_step_dev", "saspa_cfg_unipc_step", "saspa_unipc_step",
+    "saspa_vae_sample_noise", "saspa_scale", "saspa_u8_to_act", "saspa_act_to_u8", "saspa_abi_version", "saspa_half_type",
+    "saspa_build_arch",
 )
 
 _lib = None

@@ -23,6 +23,9 @@ CLIP_L = dict(vocab=49408, width=768, layers=12, heads=12, mlp=3072, max_pos=77)
 SAFETY_CHECKER = dict(image_size=224, patch=14, width=1024, layers=24, heads=16, mlp=4096, proj_dim=768, n_concepts=17,
                       n_special=3)
 SD15 = dict(unet=SD15_UNET, controlnet=SD15_CONTROLNET, vae=SD15_VAE, text=CLIP_L, safety=SAFETY_CHECKER)
+# timbrooks/instruct-pix2pix (run_aug/run_aug.py:46, :174-176): the SD-1.5 family without a ControlNet; the UNet's conv_in takes
+# 8 channels (4 noisy latents | 4 image latents).  Everything else recalled as SD-1.5's (no network here): parity unpinned.
+IP2P = dict({k: v for k, v in SD15.items() if k != "controlnet"}, unet=dict(SD15_UNET, in_channels=8))
 
 # stabilityai/sdxl-turbo (= SDXL-base architecture) : unet/config.json.  Three levels, no attention at level 0,
 # transformer_layers_per_block (1, 2, 10) -> "depth" (level 0 unused), attention_head_dim (5, 10, 20) = heads per
@@ -116,3 +119,9 @@ def tiny(width=32, ctx=64, groups=8, heads=4, vae_width=16):
                    proj_hidden=2 * ctx, out_dim=ctx)
     safety = dict(image_size=56, patch=14, width=64, layers=2, heads=4, mlp=128, proj_dim=48, n_concepts=17, n_special=3)
     return dict(unet=unet, controlnet=cn, vae=vae, text=text, qformer=qformer, ctx_begin_pos=2, safety=safety)
+
+
+def tiny_ip2p(**kw):
+    """`tiny()` as the InstructPix2Pix family: no ControlNet, 8 UNet input channels."""
+    t = tiny(**kw)
+    return dict({k: v for k, v in t.items() if k != "controlnet"}, unet=dict(t["unet"], in_channels=8))

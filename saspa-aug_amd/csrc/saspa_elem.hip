@@ -271,6 +271,47 @@ __global__ __launch_bounds__(256) void cfg_ddim_kernel(const T* eps, T* x, int n
   }
 }
 
+// Three-branch guidance + DDIM (eta = 0): the InstructPix2Pix update.  eps / x: [3 * nimg][hw][8] in the groups (uncond | image |
+// text); the UNet input carries the noisy latents in channels < C and the image latents (zeros in group 0) in channels C..7.
+//   e = e0 + g (e2 - e1) + ig (e1 - e0), then the DDIM step of cfg_ddim_kernel on e and the x of group 0.
+// One thread owns one pixel's word of each group: channels < C of all three groups get the new sample (fp32 arithmetic, one
+// rounding), channels C..7 are stored back as the bits that were loaded.  coefs / index: as cfg_ddim_kernel.
+template <typename T> struct alignas(16) Pixel8 { T v[8]; };
+template <typename T>
+__global__ __launch_bounds__(256) void cfg3_ddim_kernel(const T* eps, T* x, int nimg, long long hw, int C, float g, float ig,
+                                                        float sa_t, float s1m_t, float sa_p, float s1m_p,
+                                                        const float* coefs = nullptr, const int* index = nullptr) {
+  if (coefs) {
+    const float* c4 = coefs + 4ll * (*index);
+    sa_t = c4[0]; s1m_t = c4[1]; sa_p = c4[2]; s1m_p = c4[3];
+  }
+  const long long total = (long long)nimg * hw;
+  const long long group = total * 8;  // elements in one of the three groups
+  for (long long it = (long long)blockIdx.x * 256 + threadIdx.x; it < total; it += (long long)gridDim.x * 256) {
+    float e0[8], e1[8], e2[8];
+    load8(eps + it * 8, e0);
+    load8(eps + group + it * 8, e1);
+    load8(eps + 2 * group + it * 8, e2);
+    Pixel8<T> w0 = *reinterpret_cast<const Pixel8<T>*>(x + it * 8);
+    Pixel8<T> w1 = *reinterpret_cast<const Pixel8<T>*>(x + group + it * 8);
+    Pixel8<T> w2 = *reinterpret_cast<const Pixel8<T>*>(x + 2 * group + it * 8);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      if (j < C) {
+        const float e = e0[j] + g * (e2[j] - e1[j]) + ig * (e1[j] - e0[j]);
+        const float x0 = ((float)w0.v[j] - s1m_t * e) / sa_t;
+        const T o = (T)(sa_p * x0 + s1m_p * e);
+        w0.v[j] = o;
+        w1.v[j] = o;
+        w2.v[j] = o;
+      }
+    }
+    *reinterpret_cast<Pixel8<T>*>(x + it * 8) = w0;
+    *reinterpret_cast<Pixel8<T>*>(x + group + it * 8) = w1;
+    *reinterpret_cast<Pixel8<T>*>(x + 2 * group + it * 8) = w2;
+  }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void scale_kernel(const T* x, T* y, long long n8, float s) {
   for (long long it = (long long)blockIdx.x * 256 + threadIdx.x; it < n8; it += (long long)gridDim.x * 256) {
@@ -507,6 +548,46 @@ extern "C" int saspa_ddim_step_dev(int dtype, const void* eps, void* x, int nimg
   } else {
     return SASPA_EINVAL;
   }
+  SASPA_CHECK_LAUNCH();
+  return 0;
+}
+
+// host-side checks shared by the two entry points of cfg3_ddim_kernel (nothing is launched on a refusal)
+static int cfg3_ddim_check(int dtype, const void* eps, const void* x, int nimg, long long hw, int C, int ldc) {
+  if (!eps || !x || hw <= 0 || C <= 0) return SASPA_EINVAL;
+  if (!aligned16(eps) || !aligned16(x)) return SASPA_EALIGN;
+  if (ldc != 8 || C > 4 || nimg < 1) return SASPA_ERANGE;
+  if (!(dtype == SASPA_HALF || (dtype == SASPA_F32 && kServesF32))) return SASPA_EINVAL;
+  return 0;
+}
+
+extern "C" int saspa_cfg3_ddim_step(int dtype, const void* eps, void* x, int nimg, long long hw, int C, int ldc, float guidance,
+                                    float image_guidance, float sqrt_a_t, float sqrt_1m_a_t, float sqrt_a_prev,
+                                    float sqrt_1m_a_prev, void* stream) {
+  const int rc = cfg3_ddim_check(dtype, eps, x, nimg, hw, C, ldc);
+  if (rc) return rc;
+  if (!(sqrt_a_t > 0.f)) return SASPA_EINVAL;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const unsigned grid = grid_for((long long)nimg * hw);
+  if (dtype == SASPA_HALF)
+    hipLaunchKernelGGL(cfg3_ddim_kernel<h16_t>, dim3(grid), dim3(256), 0, s, (const h16_t*)eps, (h16_t*)x, nimg, hw, C, guidance, image_guidance, sqrt_a_t, sqrt_1m_a_t, sqrt_a_prev, sqrt_1m_a_prev);
+  else
+    hipLaunchKernelGGL(cfg3_ddim_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)eps, (float*)x, nimg, hw, C, guidance, image_guidance, sqrt_a_t, sqrt_1m_a_t, sqrt_a_prev, sqrt_1m_a_prev);
+  SASPA_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int saspa_cfg3_ddim_step_dev(int dtype, const void* eps, void* x, int nimg, long long hw, int C, int ldc, float guidance,
+                                        float image_guidance, const float* coefs, const int* index, void* stream) {
+  if (!coefs || !index) return SASPA_EINVAL;
+  const int rc = cfg3_ddim_check(dtype, eps, x, nimg, hw, C, ldc);
+  if (rc) return rc;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const unsigned grid = grid_for((long long)nimg * hw);
+  if (dtype == SASPA_HALF)
+    hipLaunchKernelGGL(cfg3_ddim_kernel<h16_t>, dim3(grid), dim3(256), 0, s, (const h16_t*)eps, (h16_t*)x, nimg, hw, C, guidance, image_guidance, 1.f, 0.f, 1.f, 0.f, coefs, index);
+  else
+    hipLaunchKernelGGL(cfg3_ddim_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)eps, (float*)x, nimg, hw, C, guidance, image_guidance, 1.f, 0.f, 1.f, 0.f, coefs, index);
   SASPA_CHECK_LAUNCH();
   return 0;
 }

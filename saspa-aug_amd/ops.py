@@ -1307,6 +1307,35 @@ def ddim_step_dev(eps, x, nimg, hw, c, guidance, coefs, index, cfg=True):
     return x
 
 
+def _cfg3_shapes(what, eps, x, nimg, hw):
+    _same_dtype(what, x, eps=eps)
+    if x.numel() != 3 * nimg * hw * 8 or eps.numel() != x.numel() or not x.is_contiguous() or not eps.is_contiguous():
+        raise ValueError(f"{what}: eps, x contiguous [3 * nimg, hw, 8]")
+
+
+def cfg3_ddim_step(eps, x, nimg, hw, c, guidance, image_guidance, sa_t, s1m_t, sa_p, s1m_p):
+    """eps, x: [3*nimg, hw, 8] in the groups (uncond | image | text): three-branch guidance (InstructPix2Pix) + DDIM.  Channels < c of
+    all three groups of x are updated in place; channels c..7 (the image latents) keep their bits."""
+    _check_dev(eps, x)
+    _cfg3_shapes("cfg3_ddim_step", eps, x, nimg, hw)
+    lib = _L(x)
+    _lib.check(lib.saspa_cfg3_ddim_step(_dt(x), _ptr(eps), _ptr(x), nimg, hw, c, 8, float(guidance), float(image_guidance), float(sa_t),
+                                        float(s1m_t), float(sa_p), float(s1m_p), _stream()), "saspa_cfg3_ddim_step")
+    return x
+
+
+def cfg3_ddim_step_dev(eps, x, nimg, hw, c, guidance, image_guidance, coefs, index):
+    """cfg3_ddim_step with the coefficients of row index[0] of the device table coefs [steps, 4]."""
+    _check_dev(eps, x, coefs, index)
+    _cfg3_shapes("cfg3_ddim_step_dev", eps, x, nimg, hw)
+    lib = _L(x)
+    if coefs.dtype != torch.float32 or coefs.dim() != 2 or coefs.shape[1] != 4 or not coefs.is_contiguous() or index.dtype != torch.int32:
+        raise ValueError("cfg3_ddim_step_dev: coefs fp32 [steps, 4], int32 index")
+    _lib.check(lib.saspa_cfg3_ddim_step_dev(_dt(x), _ptr(eps), _ptr(x), nimg, hw, c, 8, float(guidance), float(image_guidance),
+                                            _ptr(coefs), _ptr(index), _stream()), "saspa_cfg3_ddim_step_dev")
+    return x
+
+
 def cfg_plms_step_dev(eps, x, hist, saved, nimg, hw, c, guidance, table, index):
     """PLMS update with the evaluation's parameters read from row index[0] of the device table [evaluations, 10]."""
     _check_dev(eps, x, hist, saved, table, index)

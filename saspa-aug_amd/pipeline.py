@@ -26,7 +26,7 @@ from PIL import Image
 
 from . import models, ops
 from . import weights as W
-from .config import BLIP_DIFFUSION, BLIP_IMAGE_MEAN, BLIP_IMAGE_STD, SD15, SDXL_TURBO
+from .config import BLIP_DIFFUSION, BLIP_IMAGE_MEAN, BLIP_IMAGE_STD, IP2P, SD15, SDXL_TURBO
 from .scheduler import SDXL_TURBO_SCHEDULER_CONFIG, DDIMScheduler, PNDMScheduler, UniPCMultistepScheduler
 from .tokenizer import make_bert_tokenizer, make_tokenizer
 
@@ -75,10 +75,13 @@ class _StepGraph:
     Everything a step reads lives in static buffers owned by this object; what changes from step to step is read on the
     device through a step counter (time-embedding rows: ops.gather_row; DDIM coefficients: ops.ddim_step_dev)."""
 
-    def __init__(self, pipe, x_shape, cemb_shape, steps, cfg, guidance, cscale, cfg_pair=False):
+    def __init__(self, pipe, x_shape, cemb_shape, steps, cfg, guidance, cscale, cfg_pair=False, branches=2, image_guidance=1.0):
         dev, dt = pipe.device, pipe.dtype
         self.pipe, self.steps, self.cfg, self.guidance, self.cscale = pipe, steps, cfg, guidance, cscale
-        self.cfg_pair = bool(cfg and cfg_pair)      # the encoders' shared prefix once per image (cfg_prefix_enabled)
+        # branches = 3 (InstructPix2Pix): x holds the groups (uncond | image | text) and the update is ops.cfg3_ddim_step_dev; DDIM
+        # only, which _sample -- the one caller that passes 3 -- has checked
+        self.branches, self.image_guidance = int(branches), image_guidance
+        self.cfg_pair = bool(cfg and cfg_pair and self.branches == 2)   # the encoders' shared prefix once per image (cfg_prefix_enabled)
         self.x = torch.zeros(x_shape, device=dev, dtype=dt)
         self.eps = torch.zeros(x_shape, device=dev, dtype=dt)
         self.cemb = torch.zeros(cemb_shape, device=dev, dtype=dt)
@@ -177,9 +180,11 @@ class _StepGraph:
             mid, skips = pipe.unet.encode(xe, None, cfg_pair=pair)
             skips2, mid2 = pipe.controlnet.forward(xe, None, ce, self.cscale, skips, mid, cfg_pair=pair)
         pipe.unet.decode(mid2, skips2, None, out=self.eps)
-        nimg = x.shape[0] // 2 if self.cfg else x.shape[0]
+        nimg = x.shape[0] // self.branches if self.cfg else x.shape[0]
         nc, hw = pipe.cfgs["unet"]["out_channels"], x.shape[1] * x.shape[2]
-        if self.unipc and self.cfg:
+        if self.branches == 3:
+            ops.cfg3_ddim_step_dev(self.eps, x, nimg, hw, nc, self.guidance, self.image_guidance, self.coefs, self.idx)
+        elif self.unipc and self.cfg:
             ops.cfg_unipc_step(self.eps, x, self.state, nimg, hw, nc, self.guidance, table=self.coefs, index=self.idx)
         elif self.unipc:
             ops.unipc_step(self.eps, x, self.state, nimg, hw, nc, table=self.coefs, index=self.idx)
@@ -409,12 +414,15 @@ class StableDiffusionControlNetPipeline:
     def _positive_context(self, prompt_ids, query_embeds=None):
         return self.encode_prompts(prompt_ids)
 
-    def _sample(self, x2, b, hw, ctx, cemb2, steps, guidance_scale, cscale, t_start=0):
+    def _sample(self, x2, b, hw, ctx, cemb2, steps, guidance_scale, cscale, t_start=0, branches=2, image_guidance=1.0):
         """The denoising loop on the CFG-doubled latents x2 [2B,h,w,8] (in place).  t_start > 0 (img2img / SDEdit): only the
-        timesteps from index t_start of the `steps`-step schedule run (DDIM only)."""
+        timesteps from index t_start of the `steps`-step schedule run (DDIM only).  branches = 3 (InstructPix2Pix): x2 is
+        [3B,h,w,8] in the groups (uncond | image | text) and every update is ops.cfg3_ddim_step (DDIM only)."""
         sch = self.scheduler
         nc = self.cfgs["unet"]["out_channels"]
-        pair = self.CFG_PREFIX and cfg_prefix_enabled()
+        pair = self.CFG_PREFIX and cfg_prefix_enabled() and branches == 2
+        if branches == 3 and isinstance(sch, (PNDMScheduler, UniPCMultistepScheduler)):
+            raise NotImplementedError("three guidance branches (InstructPix2Pix) run on DDIM only")
         if t_start and isinstance(sch, PNDMScheduler):
             raise NotImplementedError("img2img runs on DDIM / UniPC (the reference switches non-BLIP pipelines away from PNDM)")
         if graphs_enabled():
@@ -428,8 +436,9 @@ class StableDiffusionControlNetPipeline:
                 ts, plan = [t for t, _ in plan], [r for _, r in plan]
             else:
                 ts, plan = list(sch.set_timesteps(steps))[t_start:], None
-            x2.copy_(self._step_graph(x2, cemb2, ctx, len(ts) if t_start else steps, True, guidance_scale, cscale, ts,
-                                      cfg_pair=pair).run_on(x2, cemb2, ctx, ts, plan=plan))
+            g = self._step_graph(x2, cemb2, ctx, len(ts) if t_start else steps, True, guidance_scale, cscale, ts, cfg_pair=pair,
+                                 branches=branches, image_guidance=image_guidance)
+            x2.copy_(g.run_on(x2, cemb2, ctx, ts, plan=plan))
             return
         nets = [self.unet] + ([self.controlnet] if self.controlnet is not None else [])
         for net in nets:
@@ -506,17 +515,20 @@ class StableDiffusionControlNetPipeline:
                 net.prepare_timesteps(ts)
             for i, t in enumerate(ts):
                 evaluate(i)
-                ops.cfg_ddim_step(eps, x2, b, hw, nc, guidance_scale, *sch.step_coefficients(t))
+                if branches == 3:
+                    ops.cfg3_ddim_step(eps, x2, b, hw, nc, guidance_scale, image_guidance, *sch.step_coefficients(t))
+                else:
+                    ops.cfg_ddim_step(eps, x2, b, hw, nc, guidance_scale, *sch.step_coefficients(t))
 
-    def _step_graph(self, x, cemb, ctx, steps, cfg, guidance, cscale, ts, cfg_pair=False):
+    def _step_graph(self, x, cemb, ctx, steps, cfg, guidance, cscale, ts, cfg_pair=False, branches=2, image_guidance=1.0):
         # the timesteps are part of the key: the cached time tables / coefficients follow the scheduler's configuration
         key = (tuple(x.shape), tuple(cemb.shape), tuple(ctx.shape), int(steps), bool(cfg), float(guidance), float(cscale), x.dtype,
-               type(self.scheduler).__name__, tuple(int(t) for t in ts), bool(cfg_pair))
+               type(self.scheduler).__name__, tuple(int(t) for t in ts), bool(cfg_pair), int(branches), float(image_guidance))
         g = self._graphs.pop(key, None)
         if g is None:
             while len(self._graphs) >= 3:                   # each graph keeps one step's activations resident
                 self._graphs.pop(next(iter(self._graphs)))
-            g = _StepGraph(self, x.shape, cemb.shape, steps, cfg, guidance, cscale, cfg_pair)
+            g = _StepGraph(self, x.shape, cemb.shape, steps, cfg, guidance, cscale, cfg_pair, branches, image_guidance)
         self._graphs[key] = g                               # most recently used last
         return g
 
@@ -730,6 +742,108 @@ class StableDiffusionImg2ImgPipeline(StableDiffusionControlNetImg2ImgPipeline):
         ids = self.tokenizer(str(prompt))
         neg = self.tokenizer(negative_prompt if negative_prompt is not None else "")
         out = self.generate_batch_img2img(ids, neg, src[None], e1, e2, num_inference_steps, strength, guidance_scale)
+        nsfw = None if self.last_nsfw is None else [bool(v) for v in self.last_nsfw.cpu().tolist()]
+        return PipelineOutput([Image.fromarray(a) for a in out.cpu().numpy()], nsfw)
+
+
+class StableDiffusionInstructPix2PixPipeline(StableDiffusionImg2ImgPipeline):
+    """Drop-in for diffusers' `StableDiffusionInstructPix2PixPipeline` -- the reference's BASE_MODEL = "ip2p" branch
+    (run_aug/run_aug.py:174-176; the editing model of the ALIA baseline), called as `pipe(prompt, image=<source PIL>,
+    image_guidance_scale=1.3, num_inference_steps=100, generator, guidance_scale, negative_prompt)` (:235-241, :252-255).
+    The UNet's conv_in takes 8 channels: the noisy latents and, next to them, the latents of the source image -- the MODE of the
+    VAE posterior (the mean; no draw), not multiplied by the scaling factor.  One `randn` per image, as in text-to-image.  Every
+    step evaluates the UNet on three groups, unconditional first like the other pipelines here:
+
+        group 0  negative prompt   x | 0
+        group 1  negative prompt   x | image latents
+        group 2  prompt            x | image latents
+
+    and e = e0 + gs (e2 - e1) + igs (e1 - e0) goes through the DDIM step (ops.cfg3_ddim_step: one launch, which also leaves the
+    image-latent channels of the input as they are).  DDIM only; bf16 or fp32 (no fp16 / fp8 compute: untested on three groups)."""
+    CFG_PREFIX = False                # (three groups: the pair prefix does not apply)
+    SUPPORTS_FP16 = False
+
+    def __init__(self, state_dicts, cfgs=IP2P, tokenizer=None, scheduler=None):
+        super().__init__(state_dicts, cfgs, tokenizer, scheduler)
+
+    @classmethod
+    def from_synthetic(cls, cfgs=IP2P, seed=0):
+        return cls(W.synth_family(cfgs, seed), cfgs)
+
+    @classmethod
+    def from_pretrained(cls, base_dir, cfgs=IP2P):
+        return super().from_pretrained(base_dir, cfgs)
+
+    def enable_fp8(self, on=True, convs=False):
+        raise NotImplementedError("enable_fp8() is not built for StableDiffusionInstructPix2PixPipeline (three guidance groups)")
+
+    def to(self, device, dtype=None):
+        if os.environ.get("SASPA_FP8", "0") == "1":
+            raise NotImplementedError("fp8 (SASPA_FP8=1) is not built for StableDiffusionInstructPix2PixPipeline")
+        return super().to(device, dtype)
+
+    def generate_batch_img2img(self, *a, **k):
+        raise NotImplementedError("the InstructPix2Pix UNet takes the image latents as input channels: use generate_batch_ip2p")
+
+    @torch.no_grad()
+    def generate_batch_ip2p(self, prompt_ids, negative_ids, source_u8, latents, num_inference_steps, guidance_scale=7.5,
+                            image_guidance_scale=1.5, return_latents=False):
+        """source_u8: u8 [B,H,W,3] (numpy or device); latents: [B,4,H/8,W/8] CPU noise, one draw per image.
+        Returns a device u8 tensor [B,H,W,3]."""
+        self._need_device()
+        if not (guidance_scale > 1.0 and image_guidance_scale >= 1.0):
+            raise NotImplementedError("guidance is on for guidance_scale > 1 and image_guidance_scale >= 1; the guidance-free "
+                                      "form (one evaluation per step) is not built")
+        dev, dt = self.device, self.dtype
+        src = source_u8 if torch.is_tensor(source_u8) else torch.from_numpy(np.array(source_u8))
+        src = ops.h2d(src, dev).contiguous()
+        b, hh, ww, _ = src.shape
+        mult = 8 << (len(self.cfgs["unet"]["block_out"]) - 1)
+        if hh % mult or ww % mult:
+            raise ValueError(f"image sides must be multiples of {mult} (got {hh}x{ww})")
+        h8, w8 = hh // 8, ww // 8
+        nl = self.cfgs["vae"]["latent_channels"]
+        if tuple(latents.shape) != (b, nl, h8, w8):
+            raise ValueError(f"latents shape {tuple(latents.shape)} does not match the source image {hh}x{ww}")
+        from . import imageproc
+        px = imageproc.normalize_u8(src, self.vae_encoder.dtype, (0.5, 0.5, 0.5), (0.5, 0.5, 0.5))     # [0,255] -> [-1,1]
+        with ops.f32_gemm_mode(self.vae.f32_gemm):
+            moments = self.vae_encoder.encode(px).to(dt)            # mean in channels 0..3: latent_dist.mode()
+        x = self.latents_to_device(latents)
+        # the UNet input of the three groups, built once: the sampling step rewrites channels < 4 only
+        x3 = torch.zeros((3, b, h8, w8, 8), device=dev, dtype=dt)
+        x3[..., :nl] = x[..., :nl]
+        x3[1:, ..., nl:2 * nl] = moments[..., :nl]
+        x3 = x3.view(3 * b, h8, w8, 8)
+        pos = self._positive_context(prompt_ids)
+        neg = self._negative_context(negative_ids)
+        if neg.shape[0] == 1 and b > 1:
+            neg = neg.expand(b, -1, -1)
+        ctx = torch.cat([neg, neg, pos], 0).contiguous()             # [3B,77,C]: uncond | image | text
+        cemb = torch.zeros((1,), device=dev, dtype=dt)               # placeholder: nothing reads it
+        self._sample(x3, b, h8 * w8, ctx, cemb, num_inference_steps, guidance_scale, 0.0, branches=3,
+                     image_guidance=image_guidance_scale)
+        # (group 0 carries zeros next to the latents: the layout the VAE decoder takes)
+        img = self.vae.decode(ops.scale(x3[:b], 1.0 / self.cfgs["vae"]["scaling_factor"]).to(self.vae.dtype))
+        out, self.last_nsfw = self.run_safety_checker(ops.act_to_u8(img))
+        if return_latents:
+            return out, x3[:b], img
+        return out
+
+    def __call__(self, prompt=None, image=None, num_inference_steps=100, generator=None, guidance_scale=7.5,
+                 image_guidance_scale=1.5, negative_prompt=None, **unused):
+        self._need_device()
+        if image is None or prompt is None:
+            raise ValueError("`prompt` and `image` (the image to edit) are required")
+        src = np.asarray(image.convert("RGB") if isinstance(image, Image.Image) else image, dtype=np.uint8)
+        hh, ww = src.shape[:2]
+        if generator is not None and generator.device.type != "cpu":
+            raise NotImplementedError("the reference passes the global CPU generator (run_aug/run_aug.py:324)")
+        # (the noise has the VAE's latent channels, not the UNet's 8 input channels)
+        lat = torch.randn((1, self.cfgs["vae"]["latent_channels"], hh // 8, ww // 8), generator=generator, dtype=self.noise_dtype)
+        ids = self.tokenizer(str(prompt))
+        neg = self.tokenizer(negative_prompt if negative_prompt is not None else "")
+        out = self.generate_batch_ip2p(ids, neg, src[None], lat, num_inference_steps, guidance_scale, image_guidance_scale)
         nsfw = None if self.last_nsfw is None else [bool(v) for v in self.last_nsfw.cpu().tolist()]
         return PipelineOutput([Image.fromarray(a) for a in out.cpu().numpy()], nsfw)
 

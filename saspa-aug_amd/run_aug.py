@@ -47,6 +47,9 @@ BASE_MODEL_DICT = {
 }
 CONTROLNET_DICT_SD = {"canny": "lllyasviel/control_v11p_sd15_canny", "hed": "lllyasviel/sd-controlnet-hed"}
 CONTROLNET_DICT_SD_XL = {"canny": "diffusers/controlnet-canny-sdxl-1.0"}
+# run_aug/run_aug.py:253-254: what ALIA used for biased planes; pass_thorugh_pipe and the batched loop both apply them to ip2p
+IP2P_IMAGE_GUIDANCE_SCALE = 1.3
+IP2P_NUM_INFERENCE_STEPS = 100
 
 
 def _save_png(arr, path):
@@ -318,11 +321,32 @@ def init_pipeline(base_model, controlnet, SDEdit, use_compile=False, sampler="dd
             pipe = StableDiffusionImg2ImgPipeline.from_synthetic(cfgs, seed=0)
         pipe.scheduler = _scheduler_for(pipe)
         return pipe
+    if base_model == "ip2p":
+        # run_aug/run_aug.py:174-176: StableDiffusionInstructPix2PixPipeline (the ALIA baseline's editing model), built in the
+        # ControlNet-free branch only; scheduler switched like every non-BLIP pipeline (:216-221)
+        from .config import IP2P
+        from .pipeline import StableDiffusionInstructPix2PixPipeline
+        if controlnet is not None or SDEdit:
+            raise NotImplementedError(f"(ip2p, {controlnet}, SDEdit={SDEdit}): InstructPix2Pix is built without a ControlNet and "
+                                      "without SDEdit (the reference's ControlNet branch has no ip2p pipeline)")
+        if sampler == "unipcmultistep":
+            raise NotImplementedError("ip2p with sampler='unipcmultistep' is not built: the three-branch guidance step is DDIM only")
+        cfgs = cfgs or IP2P
+        if state_dicts is not None:
+            pipe = StableDiffusionInstructPix2PixPipeline(state_dicts, cfgs)
+        elif weights_dir:
+            pipe = StableDiffusionInstructPix2PixPipeline.from_pretrained(os.path.join(weights_dir, BASE_MODEL_DICT[base_model]), cfgs)
+        else:
+            logging.info("no WEIGHTS_DIR given: using architecture-exact SYNTHETIC weights (no checkpoint available offline)")
+            pipe = StableDiffusionInstructPix2PixPipeline.from_synthetic(cfgs, seed=0)
+        pipe.scheduler = _scheduler_for(pipe)
+        return pipe
     if base_model != "sd_v1.5" or controlnet not in CONTROLNET_DICT_SD:
         raise NotImplementedError(
             f"({base_model}, {controlnet}, SDEdit={SDEdit}): sd_v1.5 (text-to-image and SDEdit img2img with the canny or HED "
-            "ControlNet; ControlNet-free SDEdit img2img), blip_diffusion and sd_xl-turbo with the canny ControlNet are built; "
-            "ip2p / blip_diffusion-edit / sd_v2.1 / sd_xl and the ControlNet-free text-to-image pipelines are baseline branches")
+            "ControlNet; ControlNet-free SDEdit img2img), blip_diffusion and sd_xl-turbo with the canny ControlNet, and ip2p without "
+            "a ControlNet are built; blip_diffusion-edit / sd_v2.1 / sd_xl and the ControlNet-free text-to-image pipelines are "
+            "baseline branches")
     cfgs = cfgs or SD15
     if SDEdit:                                  # run_aug/run_aug.py:203-206: StableDiffusionControlNetImg2ImgPipeline
         from .pipeline import StableDiffusionControlNetImg2ImgPipeline as _Cls
@@ -346,9 +370,11 @@ def pass_thorugh_pipe(base_model, pipe, prompt, orig_img, SDEdit, SDEdit_strengt
     """Single-variant call form of the reference (name kept, typo included)."""
     pipe_args = {"prompt": str(prompt), "num_inference_steps": num_inference_steps, "generator": generator,
                  "guidance_scale": guidance_scale, "negative_prompt": negative_prompt}
-    if "ip2p" in base_model or base_model == "blip_diffusion-edit" or (control_image is None and not SDEdit):
-        raise NotImplementedError("built call forms: ControlNet text-to-image / SDEdit img2img / BLIP-Diffusion, and the "
-                                  "ControlNet-free SDEdit img2img (Real-Guidance)")
+    ip2p = "ip2p" in base_model
+    built = (control_image is None and not SDEdit) if ip2p else (control_image is not None or SDEdit)
+    if base_model == "blip_diffusion-edit" or not built:
+        raise NotImplementedError("built call forms: ControlNet text-to-image / SDEdit img2img / BLIP-Diffusion, the "
+                                  "ControlNet-free SDEdit img2img (Real-Guidance) and ControlNet-free InstructPix2Pix")
     if "blip_diffusion" in base_model:                     # run_aug/run_aug.py:243-250
         pipe_args["reference_image"] = orig_img
         pipe_args["source_subject_category"] = blip_src_category
@@ -357,6 +383,10 @@ def pass_thorugh_pipe(base_model, pipe, prompt, orig_img, SDEdit, SDEdit_strengt
         pipe_args["width"] = orig_img.size[0]
         pipe_args["neg_prompt"] = NEGATIVE_PROMPT
         del pipe_args["negative_prompt"]
+    if ip2p:                                               # :252-255
+        pipe_args["image_guidance_scale"] = IP2P_IMAGE_GUIDANCE_SCALE
+        pipe_args["num_inference_steps"] = IP2P_NUM_INFERENCE_STEPS
+        pipe_args["image"] = orig_img
     if control_image is not None:
         if SDEdit:                                         # :252-255 the img2img pipelines name the control image differently
             pipe_args["control_image"] = control_image
@@ -652,6 +682,9 @@ def hip_batch_generator(pipe, s: Settings):
     neg_ids = tok(NEGATIVE_PROMPT)
 
     blip = "blip_diffusion" in s.BASE_MODEL
+    ip2p = "ip2p" in s.BASE_MODEL
+    if ip2p and (s.CONTROLNET or s.SDEDIT):
+        raise NotImplementedError("ip2p is built without a ControlNet and without SDEdit")
     hed = make_hed_detector(s, pipe.device) if s.CONTROLNET == "hed" else None
 
     side = torch.cuda.Stream(device=pipe.device)
@@ -690,6 +723,11 @@ def hip_batch_generator(pipe, s: Settings):
             q = pipe.get_query_embeddings(refs, [category] * len(batch))
             ids = np.concatenate([tok(pipe.build_prompt(it.prompt, category), max_len=pipe.prompt_token_count()) for it in batch])
             out = pipe.generate_batch(ids, neg_ids, ctrl, lat, s.NUM_INFERENCE_STEPS, s.GUIDANCE_SCALE, 1.0, query_embeds=q)
+        elif ip2p:
+            # InstructPix2Pix (run_aug/run_aug.py:252-255): the source image is the edited image, one draw per item, ALIA's step count
+            # and image guidance scale
+            ids = np.concatenate([tok(it.prompt) for it in batch])
+            out = pipe.generate_batch_ip2p(ids, neg_ids, src, lat, IP2P_NUM_INFERENCE_STEPS, s.GUIDANCE_SCALE, IP2P_IMAGE_GUIDANCE_SCALE)
         elif s.SDEDIT:
             # SDEdit (run_aug/run_aug.py:252-260, :274-276): img2img from the source image itself, two draws per item
             ids = np.concatenate([tok(it.prompt) for it in batch])

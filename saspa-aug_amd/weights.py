@@ -513,7 +513,8 @@ def synth_state_dict(kind, cfg, seed=0):
 def synth_family(cfgs, seed=0):
     kinds = ("unet", "controlnet", "vae", "text") + (("qformer",) if "qformer" in cfgs else ()) + \
         (("text2",) if "text2" in cfgs else ()) + (("safety",) if "safety" in cfgs else ())
-    fam = {k: synth_state_dict(k, cfgs[k], seed + i) for i, k in enumerate(kinds)}
+    # (a family without a ControlNet -- config.IP2P -- keeps the other networks' seeds; any other missing network is a KeyError)
+    fam = {k: synth_state_dict(k, cfgs[k], seed + i) for i, k in enumerate(kinds) if k != "controlnet" or k in cfgs}
     # the checkpoint's vae/ file holds encoder AND decoder: the encoder half (SDEdit / img2img) gets its own seed so the
     # decoder tensors are unchanged
     fam["vae"].update(synth_state_dict("vae_enc", cfgs["vae"], seed + 100))

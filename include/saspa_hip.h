@@ -89,7 +89,17 @@ typedef struct SaspaGemmParams {
   int batch, hin, win;       /* stored input extent */
   int hout, wout;            /* output extent */
   int kh, kw, stride, pad;   /* kernel window */
-  int upsample;              /* 1: conv sees the input nearest-upsampled x2 */
+  int upsample;              /* 1: conv sees the input nearest-upsampled x2.
+                              * 2: PHASE MODE of the same layer (nearest x2 + 3x3 / pad 1), 4/9 of the multiply-accumulates: output
+                              * pixel (2i+py, 2j+px) is a 2x2 correlation over the low-res input whose window starts at
+                              * (i+py-1, j+px-1) (zero padding carries over) and whose weights are sums of the 3x3 taps -- rows
+                              * {0}, {1, 2} for py = 0 and {0, 1}, {2} for py = 1, columns alike.  The caller passes kh = kw = 2,
+                              * stride = 1, pad = 1, hout = 2 hin, wout = 2 win, M = batch*hout*wout, K = 4 c0 and `w` = the four
+                              * phase matrices [py*2+px][N][ldw], each a 2x2 conv packed in `korder`; ONE launch (the phase is the
+                              * kernels' batched dimension, every row tile lies in one phase, the epilogue and the split-K reduce
+                              * scatter the rows to their pixels).  16-bit types, one source, no residual / rowvec / GEGLU /
+                              * defer_reduce: SASPA_ERANGE otherwise.  gn_stats: as usual; where hin*win % 128 != 0 only a launch
+                              * on K slices can key them (saspa_gemm_suggest_ksplit answers >= 2, SASPA_ERANGE without slabs). */
   const void* w;             /* [N][K] */
   int ldw;                   /* row pitch of w, elements */
   int M, N, K;               /* M = batch*hout*wout, K = kh*kw*(c0+c1) */

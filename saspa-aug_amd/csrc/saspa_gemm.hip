@@ -84,7 +84,9 @@ template <> struct is_x3<f32x3_t> { static constexpr bool value = true; };
 // residual read) are whole 16-byte chunks of contiguous output rows; GEGLU pairs the value /
 // gate halves there.  fp32 parity mode / odd N: direct per-lane path.
 // The caller guarantees every wave has finished reading the K-loop's LDS stages.
-template <typename T, int WM, int WN, int NWM = 2, int NWN = 2>
+// PH: phase mode of the nearest-x2 conv (SaspaGemmParams.upsample = 2) -- a template parameter here and in the kernels, so that the
+// instantiations every other launch runs are the code they were.
+template <typename T, int WM, int WN, int NWM = 2, int NWN = 2, bool PH = false>
 __device__ __forceinline__ void gemm_epilogue(const SaspaGemmParams& p, f32x4 (&acc)[WM][WN], u32x4* lds, const int cbm,
                                               const int cbn, const long long ooff) {
   constexpr int BM = 16 * WM * NWM, BN = 16 * WN * NWN, NT = 64 * NWM * NWN;
@@ -99,9 +101,19 @@ __device__ __forceinline__ void gemm_epilogue(const SaspaGemmParams& p, f32x4 (&
   const bool geglu = p.act == SASPA_ACT_GEGLU;
   const bool staged = sizeof(T) == 2 && (p.N % 8) == 0 && (p.ldo % 8) == 0 && (!res || (p.ldr % 8) == 0) &&
                       (!geglu || (p.N % BN) == 0);
+  // phase mode (lowered by saspa_gemm: blockIdx.z = phase (py, px), rows = low-res pixels): row (b, i, j) is pixel
+  // (b, 2i + py, 2j + px) of the output
+  const int phz = PH ? (int)blockIdx.z : 0;
+  auto orow = [&](const int m) __attribute__((always_inline)) -> long long {
+    if (!PH) return m;
+    const int b = m / hw, rem = m - b * hw;
+    const int i = rem / p.wout, j = rem - i * p.wout;
+    return (long long)(b * 2 * p.hout + 2 * i + (phz >> 1)) * (2 * p.wout) + 2 * j + (phz & 1);
+  };
     if (gridDim.y > 1) {
       // ---- split-K: raw fp32 partial slab, epilogue happens in the reduce launch ----
-      float* ws = p.workspace + (long long)blockIdx.y * p.M * p.N;
+      // (phase mode: slabs are [slice][phase][row of the phase][N]; the reduce launch gathers them per output pixel)
+      float* ws = p.workspace + (long long)(PH ? blockIdx.y * 4 + phz : blockIdx.y) * p.M * p.N;
 #pragma unroll
       for (int i = 0; i < WM; ++i) {
         const int m = cbm * BM + wm * (16 * WM) + i * 16 + frow;
@@ -189,7 +201,7 @@ __device__ __forceinline__ void gemm_epilogue(const SaspaGemmParams& p, f32x4 (&
           c4 = __builtin_bit_cast(u32x4, pack8(a));
           if (p.gn_stats) *reinterpret_cast<u32x4*>(ct + row * CP + ch * 8) = c4;   // the statistics read the STORED values
         }
-        *reinterpret_cast<u32x4*>(out + (long long)m * p.ldo + n) = c4;
+        *reinterpret_cast<u32x4*>(out + orow(m) * p.ldo + n) = c4;
       }
       if constexpr (sizeof(T) == 2) if (p.gn_stats) {
         // GroupNorm statistics of this tile's row block (SaspaGemmParams.gn_stats): BM = 128 rows = one block
@@ -201,9 +213,13 @@ __device__ __forceinline__ void gemm_epilogue(const SaspaGemmParams& p, f32x4 (&
         for (int hb = 0; hb < (BM + 127) / 128; ++hb) {
           const int r0 = hb * 128;
           const int nrows = min(128, min(BM, p.M - cbm * BM) - r0);
-          if (nrows > 0)
+          if (nrows > 0) {
+            // phase mode (whole 128-row blocks per low-res image, plan_gemm): image b's 4 * hw / 128 slots, phase-major
+            const int r128 = (cbm * BM + r0) / 128, nlo = hw >> 7;
+            const int rb = PH ? (r128 / nlo * 4 + phz) * nlo + r128 % nlo : r128;
             gn_tile_stats<NT>(reinterpret_cast<const h16_t*>(ct) + r0 * CP, CP, nrows, nunits, p.gn_unit, scratch,
-                              p.gn_stats + (((long long)(cbm * BM + r0) / 128) * (p.N / p.gn_unit) + (cbn * BN) / p.gn_unit) * 2);
+                              p.gn_stats + ((long long)rb * (p.N / p.gn_unit) + (cbn * BN) / p.gn_unit) * 2);
+          }
           if (hb + 1 < (BM + 127) / 128) __syncthreads();
         }
       }
@@ -254,7 +270,7 @@ __device__ __forceinline__ void gemm_epilogue(const SaspaGemmParams& p, f32x4 (&
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = act_post(p.act, v[r]);
-        Elem<T>::store4(out + (long long)m * p.ldo + n, v);
+        Elem<T>::store4(out + orow(m) * p.ldo + n, v);
       } else {
         for (int r = 0; r < 4 && n + r < p.N; ++r) {
           float x = v[r];
@@ -262,7 +278,7 @@ __device__ __forceinline__ void gemm_epilogue(const SaspaGemmParams& p, f32x4 (&
           if (rv) x += rv[n + r];
           x = act_pre(p.act, x * p.alpha);
           if (res) x += Elem<T>::load1(res + (long long)m * p.ldr + n + r);
-          Elem<T>::store1(out + (long long)m * p.ldo + n + r, act_post(p.act, x));
+          Elem<T>::store1(out + orow(m) * p.ldo + n + r, act_post(p.act, x));
         }
       }
     }
@@ -276,7 +292,7 @@ __device__ __forceinline__ void gemm_epilogue(const SaspaGemmParams& p, f32x4 (&
 // remap of the block id, G = gridDim.x).  The global loads of the NEXT tile's first two
 // K-tiles are issued before the current tile's epilogue, so workgroups stream continuously
 // instead of loading / storing in lock-step bursts (short-K layers are memory-bound).
-template <typename T, int WM, int WN, bool PW>
+template <typename T, int WM, int WN, bool PW, bool PH = false>
 __global__ __launch_bounds__(256, 2) void gemm_kernel(const SaspaGemmParams p, const int ntiles, const int npart8) {
   constexpr int BM = 32 * WM, BN = 32 * WN;
   constexpr int EPC = Elem<T>::EPC;
@@ -327,9 +343,12 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const SaspaGemmParams p, c
   const int r0 = tid >> 3;  // rows r0 + 32*i
   const int hw = p.hout * p.wout;
   const int ctot = p.c0 + p.c1;
-  const int hv = p.upsample ? 2 * p.hin : p.hin;
-  const int wv = p.upsample ? 2 * p.win : p.win;
-  const bool fast = (ctot % BK) == 0 && (p.c1 == 0 || (p.c0 % BK) == 0) && !p.upsample;
+  const int up = PH ? 0 : p.upsample;              // nearest-x2 input (phase mode reads the stored low-res input)
+  const int hv = up ? 2 * p.hin : p.hin;
+  const int wv = up ? 2 * p.win : p.win;
+  const bool fast = (ctot % BK) == 0 && (p.c1 == 0 || (p.c0 % BK) == 0) && !up;
+  // phase mode (PH: upsample = 2, blockIdx.z = phase (py, px)): a 2x2 window with pad (1 - py, 1 - px) over the low-res grid
+  const int pady = PH ? p.pad - (z >> 1) : p.pad, padx = PH ? p.pad - (z & 1) : p.pad;
   const rsrc_t rs0 = make_rsrc(a0);
   const rsrc_t rs1 = make_rsrc(p.c1 > 0 ? (const void*)a1 : (const void*)a0);
   const rsrc_t rsw = make_rsrc(w);
@@ -371,7 +390,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const SaspaGemmParams p, c
       int ox = rem - oy * p.wout;
 #pragma unroll
       for (int i = 0; i < A_CH; ++i) {
-        const int iy0 = oy * p.stride - p.pad, ix0 = ox * p.stride - p.pad;
+        const int iy0 = oy * p.stride - pady, ix0 = ox * p.stride - padx;
         if (fast) {
           // centre pixel of the window and the validity bit of every tap
           row_a[i] = b * p.hin * p.win + (oy * p.stride) * p.win + ox * p.stride;
@@ -426,7 +445,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const SaspaGemmParams p, c
       const int ldsz = (s0 ? p.lda0 : p.lda1) * SZ;
       const unsigned soff = (unsigned)((s0 ? cu : cu - p.c0) * SZ);
       const int tapbit = dyu * p.kw + dxu;
-      const int pixoff = PW ? 0 : (dyu - p.pad) * p.win + (dxu - p.pad);
+      const int pixoff = PW ? 0 : (dyu - pady) * p.win + (dxu - padx);
 #pragma unroll
       for (int i = 0; i < A_CH; ++i) {
         const unsigned off = (unsigned)((row_a[i] + pixoff) * ldsz + kc * 16);
@@ -458,7 +477,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const SaspaGemmParams p, c
         } else {
           int iy = row_a[i] + dy, ix = row_b[i] + dx;
           inb = kvalid && (unsigned)iy < (unsigned)hv && (unsigned)ix < (unsigned)wv;
-          if (p.upsample) { iy >>= 1; ix >>= 1; }
+          if (up) { iy >>= 1; ix >>= 1; }
           off = (unsigned)(((row_c[i] + iy * p.win + ix) * ld + cc) * SZ);
         }
         u32x4 v = buf_load(rs0, (inb && s0) ? off : kInvalid, 0u);
@@ -545,7 +564,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const SaspaGemmParams p, c
       if (nk > 1) load_tile(ra1, rb1);
     }
 
-    gemm_epilogue<T, WM, WN>(p, acc, lds, cbm, cbn, ooff);
+    gemm_epilogue<T, WM, WN, 2, 2, PH>(p, acc, lds, cbm, cbn, ooff);
     if (!has_next) break;
     tile = next;
     __syncthreads();   // LDS reads of the staged epilogue are done before the next tile's first store
@@ -564,7 +583,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const SaspaGemmParams p, c
 
 // UP (nearest-x2 input) is a template parameter: as a run-time flag it put one scalar branch in front of every A-piece
 // DMA of every 3x3 conv's K-tile (4 per K-tile on the 128-row tile), and this issue path does not forgive branches.
-template <typename T, int WM, int WN, int NWM, int NWN, bool PW, int NSTAGE, bool UP = false>
+template <typename T, int WM, int WN, int NWM, int NWN, bool PW, int NSTAGE, bool UP = false, bool PH = false>
 __global__ __launch_bounds__(64 * NWM * NWN, (NWM * NWN == 4 && NSTAGE > 2) ? 1 : 2) void gemm_dma_kernel(const SaspaGemmParams p,
                                                                                                       const int ntiles_abl, const int npart8) {
   // diagnostic ablation (tools/gemm_ablate.py only; 0 in production): bits 28..30 of the tile count
@@ -627,6 +646,8 @@ __global__ __launch_bounds__(64 * NWM * NWN, (NWM * NWN == 4 && NSTAGE > 2) ? 1 
   // is then one add of the (wave-uniform) tap offset instead of a 64-bit multiply-add per piece and K-tile
   unsigned offa0[A_CH], offa1[A_CH];
   const int hv = UP ? 2 * p.hin : p.hin, wv = UP ? 2 * p.win : p.win;
+  // phase mode (PH: upsample = 2, blockIdx.z = phase (py, px)): a 2x2 window with pad (1 - py, 1 - px) over the low-res grid
+  const int pady = PH ? p.pad - (z >> 1) : p.pad, padx = PH ? p.pad - (z & 1) : p.pad;
   unsigned offb[B_CH];
   int ku = 0, cu = 0, dyu = 0, dxu = 0;
 
@@ -663,7 +684,7 @@ __global__ __launch_bounds__(64 * NWM * NWN, (NWM * NWN == 4 && NSTAGE > 2) ? 1 
       int ox = rem - oy * p.wout;
 #pragma unroll
       for (int i = 0; i < A_CH; ++i) {
-        const int iy0 = oy * p.stride - p.pad, ix0 = ox * p.stride - p.pad;
+        const int iy0 = oy * p.stride - pady, ix0 = ox * p.stride - padx;
         if (UP) {
           // nearest x2: the window walks the virtual 2H x 2W grid; keep its top-left corner
           // (packed y | x) and resolve the source pixel ((iy0+dy)>>1, (ix0+dx)>>1) per tap
@@ -715,7 +736,7 @@ __global__ __launch_bounds__(64 * NWM * NWN, (NWM * NWN == 4 && NSTAGE > 2) ? 1 
     const int ldsz = (s0 ? p.lda0 : p.lda1) * SZ;
     const int soff = (s0 ? cu : cu - p.c0) * SZ;
     const int tapbit = dyu * p.kw + dxu;
-    const int pixoff = PW ? 0 : (dyu - p.pad) * p.win + (dxu - p.pad);
+    const int pixoff = PW ? 0 : (dyu - pady) * p.win + (dxu - padx);
     const unsigned tapoff = (unsigned)(pixoff * ldsz);
     u32x4* la = lds + stage * STAGE;
     u32x4* lb = la + BM * 8;
@@ -855,15 +876,26 @@ __global__ __launch_bounds__(64 * NWM * NWN, (NWM * NWN == 4 && NSTAGE > 2) ? 1 
     const int next = tile + G;
     const bool has_next = next < ntiles;
     if (has_next) setup_tile(next);
-    gemm_epilogue<T, WM, WN, NWM, NWN>(p, acc, lds, cbm, cbn, ooff);
+    gemm_epilogue<T, WM, WN, NWM, NWN, PH>(p, acc, lds, cbm, cbn, ooff);
     if (!has_next) break;
     tile = next;
     __syncthreads();   // staged epilogue reads are done before the next tile's first DMA
   }
 }
 
+// Phase mode (upsample = 2; p is the caller's view: M = batch * hout * wout output pixels): the slab row that holds output pixel m
+// = (b, y, x) -- phase (y & 1, x & 1), low-res pixel (b, y >> 1, x >> 1); slabs are [slice][phase][M / 4][N].  Both reduce kernels
+// walk the OUTPUT rows, so the GroupNorm statistics keep their blocks of 128 consecutive output rows whatever the image size.
+template <bool PH> __device__ __forceinline__ long long reduce_src_row(const SaspaGemmParams& p, const int m) {
+  if (!PH) return m;
+  const int hw = p.hout * p.wout;
+  const int b = m / hw, rem = m - b * hw;
+  const int y = rem / p.wout, x = rem - y * p.wout;
+  return (long long)((y & 1) * 2 + (x & 1)) * (p.M >> 2) + (long long)(b * p.hin + (y >> 1)) * p.win + (x >> 1);
+}
+
 // split-K reduce + epilogue: out = act(alpha*(sum_s ws[s] + bias + rowvec)) + residual
-template <typename T>
+template <typename T, bool PH = false>
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const SaspaGemmParams p, int ksplit) {
   const int n4 = p.N >> 2;
   const long long total = (long long)p.M * n4;
@@ -874,9 +906,10 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const SaspaGemmParam
   for (long long it = (long long)blockIdx.x * 256 + threadIdx.x; it < total; it += (long long)gridDim.x * 256) {
     const int m = (int)(it / n4);
     const int n = (int)(it - (long long)m * n4) * 4;
-    float4 a = *reinterpret_cast<const float4*>(p.workspace + (long long)m * p.N + n);
+    const long long ms = reduce_src_row<PH>(p, m);
+    float4 a = *reinterpret_cast<const float4*>(p.workspace + ms * p.N + n);
     for (int s = 1; s < ksplit; ++s) {
-      const float4 b = *reinterpret_cast<const float4*>(p.workspace + s * slab + (long long)m * p.N + n);
+      const float4 b = *reinterpret_cast<const float4*>(p.workspace + s * slab + ms * p.N + n);
       a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
     }
     float v[4] = {a.x, a.y, a.z, a.w};
@@ -906,7 +939,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const SaspaGemmParam
 // slab) -- 512 - 1024 workgroups on the 16x16 / 32x32 levels, two per CU; four rows per trip (4 x ksplit 16-byte loads in
 // flight per lane: the pass is bandwidth bound, the first version with one row per trip ran at half the plain reduce's rate);
 // the finished bf16 slab is staged in LDS like a GEMM tile and gn_tile_stats reads it.  bf16 only.
-__global__ __launch_bounds__(256) void splitk_reduce_stats_kernel(const SaspaGemmParams p, int ksplit) {
+template <bool PH = false> __global__ __launch_bounds__(256) void splitk_reduce_stats_kernel(const SaspaGemmParams p, int ksplit) {
   constexpr int BR = 128, BC = 80, CP = BC + 8, C4 = BC / 4, U = 4;
   __shared__ __attribute__((aligned(16))) h16_t ct[BR * CP + 4 * 256];
   const int tid = threadIdx.x;
@@ -920,17 +953,19 @@ __global__ __launch_bounds__(256) void splitk_reduce_stats_kernel(const SaspaGem
   for (int q0 = tid; q0 < total; q0 += U * 256) {
     float4 a[U];
     int row[U], c4[U];
+    long long ms[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int q = min(q0 + u * 256, total - 1);           // clamped duplicates are recomputed, never stored twice (below)
       row[u] = q / C4;
       c4[u] = q - row[u] * C4;
-      a[u] = *reinterpret_cast<const float4*>(p.workspace + (long long)(rb * BR + row[u]) * p.N + cs * BC + c4[u] * 4);
+      ms[u] = reduce_src_row<PH>(p, rb * BR + row[u]);
+      a[u] = *reinterpret_cast<const float4*>(p.workspace + ms[u] * p.N + cs * BC + c4[u] * 4);
     }
     for (int s = 1; s < ksplit; ++s) {
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        const float4 b = *reinterpret_cast<const float4*>(p.workspace + s * slab + (long long)(rb * BR + row[u]) * p.N + cs * BC + c4[u] * 4);
+        const float4 b = *reinterpret_cast<const float4*>(p.workspace + s * slab + ms[u] * p.N + cs * BC + c4[u] * 4);
         a[u].x += b.x; a[u].y += b.y; a[u].z += b.z; a[u].w += b.w;
       }
     }
@@ -988,6 +1023,27 @@ int launch(const SaspaGemmParams& p, hipStream_t s, int ksplit) {
   static const int abl = getenv("SASPA_GEMM_ABLATE") ? (atoi(getenv("SASPA_GEMM_ABLATE")) & 15) : 0;       // diagnostics only
   const int tiles_abl = tiles | (abl << 28);
   const int npart8 = saspa_gemm_npart8(p, BM, BN, gx, tiles);
+  if (p.upsample == 2) {
+    // phase mode (check_gemm: 16-bit types only), the same choices as below on instantiations of its own
+    if constexpr (sizeof(T) == 2) {
+      if constexpr (NT != 256) {
+        hipLaunchKernelGGL((gemm_dma_kernel<T, WM, WN, NWM, NWN, false, 3, false, true>), grid, dim3(NT), 0, s, p, tiles_abl, npart8);
+      } else if (dma_loader_ok(p)) {
+        constexpr bool can4 = (BM + BN) * 128 * 4 <= 160 * 1024;
+        if (can4 && (long long)tiles * zy <= 320)
+          hipLaunchKernelGGL((gemm_dma_kernel<T, WM, WN, 2, 2, false, can4 ? 4 : 2, false, true>), grid, dim3(256), 0, s, p, tiles_abl, npart8);
+        else
+          hipLaunchKernelGGL((gemm_dma_kernel<T, WM, WN, 2, 2, false, 2, false, true>), grid, dim3(256), 0, s, p, tiles_abl, npart8);
+      } else {
+        hipLaunchKernelGGL((gemm_kernel<T, WM, WN, false, true>), grid, dim3(256), 0, s, p, tiles, npart8);
+      }
+      SASPA_CHECK_LAUNCH();
+      if (ksplit > 1) return saspa_gemm_splitk_reduce(p, s, ksplit);
+      return 0;
+    } else {
+      return SASPA_ERANGE;
+    }
+  }
   if constexpr (NT != 256) {
     // 8-wave tiles exist only as DMA kernels (the plan checked dma_loader_ok)
     if (pw) hipLaunchKernelGGL((gemm_dma_kernel<T, WM, WN, NWM, NWN, true, 3>), grid, dim3(NT), 0, s, p, tiles_abl, npart8);
@@ -1142,6 +1198,9 @@ int plan_gemm(const SaspaGemmParams& p, GemmPlan& g) {
   // on a kernel that writes no slabs) would leave the workspace uninitialised: every rule below that drops the K split is closed
   // to such a call, and a call that cannot be split at all is refused here.
   const bool must_split = p.defer_reduce != 0;
+  // phase mode: un-split launches key the statistics by 128-row blocks of a phase's low-res image; smaller images need the reduce
+  // launch, which walks the output rows (saspa_gemm_suggest_ksplit answers >= 2 for them)
+  if (p.upsample == 2 && p.gn_stats && (p.hin * p.win) % 128 != 0 && ksplit <= 1) return SASPA_ERANGE;
   if (must_split && (ksplit <= 1 || p.act == SASPA_ACT_GEGLU || p.N <= 32 || p.variant == SASPA_GEMM_WS)) return SASPA_ERANGE;
   if (p.gn_stats) {
     // statistics need the LDS-staged bf16 epilogue on 160 / 320-column tiles of 128 / 256 rows (check_gemm checked the shape):
@@ -1264,15 +1323,44 @@ int check_gemm(const SaspaGemmParams* pp, SaspaGemmParams& p) {
   }
   // pre-split weights (ABI 20): only the SASPA_F32X3 DMA loop reads them
   if (p.w_split && p.dtype != SASPA_F32X3) return SASPA_ERANGE;
+  if (p.upsample == 2) {
+    // phase mode of the nearest-x2 3x3 / pad 1 conv (see SaspaGemmParams.upsample): 16-bit types, one source, plain epilogue
+    if (p.dtype != SASPA_HALF || p.kh != 2 || p.kw != 2 || p.stride != 1 || p.pad != 1) return SASPA_ERANGE;
+    if (p.hout != 2 * p.hin || p.wout != 2 * p.win) return SASPA_ERANGE;
+    if (p.c1 > 0 || p.residual || p.rowvec || p.act == SASPA_ACT_GEGLU || p.ln_gamma || p.out_t || p.defer_reduce) return SASPA_ERANGE;
+    if ((long long)p.nb1 * p.nb2 != 1) return SASPA_ERANGE;
+    if (4ll * p.N * p.ldw * 2 >= (1ll << 31)) return SASPA_ERANGE;          // the four phase matrices, [4][N][ldw]
+  }
   return 0;
+}
+
+// Phase mode: the launchers' view of the problem -- ONE phase's 2x2 conv over the low-res grid, the four phases as the batched
+// dimension (blockIdx.z: its weight matrix, the same input, the same output buffer -- the epilogue scatters the rows)
+SaspaGemmParams lower_phase(const SaspaGemmParams& p) {
+  SaspaGemmParams q = p;
+  q.M = p.M / 4;
+  q.hout = p.hin;
+  q.wout = p.win;
+  q.nb1 = 4;
+  q.nb2 = 1;
+  q.sa1 = 0;
+  q.sw1 = (long long)p.N * p.ldw;
+  q.so1 = 0;
+  return q;
 }
 
 }  // namespace
 
 // Recommended K-split of a problem (1 = none): the caller sizes the fp32 workspace (ksplit*M*N floats) from it.
+static int suggest_ksplit(const SaspaGemmParams& p);
 extern "C" int saspa_gemm_suggest_ksplit(const SaspaGemmParams* pp) {
   if (!pp) return 1;
-  const SaspaGemmParams& p = *pp;
+  const int ks = suggest_ksplit(*pp);
+  // phase mode with epilogue statistics on images of less than whole 128-row blocks per phase: only the reduce launch can key them
+  const bool need2 = pp->upsample == 2 && pp->gn_stats && (pp->hin * pp->win) % 128 != 0 && pp->N % 4 == 0;
+  return need2 && ks < 2 ? 2 : ks;
+}
+static int suggest_ksplit(const SaspaGemmParams& p) {
   if (p.M <= 0 || p.N <= 0 || p.K <= 0 || (long long)p.nb1 * p.nb2 > 1 || p.N % 4 || p.act == SASPA_ACT_GEGLU) return 1;
   const int bk = p.dtype == SASPA_HALF ? 64 : 32;
   const int ktiles = (p.K + bk - 1) / bk;
@@ -1321,16 +1409,25 @@ int saspa_gemm_npart8(const SaspaGemmParams& p, int BM, int BN, int G, int tiles
   return npart < 0.75 * mpart ? nbn / 8 : 0;
 }
 
-int saspa_gemm_splitk_reduce(const SaspaGemmParams& p, hipStream_t s, int ksplit) {
-  if (p.defer_reduce) return 0;      // ABI 18: the slabs go to saspa_splitk_groupnorm
+int saspa_gemm_splitk_reduce(const SaspaGemmParams& pl, hipStream_t s, int ksplit) {
+  if (pl.defer_reduce) return 0;      // ABI 18: the slabs go to saspa_splitk_groupnorm
+  SaspaGemmParams p = pl;
+  if (p.upsample == 2 && p.nb1 == 4) {   // phase mode: back from the launchers' per-phase view (lower_phase) to the output's
+    p.M *= 4;
+    p.hout *= 2;
+    p.wout *= 2;
+    p.nb1 = 1;
+  }
   if (p.gn_stats) {        // saspa_gemm checked: bf16, N % 160 == 0, 160 % gn_unit == 0
-    hipLaunchKernelGGL(splitk_reduce_stats_kernel, dim3((p.M + 127) / 128, p.N / 80), dim3(256), 0, s, p, ksplit);
+    if (p.upsample == 2) hipLaunchKernelGGL(splitk_reduce_stats_kernel<true>, dim3((p.M + 127) / 128, p.N / 80), dim3(256), 0, s, p, ksplit);
+    else hipLaunchKernelGGL(splitk_reduce_stats_kernel<false>, dim3((p.M + 127) / 128, p.N / 80), dim3(256), 0, s, p, ksplit);
     SASPA_CHECK_LAUNCH();
     return 0;
   }
   long long blocks = ((long long)p.M * (p.N / 4) + 255) / 256;
   if (blocks > 4096) blocks = 4096;
-  if (p.dtype == SASPA_HALF) hipLaunchKernelGGL((splitk_reduce_kernel<h16_t>), dim3((unsigned)blocks), dim3(256), 0, s, p, ksplit);
+  if (p.upsample == 2) hipLaunchKernelGGL((splitk_reduce_kernel<h16_t, true>), dim3((unsigned)blocks), dim3(256), 0, s, p, ksplit);   // 16-bit only
+  else if (p.dtype == SASPA_HALF) hipLaunchKernelGGL((splitk_reduce_kernel<h16_t>), dim3((unsigned)blocks), dim3(256), 0, s, p, ksplit);
 #ifndef SASPA_HALF_F16
   else hipLaunchKernelGGL((splitk_reduce_kernel<float>), dim3((unsigned)blocks), dim3(256), 0, s, p, ksplit);
 #endif
@@ -1355,6 +1452,7 @@ extern "C" int saspa_gemm(const SaspaGemmParams* pp, void* stream) {
   int rc = check_gemm(pp, p);
   if (rc == 0) rc = plan_gemm(p, g);
   if (rc != 0) return rc;
+  if (p.upsample == 2) p = lower_phase(p);       // planned on the caller's view (M output rows, K = 4 C), launched per phase
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   switch (g.family) {
     case SASPA_GEMM_AS: return saspa_gemm_as_launch(p, s);

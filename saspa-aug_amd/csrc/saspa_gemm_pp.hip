@@ -55,9 +55,14 @@ template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_wai
 
 // LOOP: 0 = two-barrier ping-pong, four 20-MFMA phases per K-tile; 1 = one barrier per phase, asymmetric programs (round 3,
 // slower, A/B arm); 2 = two-barrier ping-pong with TWO 40-MFMA phases per K-tile (round 5: half the pipe hand-offs)
-template <int FN, bool PW, bool UP, int LOOP>
+// UPM: 0 = the stored input, 1 = nearest-x2 input under a 3x3 window (per-lane generic loader), 2 = phase mode of the nearest-x2
+// conv (SaspaGemmParams.upsample = 2, lowered by saspa_gemm: p describes ONE phase's 2x2 conv over the low-res grid, blockIdx.z
+// is the phase).  Phase (py, px) reads taps (py + dy, px + dx), dy, dx in {0, 1}, of the 3x3 window centred on the low-res pixel:
+// the window loader as it is, with a scalar shift of the tap index; the epilogue scatters row (b, i, j) to pixel (2i+py, 2j+px).
+template <int FN, bool PW, int UPM, int LOOP>
 __global__ __launch_bounds__(512) void gemm_pp_kernel(const SaspaGemmParams p, const int ntiles_abl, const int npart8) {
   constexpr bool ONEBAR = LOOP == 1;
+  constexpr bool UP = UPM == 1, PH = UPM == 2;
   // diagnostic ablation (tools/gemm_ablate.py, `make ABLATION=1` only): bits 28..31 of the tile count
   //   1: no MFMA   2: no fragment reads   4: no DMA issue   8: no barriers;  bits 24..26 (SASPA_GEMM_EPI_ABLATE): epilogue
   const int ntiles = ntiles_abl & 0x00ffffff;
@@ -108,6 +113,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const SaspaGemmParams p, c
   }
   const int z = blockIdx.z;
   const int i1 = z / p.nb2, i2 = z - i1 * p.nb2;
+  const int py = PH ? z >> 1 : 0, px = PH ? z & 1 : 0;
   const T* a0 = reinterpret_cast<const T*>(p.a0) + (i1 * p.sa1 + i2 * p.sa2);
   const T* a1 = reinterpret_cast<const T*>(p.a1);
   const T* w = reinterpret_cast<const T*>(p.w) + (i1 * p.sw1 + i2 * p.sw2);
@@ -245,8 +251,9 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const SaspaGemmParams p, c
         }
       }
       if (!PW) {
-        const int tb = dyu * 3 + dxu;
-        soff += (dyu * p.win + dxu) * ldsz;
+        const int ty3 = dyu + py, tx3 = dxu + px;       // (phase mode: the 2x2 taps inside the 3x3 window)
+        const int tb = ty3 * 3 + tx3;
+        soff += (ty3 * p.win + tx3) * ldsz;
         bsh = 7 - (tb < 4 ? tb : tb - 1);
         amask = tb == 4 ? 0u : 0x80000000u;
       }
@@ -721,7 +728,8 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const SaspaGemmParams p, c
 #pragma unroll
         for (int j = 0; j < FN; ++j) asm volatile("" ::"v"(acc[i][j]));
     } else if (gridDim.y > 1) {
-      float* ws = p.workspace + (long long)blockIdx.y * p.M * p.N;
+      // (phase mode: slabs are [slice][phase][row of the phase][N]; the reduce launch gathers them per output pixel)
+      float* ws = p.workspace + (long long)(PH ? blockIdx.y * 4 + z : blockIdx.y) * p.M * p.N;
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         const int m = cbm * BM + ewm * 128 + i * 16 + efrow;
@@ -770,8 +778,16 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const SaspaGemmParams p, c
       const int gu = gtid % nunits, grg = gtid / nunits;
       float gsm = 0.f, gsq = 0.f;
       constexpr int CPR = BN / 8;
+      // phase mode: output row of each of the pass's 64 staged rows (-1 beyond M), behind the statistics scratch
+      int* const rmap = reinterpret_cast<int*>(ct + 128 * CP) + 1024 + ewm * 64;
 #pragma unroll
       for (int qt = 0; qt < 2; ++qt) {
+        if (PH && gtid < 64) {
+          const int m = m0 + qt * 64 + gtid;
+          const int b = m / hw, rem = m - b * hw;
+          const int i = rem / p.wout, j = rem - i * p.wout;
+          rmap[gtid] = m < p.M ? ((b * 2 * p.hout + 2 * i + py) * 2 * p.wout + 2 * j + px) : -1;
+        }
         if (!multi) {
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
@@ -898,7 +914,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const SaspaGemmParams p, c
 #pragma unroll
               for (int k = 0; k < NB; ++k) {
                 const u32x4 c4 = *reinterpret_cast<const u32x4*>(ctg + row[k] * CP + ch[k] * 8);
-                finish(c4, r4[k], row[k], ch[k], mq + row[k], cbn * BN + ch[k] * 8);
+                finish(c4, r4[k], row[k], ch[k], PH ? rmap[row[k]] : mq + row[k], cbn * BN + ch[k] * 8);
               }
             }
           } else {
@@ -909,7 +925,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const SaspaGemmParams p, c
               const u32x4 c4 = *reinterpret_cast<const u32x4*>(ctg + row * CP + ch * 8);
               uint4 r4 = make_uint4(0u, 0u, 0u, 0u);
               if (res) r4 = *reinterpret_cast<const uint4*>(res + (long long)m * p.ldr + n);
-              finish(c4, r4, row, ch, m, n);
+              finish(c4, r4, row, ch, PH ? rmap[row] : m, n);
             }
           }
         }
@@ -945,7 +961,10 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const SaspaGemmParams p, c
           const int uu = gtid >> 1, k = gtid & 1;
           float a = 0.f;
           for (int g = 0; g < rgs; ++g) a += scr[(g * nunits + uu) * 2 + k];
-          p.gn_stats[((long long)(cbm * 2 + ewm) * (p.N / p.gn_unit) + (cbn * BN) / p.gn_unit + uu) * 2 + k] = a;
+          // phase mode (whole 128-row blocks per low-res image, plan_gemm): image b's 4 * hw / 128 slots, phase-major
+          const int r128 = cbm * 2 + ewm, nlo = hw >> 7;
+          const int rb = PH ? (r128 / nlo * 4 + z) * nlo + r128 % nlo : r128;
+          p.gn_stats[((long long)rb * (p.N / p.gn_unit) + (cbn * BN) / p.gn_unit + uu) * 2 + k] = a;
         }
         lds_barrier();
       }
@@ -996,9 +1015,10 @@ int launch_pp(const SaspaGemmParams& p, hipStream_t s, int ksplit) {
   static const int eabl = getenv("SASPA_GEMM_EPI_ABLATE") ? (atoi(getenv("SASPA_GEMM_EPI_ABLATE")) & 7) : 0;
   const int ta = tiles | (abl << 28) | (stamp << 27) | (eabl << 24);
   const int npart8 = saspa_gemm_npart8(p, BM, BN, gx, tiles);
-  if (pw) hipLaunchKernelGGL((gemm_pp_kernel<FN, true, false, ONEBAR>), grid, dim3(512), 0, s, p, ta, npart8);
-  else if (p.upsample) hipLaunchKernelGGL((gemm_pp_kernel<FN, false, true, ONEBAR>), grid, dim3(512), 0, s, p, ta, npart8);
-  else hipLaunchKernelGGL((gemm_pp_kernel<FN, false, false, ONEBAR>), grid, dim3(512), 0, s, p, ta, npart8);
+  if (pw) hipLaunchKernelGGL((gemm_pp_kernel<FN, true, 0, ONEBAR>), grid, dim3(512), 0, s, p, ta, npart8);
+  else if (p.upsample == 2) hipLaunchKernelGGL((gemm_pp_kernel<FN, false, 2, ONEBAR>), grid, dim3(512), 0, s, p, ta, npart8);
+  else if (p.upsample) hipLaunchKernelGGL((gemm_pp_kernel<FN, false, 1, ONEBAR>), grid, dim3(512), 0, s, p, ta, npart8);
+  else hipLaunchKernelGGL((gemm_pp_kernel<FN, false, 0, ONEBAR>), grid, dim3(512), 0, s, p, ta, npart8);
   SASPA_CHECK_LAUNCH();
   if (ksplit > 1) return saspa_gemm_splitk_reduce(p, s, ksplit);
   return 0;
@@ -1014,7 +1034,10 @@ bool saspa_gemm_pp_eligible(const SaspaGemmParams& p) {
   if ((ctot % 64) != 0 || (p.c1 > 0 && (p.c0 % 64) != 0)) return false;        // a K-tile lies in one tap of one source
   if ((p.N % 8) != 0 || (p.ldo % 8) != 0 || (p.residual && (p.ldr % 8) != 0)) return false;
   const bool pw = p.kh == 1 && p.kw == 1 && p.stride == 1 && p.pad == 0 && !p.upsample;
-  if (!pw) {
+  if (p.upsample == 2) {
+    // phase mode (check_gemm checked the geometry): four 2x2 convs over the low-res grid, one source
+    if (p.kh != 2 || p.kw != 2 || p.stride != 1 || p.pad != 1 || p.c1 > 0 || p.residual || p.rowvec) return false;
+  } else if (!pw) {
     // 3x3 / pad 1 window (any stride, optional nearest x2): 8 halo taps + an always-inside centre tap
     if (p.kh != 3 || p.kw != 3 || p.pad != 1) return false;
     const int hv = p.upsample ? 2 * p.hin : p.hin, wv = p.upsample ? 2 * p.win : p.win;

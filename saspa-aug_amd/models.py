@@ -67,6 +67,25 @@ class _Packed:
         if name + ".bias" in self.sd:
             self.p[name + ".b"] = _f32(self.sd[name + ".bias"], self.dev)
 
+    def conv_up2x(self, name):
+        """The 3x3 conv of an Upsample2D (nearest x2 first).  16-bit types: the four 2x2 phase matrices of weights.pack_conv_up2x
+        (4/9 of the multiply-accumulates; ops.conv recognises the [4, N, 4C] tensor) -- the weights are constant, so the sums are
+        formed once, here.  fp32 (parity paths) or SASPA_UPCONV_PHASE=0: the 3x3 weights as for any conv."""
+        if not (_is_half(self.dtype) and ops.upconv_phase_enabled()):
+            return self.conv(name)
+        w = self.sd[name + ".weight"]
+        c0p = W.round8(w.shape[1])
+        pk = W.pack_conv_up2x(w)
+        chunk = W.chunk_major_ok(2, 2, c0p, 0, self.dtype)
+        if chunk:
+            pk = torch.stack([W.to_chunk_major(pk[i], 4, self.dtype) for i in range(4)])
+        t = pk.to(self.dev, self.dtype)             # the one rounding of the summed taps
+        t.saspa_korder = 1 if chunk else 0
+        t.saspa_cin = c0p
+        self.p[name + ".w"] = t
+        if name + ".bias" in self.sd:
+            self.p[name + ".b"] = _f32(self.sd[name + ".bias"], self.dev)
+
     def linear(self, name, dtype=None):
         self.p[name + ".w"] = W.pack_linear(self.sd[name + ".weight"]).to(self.dev, dtype or self.dtype)
         if name + ".bias" in self.sd:
@@ -662,7 +681,7 @@ class UNet(_Net):
                     self._pack_transformer(f"up_blocks.{i}.attentions.{j}", n_lvl - 1 - i)
                 prev = c
             if i != n_lvl - 1:
-                pk.conv(f"up_blocks.{i}.upsamplers.0.conv")
+                pk.conv_up2x(f"up_blocks.{i}.upsamplers.0.conv")
         pk.norm("conv_norm_out")
         pk.conv("conv_out")
         pk.sd = None  # drop the fp32 host copy reference
@@ -767,7 +786,7 @@ class VAEDecoder:
             for j in range(cfg["layers"] + 1):
                 self._pack_resnet(f"decoder.up_blocks.{i}.resnets.{j}")
             if i != n_lvl - 1:
-                pk.conv(f"decoder.up_blocks.{i}.upsamplers.0.conv")
+                pk.conv_up2x(f"decoder.up_blocks.{i}.upsamplers.0.conv")
         pk.norm("decoder.conv_norm_out")
         pk.conv("decoder.conv_out")
         pk.sd = None

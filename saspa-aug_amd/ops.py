@@ -300,6 +300,12 @@ def gn_fusion_enabled():
     return os.environ.get("SASPA_GN_FUSE", "1") != "0"
 
 
+def upconv_phase_enabled():
+    """SASPA_UPCONV_PHASE=0: the Upsample2D convs keep their 3x3 weights and run as one nearest-x2 implicit GEMM over all nine
+    taps again (A/B knob; read when a network is packed).  Default: the four 2x2 phase convs, 4/9 of the multiply-accumulates."""
+    return os.environ.get("SASPA_UPCONV_PHASE", "1") != "0"
+
+
 def _gn_stats_for(p, out, gn_unit, b, hw, n):
     """Epilogue GroupNorm statistics (SaspaGemmParams.gn_stats): allocate the [rows / 128, N / unit, 2] fp32 buffer, hang it
     on the output tensor (`saspa_gn` = (stats, unit): `groupnorm` picks it up and skips its statistics pass) -- when the
@@ -326,6 +332,8 @@ def conv(x, w, bias=None, *, kh=1, kw=1, stride=1, pad=0, upsample=False, x2=Non
     (pad channels zero).  ``korder``: K order the weights were packed in (default: the tensor's
     ``saspa_korder`` attribute set by the packer, else tap-major).  ``gn_unit``: the output feeds a GroupNorm whose
     groups are multiples of this many channels -> the epilogue leaves its statistics (`_gn_stats_for`).
+    ``w`` [4, N, 4*C0] (weights.pack_conv_up2x) with ``upsample=True, kh=kw=3, pad=1``: the same layer as four 2x2 phase convs over
+    the low-res input in one launch (SaspaGemmParams.upsample = 2); no x2 / rowvec / residual / act there.
     ``fuse_gn`` = (gamma, beta, groups, eps, act): the conv's ONLY consumer is this GroupNorm (ResnetBlock2D.conv1 -> norm2 ->
     SiLU), so the call returns the NORMALISED tensor: where the conv runs on K slices and an image's group fits one workgroup
     (the 8x8 / 16x16 levels) the reduce launch, the statistics and the apply pass are one launch (saspa_splitk_groupnorm, ABI
@@ -335,17 +343,24 @@ def conv(x, w, bias=None, *, kh=1, kw=1, stride=1, pad=0, upsample=False, x2=Non
     b, h, wd, c0 = x.shape
     c1 = 0 if x2 is None else x2.shape[3]
     hv, wv = (2 * h, 2 * wd) if upsample else (h, wd)
+    # phase weights of weights.pack_conv_up2x ([4, N, 4C]): the caller describes the layer (nearest x2, 3x3, pad 1), the launch is
+    # SaspaGemmParams.upsample = 2 -- four 2x2 convs over the low-res input, one launch
+    phase = w.dim() == 3
+    if phase and not (upsample and kh == 3 and kw == 3 and stride == 1 and pad == 1 and w.shape[0] == 4 and is_half(x)
+                      and x2 is None and rowvec is None and residual is None and act == ACT_NONE and out_hw is None
+                      and fuse_gn is None and w.is_contiguous()):
+        raise ValueError("phase weights serve the plain nearest-x2 3x3 / pad 1 conv of a 16-bit tensor only")
     ho = (hv + 2 * pad - kh) // stride + 1
     wo = (wv + 2 * pad - kw) // stride + 1
     if out_hw is not None:
         # asymmetric zero padding (Downsample2D(padding=0) of the VAE encoder pads right / bottom only): windows may hang
         # over the far edges, where the loaders' bounds masks read zeros; the C ABI checks the window origins
         ho, wo = out_hw
-    n = w.shape[0] if n_out is None else n_out
+    n = w.shape[-2] if n_out is None else n_out
     # geometry is validated HERE: the kernel trusts it (a mismatched skip / residual would be read out of bounds)
     if x2 is not None and (tuple(x2.shape[:3]) != (b, h, wd) or x2.dtype != x.dtype):
         raise ValueError(f"concat source {tuple(x2.shape)} does not match {tuple(x.shape)} (batch / height / width / dtype)")
-    if w.shape[1] < kh * kw * (c0 + c1) or w.dtype != x.dtype:
+    if w.shape[-1] < (4 if phase else kh * kw) * (c0 + c1) or w.dtype != x.dtype:
         raise ValueError(f"weights {tuple(w.shape)} {w.dtype} do not fit a {kh}x{kw} window over {c0}+{c1} channels of {x.dtype}")
     if ho <= 0 or wo <= 0:
         raise ValueError("empty convolution output")
@@ -367,8 +382,11 @@ def conv(x, w, bias=None, *, kh=1, kw=1, stride=1, pad=0, upsample=False, x2=Non
     p.lda1 = 0 if x2 is None else _pitch4(x2)
     p.batch, p.hin, p.win, p.hout, p.wout = b, h, wd, ho, wo
     p.kh, p.kw, p.stride, p.pad, p.upsample = kh, kw, stride, pad, int(upsample)
-    p.w, p.ldw = _ptr(w), w.stride(0)
+    p.w, p.ldw = _ptr(w), w.stride(-2)
     p.M, p.N, p.K = b * ho * wo, n, kh * kw * (c0 + c1)
+    if phase:
+        kh = kw = p.kh = p.kw = 2
+        p.upsample, p.K = 2, 4 * c0
     p.bias = _ptr(bias)
     p.rowvec = _ptr(rowvec)
     p.ldrv = 0 if (rowvec is None or rowvec.dim() == 1 or rowvec.shape[0] == 1) else rowvec.stride(0)
@@ -390,6 +408,7 @@ def conv(x, w, bias=None, *, kh=1, kw=1, stride=1, pad=0, upsample=False, x2=Non
     if gn_unit and kh == 1 and kw == 1 and c1 == 0 and is_half(x) and _as_over_stats() and \
             lib.saspa_gemm_as_auto(C.byref(p)) == 1:
         gn_unit = None
+    # (phase mode reports what runs: K = 4C, a 2x2 window over M / 4 low-res rows, 2*M*N*4C FLOPs)
     meta = (p.M, p.N, p.K, kh, stride, int(upsample), c1 > 0, residual is not None, n // 2 if act == ACT_GEGLU else n)
     if fuse_gn is not None:
         gamma, beta, groups, eps, gact = fuse_gn

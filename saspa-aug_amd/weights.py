@@ -644,6 +644,31 @@ def pack_conv_split(w, c0, c0_pad, c1, c1_pad):
     return torch.cat([a, b], -1).reshape(co, kh * kw * (c0_pad + c1_pad)).contiguous()
 
 
+def pack_conv_up2x(w, cin_pad=None):
+    """Phase weights of `nearest x2 upsample + 3x3 / pad 1 conv` (SaspaGemmParams.upsample = 2): [Cout, Cin, 3, 3] ->
+    [4, Cout, 4*Cin_pad] float64, phase index py*2+px, K index (dy*2+dx)*Cin_pad + c.  Output pixel (2i+py, 2j+px) sees the
+    hi-res rows 2i+py-1 .. 2i+py+1, which fall on the low-res rows {i-1, i, i} (py = 0) or {i, i, i+1} (py = 1): a 2x2
+    correlation over the low-res input with its window at (i+py-1, j+px-1), whose taps are the SUMS of the 3x3 taps that share
+    a low-res pixel -- rows {0}, {1, 2} for py = 0 and {0, 1}, {2} for py = 1, columns alike.  Summed in float64 from the
+    master weights and returned unrounded: the caller rounds ONCE, to the storage type."""
+    co, ci, kh, kw = w.shape
+    assert (kh, kw) == (3, 3), "phase weights exist for the 3x3 window only"
+    cp = round8(ci) if cin_pad is None else cin_pad
+    t = w.detach().to(torch.float64).permute(0, 2, 3, 1)                 # [Cout, ky, kx, Cin]
+    sets = (((0,), (1, 2)), ((0, 1), (2,)))                              # [phase bit][tap of the 2x2 window] -> 3x3 taps
+    out = torch.zeros((4, co, 2, 2, cp), dtype=torch.float64)
+    for py in range(2):
+        for px in range(2):
+            for dy in range(2):
+                for dx in range(2):
+                    acc = torch.zeros((co, ci), dtype=torch.float64)
+                    for ky in sets[py][dy]:
+                        for kx in sets[px][dx]:
+                            acc += t[:, ky, kx, :]
+                    out[py * 2 + px, :, dy, dx, :ci] = acc
+    return out.reshape(4, co, 4 * cp).contiguous()
+
+
 def ktile(dtype):
     """Elements of one K-tile of the implicit GEMM (128 bytes per row): 64 of the 16-bit compute type (bf16 / fp16) / 32 fp32."""
     return 64 if dtype in (torch.bfloat16, torch.float16) else 32

@@ -14,6 +14,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import fp8_ref, sampler_ref
 from tests.errbudget import (LIMITS, UNIT_BF16, UNIT_F32X3, attn_scale, budget_stats, check_budget, conv_scale, elem_scale,
                              fmt, gemm_scale, geglu_gemm_scale, norm_scale, ratio, rejects)
 
@@ -912,8 +913,27 @@ def _as_cases():
     return out
 
 
+def _bf16_only(cases):
+    """The fp8 W8A8 path and the sampler-step references exist for the default bf16 library only (fp8 and the fp16 compute mode
+    exclude each other; tests/fp8_ref.py and tests/sampler_ref.py round to bf16 themselves): when tests/fp16_budget.py re-runs a family
+    with this module's rounding switched to fp16, they stay out."""
+    return cases() if BF is torch.bfloat16 else []
+
+
 def _gemm_family_cases():
-    return _gemm_cases() + _as_plain_cases()
+    """... and the fp8 W8A8 GEMM (tests/fp8_ref.py: random operands, plain and residual forms)."""
+    return _gemm_cases() + _as_plain_cases() + _bf16_only(lambda: fp8_ref.gemm_cases(_rand))
+
+
+def _elem_family_cases():
+    """... the fp8 GEMM's GEGLU epilogue on exact operands (tests/fp8_ref.py) and ONE update of the multistep sampler kernels
+    (tests/sampler_ref.py)."""
+    return _elem_cases() + _bf16_only(lambda: fp8_ref.geglu_cases(_rand) + sampler_ref.elem_cases(_rand))
+
+
+def _e4m3_cases():
+    """The fp8 emission of the fp8 GEMM's GEGLU epilogue: decoded bytes x scale against float64, in units of 2^-4."""
+    return fp8_ref.e4m3_cases(_rand)
 
 
 def _chain_res_cases():
@@ -922,7 +942,7 @@ def _chain_res_cases():
 
 
 FAMILIES = {"gemm": (_gemm_family_cases, UNIT_BF16), "attn": (_attn_cases, UNIT_BF16), "norm": (_norm_cases, UNIT_BF16),
-            "elem": (_elem_cases, UNIT_BF16), "f32x3": (_f32x3_cases, UNIT_F32X3), "xattn": (_xattn_cases, UNIT_BF16),
+            "elem": (_elem_family_cases, UNIT_BF16), "e4m3": (_e4m3_cases, fp8_ref.UNIT_E4M3), "f32x3": (_f32x3_cases, UNIT_F32X3), "xattn": (_xattn_cases, UNIT_BF16),
             "ff": (_ff_cases, UNIT_BF16), "as": (_as_cases, UNIT_BF16), "chain_res": (_chain_res_cases, UNIT_BF16)}
 
 
@@ -1000,7 +1020,18 @@ def test_catalogue_is_complete():
                  "fused LayerNorm n-1 variance", "fused LayerNorm eps 1e-3",
                  "fused-GEGLU gate and value from different 128-column packs",
                  "V^T tail: first row of sample s+1 where the last row of sample s belongs",
-                 "ragged last block: its last row copies its neighbour A-stationary"]:
+                 "ragged last block: its last row copies its neighbour A-stationary",
+                 # the fp8 W8A8 GEMM (tests/fp8_ref.py)
+                 "truncating tile pack fp8 gemm", "truncating final pack fp8 gemm", "last K-tile dropped fp8 gemm",
+                 "sa of the neighbouring row fp8 gemm", "sw of the neighbouring 4-column group fp8 gemm",
+                 "fp8 bias missing on last 8 columns", "tanh-gelu in the fp8 geglu",
+                 "value and gate halves of one 128-column tile swapped fp8 geglu", "emission rounding toward zero",
+                 "out_scale applied twice",
+                 # ONE update of the sampler steps (tests/sampler_ref.py)
+                 "truncating stores cfg_unipc", "truncating stores unipc", "truncating stores cfg_plms",
+                 "truncating stores ddim without cfg", "truncating stores vae_sample_noise", "guidance 7.0 cfg_unipc",
+                 "guidance 7.0 cfg_plms", "UniPC predictor reads m1 for the old m0", "UniPC corrector skipped",
+                 "PLMS history weights rotated by one slot", "exp(logvar) for exp(0.5 logvar)"]:
         assert want in names, want
 
 

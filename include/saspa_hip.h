@@ -527,6 +527,23 @@ typedef struct SaspaGemmF8Params {
   float* amax;             /* GEGLU only, optional device scalar: atomic max of |gated value| over the launch (calibration of out_scale) */
 } SaspaGemmF8Params;
 int saspa_gemm_fp8(const SaspaGemmF8Params* p, void* stream);
+/* Calibration-free feed-forward (ff.net.0.proj -> ff.net.2 with no tensor-wide scale): the hidden state as MX e4m3, one E8M0
+ * exponent per row and 32 columns.  Both take SaspaGemmF8Params as saspa_gemm_fp8 reads it, plus the exponent array; default
+ * library only.
+ * saspa_gemm_fp8_geglu_mx (producer): the GEGLU launch of saspa_gemm_fp8 up to and including the gated value y (same K loop, same
+ *   acc * (sa * sw) + bias, same bf16 rounding of the tile); then for every row m < M and block b of 32 consecutive gated columns
+ *   (N / 64 blocks per row): e = the smallest integer with max|y| <= 448 * 2^e, clamped to [-127, 127], 0 for an all-zero block (the
+ *   rule of saspa_groupnorm_quant_mxfp8); qs[m][b] = e + 127 (uint8 at pitch ldqs), out[m][n] = e4m3fn(y * 2^-e) rounded to nearest
+ *   even, bytes at pitch ldo.  Cannot saturate; no atomics; a row's bytes depend on that row alone; rows >= M write nothing.
+ *   act must be SASPA_ACT_GEGLU and out_fp8 / out_scale / amax 0 / NULL (SASPA_EINVAL); ldo % 16, ldqs % 4, qs 4-byte aligned
+ *   (SASPA_EALIGN); ldqs >= N / 64, no residual (SASPA_ERANGE).
+ * saspa_gemm_mxfp8 (consumer): out[m][n] = bf16(sw[n] * sum_k 2^(qs[m][k / 32] - 127) a[m][k] w[n][k] + bias[n]) (+ residual[m][n]),
+ *   the exponent applied inside v_mfma_scale_f32_16x16x128_f8f6f4 as the activation-side scale operand (weight side 127).  sa must
+ *   be NULL, act SASPA_ACT_NONE, out_fp8 / out_scale / amax 0 / NULL (SASPA_EINVAL); K and N multiples of 128 (SASPA_ERANGE);
+ *   ldqs % 4, qs 4-byte aligned (SASPA_EALIGN: the four exponents of a row's K-tile are one aligned dword); ldqs >= K / 32
+ *   (SASPA_ERANGE).  Rows >= M of qs are never read.  Tile shape, ring, XCD order and epilogue of saspa_gemm_fp8. */
+int saspa_gemm_fp8_geglu_mx(const SaspaGemmF8Params* p, void* qs, int ldqs, void* stream);
+int saspa_gemm_mxfp8(const SaspaGemmF8Params* p, const void* qs, int ldqs, void* stream);
 int saspa_layernorm_quant_fp8(const void* x, int ldx, void* q, int ldq, float* scale, long long rows, int C,
                               const float* gamma, const float* beta, float eps, void* stream);
 

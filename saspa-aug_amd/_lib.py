@@ -154,6 +154,8 @@ SYMBOLS = {
     "saspa_resize_taps_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P]),
     "saspa_hed_fuse": (_I, [C.POINTER(HedFuseParams), _P]),
     "saspa_gemm_fp8": (_I, [C.POINTER(GemmF8Params), _P]),
+    "saspa_gemm_fp8_geglu_mx": (_I, [C.POINTER(GemmF8Params), _P, _I, _P]),
+    "saspa_gemm_mxfp8": (_I, [C.POINTER(GemmF8Params), _P, _I, _P]),
     "saspa_layernorm_quant_fp8": (_I, [_P, _I, _P, _I, _P, _LL, _I, _P, _P, _F, _P]),
     "saspa_resize_area_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "saspa_vae_sample_noise": (_I, [_I, _P, _P, _P, _P, _LL, _F, _F, _F, _P]),

@@ -225,6 +225,15 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// MX block exponent (saspa_groupnorm_quant_mxfp8, saspa_gemm_fp8_geglu_mx): the smallest e with amax <= 448 * 2^e, read off the fp32
+// bits (448 = 1.75 * 2^8: mantissa above 0.75 needs one binade more), clamped to the E8M0 range; 0 for an all-zero block
+__device__ __forceinline__ int mx_block_exponent(float amax) {
+  const unsigned bits = __float_as_uint(amax);
+  if (bits == 0u) return 0;
+  const int e = (int)(bits >> 23) - 135 + ((bits & 0x7fffffu) > 0x600000u ? 1 : 0);
+  return max(-127, min(127, e));
+}
+
 // Raw buffer loads: 32-bit per-lane byte offset + scalar byte offset against a 128-bit
 // descriptor; an offset >= num_records (2 GiB here) returns zeros -- that is how M / N / halo
 // padding is produced with no branch and no zero-fill (kInvalid below).

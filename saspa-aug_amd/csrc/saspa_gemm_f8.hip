@@ -8,6 +8,14 @@
 // (row, g = lane >> 4) reads chunks 2g, 2g + 1 = its 32 k values -- both operands use the same assignment, so it is a valid
 // permutation of the sum whatever the hardware's k order inside the instruction is), 2-stage ring, one barrier per K-tile.
 // Bound: L2 -> LDS fill (32 KB per 4.2 MFLOP K-tile: 1.85x the flops per filled byte of the bf16 128x160 tile).
+// MX feed-forward (calibration-free ff.net.0 -> ff.net.2, the same kernel with MX = true):
+//   saspa_gemm_fp8_geglu_mx     the GEGLU launch whose epilogue emits e4m3 bytes + one E8M0 exponent per row and 32 gated columns
+//                               (mx_block_exponent, the rule of saspa_groupnorm_quant_mxfp8): 8 threads walk a row of the tile, so a
+//                               block is four adjacent lanes and its maximum two lane exchanges; no tensor-wide scale, no atomics
+//   saspa_gemm_mxfp8            the plain launch with those exponents applied INSIDE v_mfma_scale_f32_16x16x128_f8f6f4 as the
+//                               activation-side scale operand, staged the way saspa_conv_mx.hip stages them (per-lane byte loads
+//                               issued with the DMA of the same K-tile, retired by the same vmcnt(0)); fragments as saspa_conv_mx.hip
+//                               reads them (chunks g, g + 4), because the instruction scales k = 32 b .. 32 b + 31 by lane group b
 #include "common.h"
 
 namespace {
@@ -15,8 +23,16 @@ namespace {
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 constexpr unsigned kInvalidOff = 0x80000000u;   // beyond num_records of make_rsrc: the DMA lands zeros
 
-template <bool GEGLU>
-__global__ __launch_bounds__(256, 2) void gemm_f8_kernel(const SaspaGemmF8Params p) {
+template <int SEL>
+__device__ __forceinline__ f32x4 mma_mx(const i32x8& w, const i32x8& x, const f32x4& c, int sx) {
+  // as saspa_conv_mx.hip: weight scale 127 = 1.0, activation scale = byte SEL of sx (the lane's block exponent of row fragment SEL)
+  return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(w, x, c, 0, 0, 0, 127, SEL, sx);
+}
+
+// MX = false: qs / ldqs unused.  MX && GEGLU: qs receives the block exponents.  MX && !GEGLU: qs holds those of the activations.
+template <bool GEGLU, bool MX>
+__global__ __launch_bounds__(256, 2) void gemm_f8_kernel(const SaspaGemmF8Params p, uint8_t* qs, int ldqs) {
+  constexpr bool MXIN = MX && !GEGLU, MXOUT = MX && GEGLU;
   constexpr int BM = 128, BN = 128, STAGE = (BM + BN) * 8;   // u32x4 per stage
   __shared__ u32x4 lds[2 * STAGE];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -33,6 +49,17 @@ __global__ __launch_bounds__(256, 2) void gemm_f8_kernel(const SaspaGemmF8Params
   }
   const int bm = tile / nbn, bn = tile - bm * nbn;
   const rsrc_t rsa = make_rsrc(p.a), rsw = make_rsrc(p.w);
+  // MXIN: the exponent bytes of the lane's MFMA rows wm * 64 + 16 i + frow, block fg of each K-tile; rows >= M are never read
+  // (their data is zero: any finite scale would do, an E8M0 255 from stray memory would not)
+  const rsrc_t rss = make_rsrc(qs);
+  unsigned bases[4], sb[4];
+  if constexpr (MXIN) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int m = bm * BM + wm * 64 + 16 * i + frow;
+      bases[i] = m < p.M ? (unsigned)m * (unsigned)ldqs + (unsigned)fg : kInvalidOff;
+    }
+  }
   const int r0 = tid >> 3;
   const int kcs = (tid & 7) ^ (r0 & 7);
   unsigned offa[4], offb[4];
@@ -53,6 +80,11 @@ __global__ __launch_bounds__(256, 2) void gemm_f8_kernel(const SaspaGemmF8Params
 #pragma unroll
     for (int i = 0; i < 4; ++i)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (lds_void_t*)(lb + (32 * i + 8 * wave) * 8), 16, (int)offb[i], soff, 0, 0);
+    if constexpr (MXIN) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        sb[i] = __builtin_amdgcn_raw_buffer_load_b8(rss, (int)(bases[i] + 4u * (unsigned)kt), 0, 0);   // kInvalidOff + 4 kt stays out of range
+    }
   };
   f32x4 acc[4][4];
 #pragma unroll
@@ -60,8 +92,10 @@ __global__ __launch_bounds__(256, 2) void gemm_f8_kernel(const SaspaGemmF8Params
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   auto frag = [&](const u32x4* base, int row) __attribute__((always_inline)) {
-    const u32x4 c0 = base[row * 8 + ((2 * fg) ^ (row & 7))];
-    const u32x4 c1 = base[row * 8 + ((2 * fg + 1) ^ (row & 7))];
+    // MXIN: chunks g and g + 4 (saspa_conv_mx.hip), so that the block the instruction scales with lane group b's byte is the
+    // 32 consecutive k of block b; otherwise chunks 2 g, 2 g + 1 (any assignment both operands share sums the same products)
+    const u32x4 c0 = base[row * 8 + ((MXIN ? fg : 2 * fg) ^ (row & 7))];
+    const u32x4 c1 = base[row * 8 + ((MXIN ? fg + 4 : 2 * fg + 1) ^ (row & 7))];
     return i32x8{(int)c0[0], (int)c0[1], (int)c0[2], (int)c0[3], (int)c1[0], (int)c1[1], (int)c1[2], (int)c1[3]};
   };
   const int nk = p.K / 128;
@@ -70,6 +104,8 @@ __global__ __launch_bounds__(256, 2) void gemm_f8_kernel(const SaspaGemmF8Params
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();                     // K-tile kt has landed for everyone; the other stage is free
     asm volatile("" ::: "memory");
+    int sx = 0;
+    if constexpr (MXIN) sx = (int)(sb[0] | (sb[1] << 8) | (sb[2] << 16) | (sb[3] << 24));
     if (kt + 1 < nk) dma(kt + 1, (kt + 1) & 1);
     __builtin_amdgcn_sched_barrier(0);                // issue the DMA before the MFMA block so that it flies under it
     const u32x4* la = lds + (kt & 1) * STAGE;
@@ -80,11 +116,18 @@ __global__ __launch_bounds__(256, 2) void gemm_f8_kernel(const SaspaGemmF8Params
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const i32x8 wb = frag(lb, wn * 64 + j * 16 + frow);
+      if constexpr (MXIN) {
+        acc[0][j] = mma_mx<0>(wb, xa[0], acc[0][j], sx);
+        acc[1][j] = mma_mx<1>(wb, xa[1], acc[1][j], sx);
+        acc[2][j] = mma_mx<2>(wb, xa[2], acc[2][j], sx);
+        acc[3][j] = mma_mx<3>(wb, xa[3], acc[3][j], sx);
+      } else {
 #pragma unroll
-      for (int i = 0; i < 4; ++i)
-        // D^T: weights as the A operand, so a lane owns 4 consecutive output channels of one row; formats 0 / 0 = e4m3,
-        // scale exponents 127 = 1.0 (E8M0) in byte 0 of both scale operands
-        acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wb, xa[i], acc[i][j], 0, 0, 0, 127, 0, 127);
+        for (int i = 0; i < 4; ++i)
+          // D^T: weights as the A operand, so a lane owns 4 consecutive output channels of one row; formats 0 / 0 = e4m3,
+          // scale exponents 127 = 1.0 (E8M0) in byte 0 of both scale operands
+          acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wb, xa[i], acc[i][j], 0, 0, 0, 127, 0, 127);
+      }
     }
   }
   __syncthreads();
@@ -102,7 +145,8 @@ __global__ __launch_bounds__(256, 2) void gemm_f8_kernel(const SaspaGemmF8Params
   for (int i = 0; i < 4; ++i) {
     const int mrow = wm * 64 + i * 16 + frow;
     const int m = bm * BM + mrow;
-    const float sa = m < p.M ? p.sa[p.sa_broadcast ? 0 : m] : 0.f;
+    float sa = 1.0f;                                  // MXIN: the activation scales went into the MFMA
+    if constexpr (!MXIN) sa = m < p.M ? p.sa[p.sa_broadcast ? 0 : m] : 0.f;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int ncol = wn * 64 + j * 16 + fg * 4;
@@ -113,7 +157,39 @@ __global__ __launch_bounds__(256, 2) void gemm_f8_kernel(const SaspaGemmF8Params
   }
   __syncthreads();
   bf16_t* out = reinterpret_cast<bf16_t*>(p.out);
-  if constexpr (GEGLU) {
+  if constexpr (MXOUT) {
+    // ABI 20 + saspa_gemm_fp8_geglu_mx: the hidden state leaves as e4m3 under one exponent per row and 32 gated columns.  Thread
+    // (row, ch) holds 8 of them, lanes ch & ~3 .. ch | 3 one block.  The trip count is uniform (BM * 8 = 4 * 256) and pad rows take
+    // part in the exchanges (whole 8-lane rows are live or not): only their stores are masked.
+    uint8_t* out8 = reinterpret_cast<uint8_t*>(p.out);
+    for (int q = tid; q < BM * 8; q += 256) {
+      const int row = q >> 3, ch = q & 7;
+      const int m = bm * BM + row;
+      float a[8], g[8];
+      unpack8(*reinterpret_cast<const uint4*>(ct + row * CP + ch * 8), a);
+      unpack8(*reinterpret_cast<const uint4*>(ct + row * CP + 64 + ch * 8), g);
+      float amax = 0.f;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        a[e] = fast_gelu_mul(a[e], g[e]);
+        amax = fmaxf(amax, fabsf(a[e]));
+      }
+      amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
+      amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
+      const int ex = mx_block_exponent(amax);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) a[e] = ldexpf(a[e], -ex);    // exact; |a| <= 448 by the choice of ex
+      int w0 = 0, w1 = 0;
+      w0 = __builtin_amdgcn_cvt_pk_fp8_f32(a[0], a[1], w0, false);
+      w0 = __builtin_amdgcn_cvt_pk_fp8_f32(a[2], a[3], w0, true);
+      w1 = __builtin_amdgcn_cvt_pk_fp8_f32(a[4], a[5], w1, false);
+      w1 = __builtin_amdgcn_cvt_pk_fp8_f32(a[6], a[7], w1, true);
+      if (m < p.M) {
+        *reinterpret_cast<int2*>(out8 + (long long)m * p.ldo + bn * 64 + ch * 8) = make_int2(w0, w1);
+        if ((ch & 3) == 0) qs[(long long)m * ldqs + bn * 2 + (ch >> 2)] = (uint8_t)(ex + 127);
+      }
+    }
+  } else if constexpr (GEGLU) {
     // tile columns [0, 64) are values, [64, 128) their gates (weights.pack_geglu with a 128-column tile)
     float amax = 0.f;
     const float inv_os = p.out_fp8 ? 1.0f / *p.out_scale : 1.0f;
@@ -265,8 +341,53 @@ extern "C" int saspa_gemm_fp8(const SaspaGemmF8Params* pp, void* stream) {
   if ((long long)p.M * p.lda >= (1ll << 31) || (long long)p.N * p.ldw >= (1ll << 31)) return SASPA_ERANGE;   // 32-bit DMA offsets
   const int tiles = ((p.M + 127) / 128) * (p.N / 128);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (p.act == SASPA_ACT_GEGLU) hipLaunchKernelGGL(gemm_f8_kernel<true>, dim3(tiles), dim3(256), 0, s, p);
-  else hipLaunchKernelGGL(gemm_f8_kernel<false>, dim3(tiles), dim3(256), 0, s, p);
+  if (p.act == SASPA_ACT_GEGLU) hipLaunchKernelGGL((gemm_f8_kernel<true, false>), dim3(tiles), dim3(256), 0, s, p, (uint8_t*)nullptr, 0);
+  else hipLaunchKernelGGL((gemm_f8_kernel<false, false>), dim3(tiles), dim3(256), 0, s, p, (uint8_t*)nullptr, 0);
+  SASPA_CHECK_LAUNCH();
+  return 0;
+}
+
+namespace {
+
+// what saspa_gemm_fp8 asks of the operands both MX entry points share with it (same codes); nout = columns of `out`
+int gemm_f8_mx_checks(const SaspaGemmF8Params& p, int nout) {
+  if (!p.a || !p.w || !p.sw || !p.out || p.M <= 0 || p.N <= 0 || p.K <= 0) return SASPA_EINVAL;
+  if (p.K % 128 || p.N % 128) return SASPA_ERANGE;                 // whole K-tiles and output tiles
+  if (p.lda < p.K || p.ldw < p.K || p.lda % 16 || p.ldw % 16) return SASPA_EALIGN;
+  if (!aligned16(p.a) || !aligned16(p.w) || !aligned16(p.out) || !aligned16(p.sw) || (p.bias && !aligned16(p.bias))) return SASPA_EALIGN;
+  if (p.ldo < nout) return SASPA_EALIGN;
+  if ((long long)p.M * p.lda >= (1ll << 31) || (long long)p.N * p.ldw >= (1ll << 31)) return SASPA_ERANGE;   // 32-bit DMA offsets
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int saspa_gemm_fp8_geglu_mx(const SaspaGemmF8Params* pp, void* qs, int ldqs, void* stream) {
+  if (!pp || !qs) return SASPA_EINVAL;
+  const SaspaGemmF8Params& p = *pp;
+  if (p.act != SASPA_ACT_GEGLU || !p.sa || p.out_fp8 || p.out_scale || p.amax) return SASPA_EINVAL;   // no tensor-wide scale here
+  if (const int rc = gemm_f8_mx_checks(p, p.N / 2)) return rc;
+  if (p.ldo % 16) return SASPA_EALIGN;                             // the consumer's DMA reads 16-byte pieces
+  if (ldqs % 4 || (reinterpret_cast<uintptr_t>(qs) & 3u)) return SASPA_EALIGN;     // a row's K-tile of exponents is one aligned dword
+  if (ldqs < p.N / 64 || p.residual) return SASPA_ERANGE;
+  const int tiles = ((p.M + 127) / 128) * (p.N / 128);
+  hipLaunchKernelGGL((gemm_f8_kernel<true, true>), dim3(tiles), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, (uint8_t*)qs, ldqs);
+  SASPA_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int saspa_gemm_mxfp8(const SaspaGemmF8Params* pp, const void* qs, int ldqs, void* stream) {
+  if (!pp || !qs) return SASPA_EINVAL;
+  const SaspaGemmF8Params& p = *pp;
+  if (p.act != SASPA_ACT_NONE || p.sa || p.out_fp8 || p.out_scale || p.amax) return SASPA_EINVAL;     // the exponents ARE the scales
+  if (const int rc = gemm_f8_mx_checks(p, p.N)) return rc;
+  if (p.ldo % 8) return SASPA_EALIGN;
+  if (ldqs % 4 || (reinterpret_cast<uintptr_t>(qs) & 3u)) return SASPA_EALIGN;
+  if (ldqs < p.K / 32 || (long long)p.M * ldqs >= (1ll << 31)) return SASPA_ERANGE;
+  if (p.residual && (p.ldr % 8 || !aligned16(p.residual))) return SASPA_EALIGN;
+  const int tiles = ((p.M + 127) / 128) * (p.N / 128);
+  hipLaunchKernelGGL((gemm_f8_kernel<false, true>), dim3(tiles), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p,
+                     const_cast<uint8_t*>(reinterpret_cast<const uint8_t*>(qs)), ldqs);
   SASPA_CHECK_LAUNCH();
   return 0;
 }

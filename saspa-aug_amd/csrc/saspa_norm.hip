@@ -282,14 +282,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const SaspaGroupNormParam
 // maximum is two lane exchanges.  y is quantised from fp32, never rounded to bf16.
 constexpr int kQuantMaxC = 4096;
 
-// smallest e with amax <= 448 * 2^e, read off the fp32 bits (448 = 1.75 * 2^8: mantissa above 0.75 needs one binade more),
-// clamped to the E8M0 range; 0 for an all-zero block
-__device__ __forceinline__ int mx_block_exponent(float amax) {
-  const unsigned bits = __float_as_uint(amax);
-  if (bits == 0u) return 0;
-  const int e = (int)(bits >> 23) - 135 + ((bits & 0x7fffffu) > 0x600000u ? 1 : 0);
-  return max(-127, min(127, e));
-}
+// (the block exponent rule: mx_block_exponent, common.h)
 
 __global__ __launch_bounds__(256) void gn_quant_mx_kernel(const SaspaGroupNormParams p, int slabs, int ipb, uint8_t* q, int ldq,
                                                           uint8_t* qs, int ldqs) {

@@ -218,7 +218,7 @@ def mxfp8_conv_takes(m, n, c):
 
 
 class _Net:
-    def __init__(self, sd, cfg, dev, dtype, fp8=False, fp8_conv=False):
+    def __init__(self, sd, cfg, dev, dtype, fp8=False, fp8_conv=False, fp8_ff="calibrated"):
         self.cfg, self.dev, self.dtype = cfg, dev, dtype
         # fp8: the LayerNorm-fed projections of the transformer blocks (attn2.to_q, ff.net.0.proj) run W8A8 on
         # saspa_gemm_fp8 (bf16 networks only; blocks whose width is not a multiple of 128 stay bf16)
@@ -232,6 +232,13 @@ class _Net:
         self.fp8_blocks = set()
         self.fp8_qkv = set()              # blocks whose fused self-attention projection runs on fp8 tiles (round 6)
         self.fp8_ffout = {}               # block -> calibrated?  (feed-forward output projection on fp8 tiles, round 6)
+        # fp8_ff: how the feed-forward hidden state reaches that projection.  "calibrated": e4m3 under ONE tensor-wide scale measured
+        # on the first execution (fp8_ffout).  "mx": e4m3 under one E8M0 exponent per row and 32 columns, computed in the GEGLU epilogue
+        # and applied inside the consumer's MFMA (saspa_gemm_fp8_geglu_mx -> saspa_gemm_mxfp8): no calibration, no state (fp8_ff_mx)
+        if fp8_ff not in ("calibrated", "mx"):
+            raise ValueError(f"fp8_ff must be 'calibrated' or 'mx', not {fp8_ff!r}")
+        self.fp8_ff = fp8_ff
+        self.fp8_ff_mx = set()            # blocks whose feed-forward runs the MX pair
         self.xattn_blocks = set()         # transformer blocks whose cross-attention half can run as one launch (ops.xattn_block)
         self.ff_blocks = set()            # transformer blocks whose feed-forward half can run as one launch (ops.ff_block)
         self.pk = _Packed(sd, dev, dtype)
@@ -468,7 +475,8 @@ class _Net:
         flash kernel reads its V columns row-major -- and the feed-forward OUTPUT projection ff.net.2, whose input leaves the
         GEGLU epilogue as e4m3 under one calibrated tensor-wide power-of-two scale (`ff.amax` / `ff.scale`, see transformer()):
         16 of the 18 C^2 multiply-accumulates per token of a block run on fp8 tiles (attn1 / attn2 to_out stay bf16: their input
-        is the attention kernel's output)."""
+        is the attention kernel's output).  fp8_ff == "mx": ff.net.2 is packed the same way, but its input leaves the GEGLU epilogue
+        under per-row, per-32-column exponents instead: no `ff.amax` / `ff.scale`, no `fp8_ffout` entry, the block joins `fp8_ff_mx`."""
         sd, p = self.pk.sd, self.p
         wq, sw = W.quantize_fp8(sd[t + ".attn2.to_q.weight"].float() * self.qscaled.get(t, 1.0))   # same fold as the bf16 rows
         p[t + ".attn2.q.w8"], p[t + ".attn2.q.sw"] = wq.to(self.dev), sw.to(self.dev)
@@ -493,6 +501,9 @@ class _Net:
             wq, sw = W.quantize_fp8(sd[t + ".ff.net.2.weight"].float())
             p[t + ".ff.net.2.w8"], p[t + ".ff.net.2.sw"] = wq.to(self.dev), sw.to(self.dev)
             del p[t + ".ff.net.2.w"]
+            if self.fp8_ff == "mx":
+                self.fp8_ff_mx.add(t)
+                return
             p[t + ".ff.amax"] = torch.zeros(1, device=self.dev, dtype=torch.float32)
             p[t + ".ff.scale"] = torch.ones(1, device=self.dev, dtype=torch.float32)
             self.fp8_ffout[t] = False          # -> True once the scale has been calibrated (first execution of the block)
@@ -565,6 +576,13 @@ class _Net:
                 o = attention_core(q, k, vtc, heads, n, nk, prescaled=pre)
                 h = ops.linear(o, p[t + ".attn2.o.w"], p[t + ".attn2.o.b"], residual=h)
                 q8, s8 = ops.layernorm_quant_fp8(h, p[t + ".norm3.g"], p[t + ".norm3.b"])
+                if t in self.fp8_ff_mx:
+                    # the hidden state leaves the GEGLU epilogue as MX e4m3 (an exponent per row and 32 columns, from that row's own
+                    # values) and the output projection applies the exponents inside its MFMAs: nothing to calibrate
+                    ff8, ffs = ops.linear_fp8(q8, s8, p[t + ".ff.net.0.proj.w8"], p[t + ".ff.net.0.proj.sw"], p[t + ".ff.net.0.proj.b8"],
+                                              act=ops.ACT_GEGLU, out_mx=True)
+                    h = ops.linear_mxfp8(ff8, ffs, p[t + ".ff.net.2.w8"], p[t + ".ff.net.2.sw"], p[t + ".ff.net.2.b"], residual=h)
+                    continue
                 if t in self.fp8_ffout:
                     # the hidden state leaves the GEGLU epilogue as e4m3 under ONE tensor-wide scale and the output projection
                     # reads the bytes.  The scale is calibrated the first time the block runs (always an eager launch: a step graph
@@ -659,8 +677,8 @@ class _Net:
 class UNet(_Net):
     """UNet2DConditionModel (SD-1.5 topology)."""
 
-    def __init__(self, sd, cfg, dev, dtype, fp8=False, fp8_conv=False):
-        super().__init__(sd, cfg, dev, dtype, fp8, fp8_conv)
+    def __init__(self, sd, cfg, dev, dtype, fp8=False, fp8_conv=False, fp8_ff="calibrated"):
+        super().__init__(sd, cfg, dev, dtype, fp8, fp8_conv, fp8_ff)
         self._pack_encoder()
         pk = self.pk
         bo = cfg["block_out"]
@@ -713,8 +731,8 @@ class UNet(_Net):
 class ControlNet(_Net):
     """ControlNetModel (control_v11p_sd15_canny topology)."""
 
-    def __init__(self, sd, cfg, dev, dtype, fp8=False, fp8_conv=False):
-        super().__init__(sd, cfg, dev, dtype, fp8, fp8_conv)
+    def __init__(self, sd, cfg, dev, dtype, fp8=False, fp8_conv=False, fp8_ff="calibrated"):
+        super().__init__(sd, cfg, dev, dtype, fp8, fp8_conv, fp8_ff)
         self._pack_encoder()
         pk = self.pk
         ce = cfg["cond_embed"]

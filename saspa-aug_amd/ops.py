@@ -1036,12 +1036,14 @@ def layernorm_quant_fp8(x, gamma, beta, eps=1e-5):
     return q.view(*x.shape[:-1], c), scale
 
 
-def linear_fp8(xq, xscale, wq, wscale, bias=None, *, residual=None, act=ACT_NONE, out_fp8_scale=None, amax=None):
+def linear_fp8(xq, xscale, wq, wscale, bias=None, *, residual=None, act=ACT_NONE, out_fp8_scale=None, amax=None, out_mx=False):
     """e4m3 activations (uint8 [..., K] + per-row scale, or ONE scale for the whole tensor: a 1-element `xscale`) @ e4m3 weights
     (uint8 [N, K] + per-channel scale)^T -> bf16 [..., N] (N / 2 with the fused GEGLU): `saspa_gemm_fp8`.
     GEGLU only (ABI 20): `out_fp8_scale` (device fp32 scalar) makes the result e4m3 bytes under that tensor-wide scale -- uint8
     [..., N / 2], what the feed-forward output projection reads --, `amax` (device fp32 scalar) receives the atomic maximum of the
-    gated values' magnitudes (calibration of that scale)."""
+    gated values' magnitudes (calibration of that scale).
+    GEGLU only, instead of those two: `out_mx=True` returns (q, qs), the gated values as MX e4m3 -- q uint8 [..., N / 2], qs uint8
+    [rows, N / 64] E8M0 exponents, one per row and 32 columns -- for `linear_mxfp8`: `saspa_gemm_fp8_geglu_mx`, no calibrated scale."""
     _check_dev(xq, xscale, wq, wscale, bias, residual, out_fp8_scale, amax)
     k = xq.shape[-1]
     x2 = xq.reshape(-1, k)
@@ -1049,7 +1051,9 @@ def linear_fp8(xq, xscale, wq, wscale, bias=None, *, residual=None, act=ACT_NONE
     nout = n // 2 if act == ACT_GEGLU else n
     if (out_fp8_scale is not None or amax is not None) and act != ACT_GEGLU:
         raise ValueError("fp8 emission / amax exist in the GEGLU epilogue only")
-    out = torch.empty((m, nout), device=xq.device, dtype=torch.uint8 if out_fp8_scale is not None else torch.bfloat16)
+    if out_mx and (act != ACT_GEGLU or out_fp8_scale is not None or amax is not None):
+        raise ValueError("out_mx exists in the GEGLU epilogue only, and not together with out_fp8_scale / amax")
+    out = torch.empty((m, nout), device=xq.device, dtype=torch.uint8 if (out_fp8_scale is not None or out_mx) else torch.bfloat16)
     r2 = None if residual is None else residual.reshape(-1, residual.shape[-1])
     p = _lib.GemmF8Params()
     p.a, p.lda, p.w, p.ldw = _ptr(x2), x2.stride(0) if m > 1 else k, _ptr(wq), wq.stride(0)
@@ -1069,9 +1073,42 @@ def linear_fp8(xq, xscale, wq, wscale, bias=None, *, residual=None, act=ACT_NONE
         if amax.dtype != torch.float32 or amax.numel() != 1:
             raise ValueError("amax is one fp32 value on the device")
         p.amax = _ptr(amax)
+    if out_mx:
+        ldqs = (n // 64 + 3) & ~3                  # a row's exponents start on a dword (the consumer's K-tile of 4 is one)
+        qs = torch.empty((m, ldqs), device=xq.device, dtype=torch.uint8)[:, :n // 64]
+        _launch("gemm", 2.0 * m * n * k,
+                lambda: _lib.check(_L().saspa_gemm_fp8_geglu_mx(C.byref(p), _ptr(qs), ldqs, _stream()), "saspa_gemm_fp8_geglu_mx"),
+                (m, n, k, 0, 1, 0, False, False, nout, GEMM_FAMILY_FP8, 1))
+        return out.reshape(*xq.shape[:-1], nout), qs
     _launch("gemm", 2.0 * m * n * k, lambda: _lib.check(_L().saspa_gemm_fp8(C.byref(p), _stream()), "saspa_gemm_fp8"),
             (m, n, k, 0, 1, 0, False, residual is not None, nout, GEMM_FAMILY_FP8, 1))
     return out.reshape(*xq.shape[:-1], nout)
+
+
+def linear_mxfp8(q, qs, wq, wscale, bias=None, *, residual=None):
+    """MX e4m3 activations (`linear_fp8(..., out_mx=True)`'s (q uint8 [..., K], qs uint8 [rows, >= K / 32] E8M0 exponents, one per
+    row and 32 columns)) @ e4m3 weights (uint8 [N, K] + per-channel scale)^T -> bf16 [..., N]: `saspa_gemm_mxfp8`, the exponents
+    applied inside the scaled MFMA.  The feed-forward output projection of the calibration-free fp8 mode."""
+    _check_dev(q, qs, wq, wscale, bias, residual)
+    if q.dtype != torch.uint8 or qs.dtype != torch.uint8 or wq.dtype != torch.uint8:
+        raise TypeError("linear_mxfp8 takes uint8 e4m3 bytes / E8M0 exponents")
+    k = q.shape[-1]
+    x2 = q.reshape(-1, k)
+    m, n = x2.shape[0], wq.shape[0]
+    if qs.dim() != 2 or qs.shape[0] != m or qs.shape[1] < k // 32 or qs.stride(1) != 1:
+        raise ValueError(f"block exponents {tuple(qs.shape)} do not cover {m} rows of {k // 32} blocks")
+    out = torch.empty((m, n), device=q.device, dtype=torch.bfloat16)
+    r2 = None if residual is None else residual.reshape(-1, residual.shape[-1])
+    p = _lib.GemmF8Params()
+    p.a, p.lda, p.w, p.ldw = _ptr(x2), x2.stride(0) if m > 1 else k, _ptr(wq), wq.stride(0)
+    p.M, p.N, p.K = m, n, k
+    p.sw, p.bias = _ptr(wscale), _ptr(bias)
+    p.residual, p.ldr = _ptr(r2), 0 if r2 is None else r2.stride(0)
+    p.act, p.out, p.ldo = int(ACT_NONE), _ptr(out), n
+    ldqs = qs.stride(0) if m > 1 else (k // 32 + 3) & ~3      # one row: the pitch is never used
+    _launch("gemm", 2.0 * m * n * k, lambda: _lib.check(_L().saspa_gemm_mxfp8(C.byref(p), _ptr(qs), ldqs, _stream()), "saspa_gemm_mxfp8"),
+            (m, n, k, 0, 1, 0, False, residual is not None, n, GEMM_FAMILY_FP8, 1))
+    return out.reshape(*q.shape[:-1], n)
 
 
 def fp8_pow2_scale(amax, margin=16.0):

@@ -325,8 +325,13 @@ class StableDiffusionControlNetPipeline:
         fp8_conv = fp8 and (getattr(self, "_fp8_conv", False) or os.environ.get("SASPA_FP8_CONV", "0") == "1")
         if fp8 and cdt == torch.float16:
             raise ValueError("fp8 together with fp16 compute is not supported: the fp8 projections quantise bf16 activations")
-        self.unet = models.UNet(sd["unet"], cf["unet"], device, cdt, fp8=fp8, fp8_conv=fp8_conv)
-        self.controlnet = (models.ControlNet(sd["controlnet"], cf["controlnet"], device, cdt, fp8=fp8, fp8_conv=fp8_conv)
+        fp8_ff = getattr(self, "_fp8_ff", "calibrated")
+        if fp8_ff == "calibrated":
+            fp8_ff = os.environ.get("SASPA_FP8_FF", "calibrated")
+            if fp8_ff not in ("calibrated", "mx"):
+                raise ValueError(f"SASPA_FP8_FF must be 'calibrated' or 'mx', got {fp8_ff!r}")
+        self.unet = models.UNet(sd["unet"], cf["unet"], device, cdt, fp8=fp8, fp8_conv=fp8_conv, fp8_ff=fp8_ff)
+        self.controlnet = (models.ControlNet(sd["controlnet"], cf["controlnet"], device, cdt, fp8=fp8, fp8_conv=fp8_conv, fp8_ff=fp8_ff)
                            if self.HAS_CONTROLNET else None)
         self.vae = models.VAEDecoder(sd["vae"], cf["vae"], device, vdt,
                                      f32_gemm="x3" if (cdt == torch.float16 and vdt == torch.float32) else "exact")
@@ -360,20 +365,28 @@ class StableDiffusionControlNetPipeline:
         self._fp16, self._fp16_vae = bool(on), vae
         return self
 
-    def enable_fp8(self, on=True, convs=False):
+    def enable_fp8(self, on=True, convs=False, ff="calibrated"):
         """Call BEFORE `.to()`: the LayerNorm-fed projections of the UNet / ControlNet transformer blocks (cross-attention
         query, GEGLU feed-forward) run as e4m3 W8A8 GEMMs (BASELINE.json configs[4] "fp8 MFMA"; SASPA_FP8=1 does the same).
         convs=True (SASPA_FP8_CONV=1, needs fp8 on): the ResnetBlock2D conv1 / conv2 also run as MX-fp8 (block-scaled e4m3) convs
-        where models.mxfp8_conv_takes admits them (models._Net.fp8_convs lists those that ran).  Off by default: the headline
-        metric is quoted in bf16."""
+        where models.mxfp8_conv_takes admits them (models._Net.fp8_convs lists those that ran).
+        ff="mx" (SASPA_FP8_FF=mx, needs fp8 on): the feed-forward hidden state carries one exponent per row and 32 columns instead
+        of the tensor-wide scale calibrated on the first batch a process runs (the default, ff="calibrated"): an image's bytes
+        depend on that image alone, nothing saturates, a block can be captured without an eager run.  Same average error.
+        Off by default: the headline metric is quoted in bf16."""
         if self.unet is not None:
             raise RuntimeError("enable_fp8() must be called before .to(): the weights are quantised at pack time")
+        if ff not in ("calibrated", "mx"):
+            raise ValueError(f"ff must be 'calibrated' or 'mx', got {ff!r}")
         if convs and not on:
             raise ValueError("fp8 convs need fp8 on: enable_fp8(True, convs=True)")
+        if ff == "mx" and not on:
+            raise ValueError("the MX feed-forward needs fp8 on: enable_fp8(True, ff='mx')")
         if on and self._fp16:
             raise ValueError("fp8 together with fp16 compute is not supported: the fp8 projections quantise bf16 activations")
         self._fp8 = bool(on)
         self._fp8_conv = bool(convs)
+        self._fp8_ff = ff
         return self
 
     def upcast_vae(self, gemm=None):  # SDXL-only hook the reference calls at run_aug/run_aug.py:224
@@ -774,7 +787,7 @@ class StableDiffusionInstructPix2PixPipeline(StableDiffusionImg2ImgPipeline):
     def from_pretrained(cls, base_dir, cfgs=IP2P):
         return super().from_pretrained(base_dir, cfgs)
 
-    def enable_fp8(self, on=True, convs=False):
+    def enable_fp8(self, on=True, convs=False, ff="calibrated"):
         raise NotImplementedError("enable_fp8() is not built for StableDiffusionInstructPix2PixPipeline (three guidance groups)")
 
     def to(self, device, dtype=None):

@@ -6,6 +6,7 @@ Activations are channels-last ``[B, H, W, C]`` (or ``[M, C]`` token matrices) wh
 dim is contiguous; the pixel pitch (``stride(-2)``) may exceed C (views into wider
 buffers, e.g. the q/k slices of a fused projection)."""
 import os
+import collections
 import ctypes as C
 
 import torch
@@ -267,18 +268,27 @@ class twin_branch:
         _TWIN[0] = self.prev
 
 
-def _set_splitk(p, m, n, k, t, force=None):
+def _suggest_ksplit(p, t, force=None):
     """Split-K factor from the library's own heuristic (saspa_gemm_suggest_ksplit: every other field of p is already
-    filled in) or the caller's override; allocates the fp32 slab workspace."""
+    filled in, `sharing` from the twin context here) or the caller's override."""
     p.ksplit, p.workspace = 1, None
     p.sharing = 1 if _TWIN[0] else 0
-    ks = _L(t).saspa_gemm_suggest_ksplit(C.byref(p)) if force is None else int(force)
+    return _L(t).saspa_gemm_suggest_ksplit(C.byref(p)) if force is None else int(force)
+
+
+def _alloc_slabs(p, ks, t):
+    """Run p on ks K slices: allocates the ks * M * N fp32 slab workspace (None for one slice)."""
+    p.ksplit, p.workspace = 1, None
     if ks > 1:
-        ws = torch.empty((ks * m * n,), device=t.device, dtype=torch.float32)
+        ws = torch.empty((ks * p.M * p.N,), device=t.device, dtype=torch.float32)
         p.ksplit, p.workspace = ks, C.c_void_p(ws.data_ptr())
         return ws           # keep alive until the launch is enqueued
-    p.ksplit, p.workspace = 1, None
     return None
+
+
+def _set_splitk(p, m, n, k, t, force=None):
+    """Split-K factor (heuristic or override) and its slab workspace for the M x N x K problem p describes."""
+    return _alloc_slabs(p, _suggest_ksplit(p, t, force), t)
 
 
 def _as_over_stats():
@@ -306,6 +316,12 @@ def upconv_phase_enabled():
     return os.environ.get("SASPA_UPCONV_PHASE", "1") != "0"
 
 
+# What an epilogue hangs on its output tensor as `saspa_gn`: the statistics, their channel unit, and the buffer and tensor version
+# they describe.  `_fresh_stats` re-checks the last two, so a tensor that was re-pointed or written in place through torch since the
+# launch falls back to its own statistics pass.
+GnStats = collections.namedtuple("GnStats", "stats unit data_ptr version")
+
+
 def _gn_stats_for(p, out, gn_unit, b, hw, n):
     """Epilogue GroupNorm statistics (SaspaGemmParams.gn_stats): allocate the [rows / 128, N / unit, 2] fp32 buffer, hang it
     on the output tensor (`saspa_gn` = (stats, unit): `groupnorm` picks it up and skips its statistics pass) -- when the
@@ -318,10 +334,138 @@ def _gn_stats_for(p, out, gn_unit, b, hw, n):
         return None
     stats = torch.empty((b * hw // 128, n // gn_unit, 2), device=out.device, dtype=torch.float32)
     p.gn_stats, p.gn_unit = _ptr(stats), int(gn_unit)
-    # (statistics, unit, the buffer and tensor version they describe): `groupnorm` re-checks the last two, so a tensor that
-    # was re-pointed or written in place through torch since the launch falls back to its own statistics pass
-    out.saspa_gn = (stats, int(gn_unit), out.data_ptr(), out._version)
+    out.saspa_gn = GnStats(stats, int(gn_unit), out.data_ptr(), out._version)
     return stats
+
+
+def _fresh_stats(t):
+    """The epilogue statistics hung on t (`saspa_gn`) as GnStats, when they still describe it -- the same buffer and tensor version,
+    one statistics row per 128 pixels -- else None."""
+    g = getattr(t, "saspa_gn", None) if t is not None else None
+    if g is None:
+        return None
+    g = GnStats(*g)
+    if g.data_ptr != t.data_ptr() or g.version != t._version or g.stats.shape[0] * 128 != t.shape[0] * t.shape[1] * t.shape[2]:
+        return None
+    return g
+
+
+def _epilogue_stats(x, x2, groups):
+    """(GnStats of x, GnStats of x2 or None) that the producers' epilogues hung on the tensors (`saspa_gn`, see _gn_stats_for), when
+    they still describe the tensors and a GroupNorm of `groups` groups over cat(x, x2) can use them; else (None, None)."""
+    b, h, w, c0 = x.shape
+    c1 = 0 if x2 is None else x2.shape[3]
+    g0, g1 = _fresh_stats(x), _fresh_stats(x2)
+    fused = (g0 is not None and (x2 is None or g1 is not None) and gn_fusion_enabled() and (h * w) % 128 == 0
+             and (x2 is None or g1.unit == g0.unit) and c0 % g0.unit == 0 and c1 % g0.unit == 0 and ((c0 + c1) // groups) % g0.unit == 0
+             and g0.stats.shape[1] * g0.unit == c0 and (x2 is None or g1.stats.shape[1] * g1.unit == c1))
+    return (g0, g1) if fused else (None, None)
+
+
+def _gn_nsplit(batch, hw, c8):
+    """Pixel splits of the statistics pass: about 1024 workgroups per channel slab (the apply pass re-reads
+    nsplit * slabs * groups sums per workgroup, so no more than needed to fill the chip)."""
+    want = max(1, int(os.environ.get("SASPA_GN_BLOCKS", "1024")) // max(1, batch))
+    return max(1, min(want, 64, hw // 16 if hw >= 16 else 1))
+
+
+def _gn_params(x, x2, gamma, beta, groups, eps, act, out, *, partial=None, nsplit=0, stats=(None, None)):
+    """SaspaGroupNormParams of GroupNorm(+act) over cat(x, x2) into `out` (None: a launch that writes no y -- the statistics pass, the
+    quantiser).  Where the statistics come from is the caller's: `partial` / `nsplit` of a statistics pass, or `stats` = the
+    producers' (GnStats, GnStats or None) from `_epilogue_stats`; neither for the launches that take their own."""
+    p = _lib.GroupNormParams()
+    p.dtype = _dt(x)
+    p.x0, p.x1, p.c0, p.c1 = _ptr(x), _ptr(x2), x.shape[3], 0 if x2 is None else x2.shape[3]
+    p.ldx0, p.ldx1 = _pitch4(x), 0 if x2 is None else _pitch4(x2)
+    p.batch, p.hw, p.groups, p.eps = x.shape[0], x.shape[1] * x.shape[2], int(groups), float(eps)
+    p.gamma, p.beta = _ptr(gamma), _ptr(beta)
+    p.partial, p.nsplit, p.scale_shift = _ptr(partial), nsplit, None
+    p.act = int(act)
+    if out is not None:
+        p.y, p.ldy = _ptr(out), _pitch4(out)
+    g0, g1 = stats
+    if g0 is not None:
+        p.stats0, p.stats1, p.unit = _ptr(g0.stats), _ptr(None if g1 is None else g1.stats), g0.unit
+    return p
+
+
+def _ldrv(rowvec):
+    """Pitch of the per-image row vector: 0 = one vector for every image ([N] or [1, N])."""
+    return 0 if (rowvec is None or rowvec.dim() == 1 or rowvec.shape[0] == 1) else rowvec.stride(0)
+
+
+def _check_conv_operands(x, x2, w, taps, window, n, ho, wo, bias, rowvec, residual, out):
+    """Operands of a conv of x (| x2) with `taps` weight columns per input channel into [B, ho, wo, >= n].
+    Geometry is validated HERE: the kernel trusts it (a mismatched skip / residual would be read out of bounds)."""
+    b, h, wd, c0 = x.shape
+    c1 = 0 if x2 is None else x2.shape[3]
+    if x2 is not None and (tuple(x2.shape[:3]) != (b, h, wd) or x2.dtype != x.dtype):
+        raise ValueError(f"concat source {tuple(x2.shape)} does not match {tuple(x.shape)} (batch / height / width / dtype)")
+    if w.shape[-1] < taps * (c0 + c1) or w.dtype != x.dtype:
+        raise ValueError(f"weights {tuple(w.shape)} {w.dtype} do not fit a {window} window over {c0}+{c1} channels of {x.dtype}")
+    if ho <= 0 or wo <= 0:
+        raise ValueError("empty convolution output")
+    for name, t in (("residual", residual), ("out", out)):
+        if t is not None and (t.dim() != 4 or tuple(t.shape[:3]) != (b, ho, wo) or t.shape[3] < n or t.dtype != x.dtype):
+            raise ValueError(f"{name} {tuple(t.shape)} {t.dtype} does not match the output [{b},{ho},{wo},>={n}] {x.dtype}")
+    if bias is not None and bias.numel() < n:
+        raise ValueError("bias shorter than N")
+    if rowvec is not None and (rowvec.shape[-1] < n or (rowvec.dim() == 2 and rowvec.shape[0] not in (1, b))):
+        raise ValueError(f"rowvec {tuple(rowvec.shape)} must be [N] or [batch, N]")
+
+
+def _conv_out(x, ho, wo, n):
+    """The output a conv allocates: [B, ho, wo, round8(N)], pad channels zero."""
+    nc = round8(n)
+    return (torch.zeros if nc != n else torch.empty)((x.shape[0], ho, wo, nc), device=x.device, dtype=x.dtype)
+
+
+def _conv_gemm_params(x, x2, w, bias, rowvec, residual, alpha, act, kh, kw, stride, pad, upsample, ho, wo, n):
+    """The implicit-GEMM fields of SaspaGemmParams for a conv of x (| x2) into [B, ho, wo, n]: sources and pitches, window, weights,
+    M / N / K and the epilogue operands.  Output, K order, variant, statistics and split-K are the caller's."""
+    b, h, wd, c0 = x.shape
+    c1 = 0 if x2 is None else x2.shape[3]
+    p = _lib.GemmParams()
+    p.dtype = _gemm_dt(x)
+    p.a0, p.a1, p.c0, p.c1 = _ptr(x), _ptr(x2), c0, c1
+    p.lda0 = _pitch4(x)
+    p.lda1 = 0 if x2 is None else _pitch4(x2)
+    p.batch, p.hin, p.win, p.hout, p.wout = b, h, wd, ho, wo
+    p.kh, p.kw, p.stride, p.pad, p.upsample = kh, kw, stride, pad, upsample
+    p.w, p.ldw = _ptr(w), w.stride(-2)
+    p.M, p.N, p.K = b * ho * wo, n, kh * kw * (c0 + c1)
+    p.bias, p.rowvec, p.ldrv = _ptr(bias), _ptr(rowvec), _ldrv(rowvec)
+    p.residual = _ptr(residual)
+    p.ldr = 0 if residual is None else _pitch4(residual)
+    p.alpha, p.act = float(alpha), int(act)
+    p.nb1 = p.nb2 = 1
+    return p
+
+
+def _deferred_reduce_gn(p, lib, out, split, launch_conv, what, gn, flops, meta):
+    """conv -> GroupNorm whose only reader is that GroupNorm, as the conv on K slices with the reduce left to saspa_splitk_groupnorm
+    (sums the slabs, takes the statistics, normalises: the un-normalised output is never written).  p: the conv's filled
+    SaspaGemmParams; split(): chooses its K slices (the heuristic WITHOUT epilogue statistics: nobody reads them); launch_conv():
+    launches it and returns the library's code (`what` names it in an error); gn = (gamma, beta, groups, eps, act) of the GroupNorm
+    over `out`; meta(): the recorder meta of the conv launch.  True: `out` holds the normalised tensor.  False: nothing was
+    launched and p is back on one slice, not deferred -- the caller runs conv and groupnorm as usual."""
+    if not (splitk_gn_enabled() and not p.residual and p.act == ACT_NONE and out.shape[-1] == p.N):
+        return False
+    _ws = split()  # noqa: F841
+    gamma, beta, groups, eps, act = gn
+    q = _gn_params(out, None, gamma, beta, groups, eps, act, out)
+    if p.ksplit > 1 and lib.saspa_splitk_groupnorm_eligible(C.byref(p), C.byref(q)):
+        p.defer_reduce = 1
+        # SASPA_ERANGE: the dispatch would run this problem on ONE slice / a kernel without slabs (a variant pin, an A/B
+        # knob): nothing was launched, fall back to conv + groupnorm
+        rc = _probe_launch("gemm", flops, launch_conv, meta())
+        if rc == 0:
+            _launch("splitk_gn", 0.0, lambda: _lib.check(lib.saspa_splitk_groupnorm(C.byref(p), C.byref(q), _stream()), "saspa_splitk_groupnorm"))
+            return True
+        if rc != _lib.SASPA_ERANGE:
+            _lib.check(rc, what)
+    p.ksplit, p.workspace, p.defer_reduce = 1, None, 0
+    return False
 
 
 def conv(x, w, bias=None, *, kh=1, kw=1, stride=1, pad=0, upsample=False, x2=None, rowvec=None,
@@ -357,44 +501,13 @@ def conv(x, w, bias=None, *, kh=1, kw=1, stride=1, pad=0, upsample=False, x2=Non
         # over the far edges, where the loaders' bounds masks read zeros; the C ABI checks the window origins
         ho, wo = out_hw
     n = w.shape[-2] if n_out is None else n_out
-    # geometry is validated HERE: the kernel trusts it (a mismatched skip / residual would be read out of bounds)
-    if x2 is not None and (tuple(x2.shape[:3]) != (b, h, wd) or x2.dtype != x.dtype):
-        raise ValueError(f"concat source {tuple(x2.shape)} does not match {tuple(x.shape)} (batch / height / width / dtype)")
-    if w.shape[-1] < (4 if phase else kh * kw) * (c0 + c1) or w.dtype != x.dtype:
-        raise ValueError(f"weights {tuple(w.shape)} {w.dtype} do not fit a {kh}x{kw} window over {c0}+{c1} channels of {x.dtype}")
-    if ho <= 0 or wo <= 0:
-        raise ValueError("empty convolution output")
-    for name, t in (("residual", residual), ("out", out)):
-        if t is not None and (t.dim() != 4 or tuple(t.shape[:3]) != (b, ho, wo) or t.shape[3] < n or t.dtype != x.dtype):
-            raise ValueError(f"{name} {tuple(t.shape)} {t.dtype} does not match the output [{b},{ho},{wo},>={n}] {x.dtype}")
-    if bias is not None and bias.numel() < n:
-        raise ValueError("bias shorter than N")
-    if rowvec is not None and (rowvec.shape[-1] < n or (rowvec.dim() == 2 and rowvec.shape[0] not in (1, b))):
-        raise ValueError(f"rowvec {tuple(rowvec.shape)} must be [N] or [batch, N]")
+    _check_conv_operands(x, x2, w, 4 if phase else kh * kw, f"{kh}x{kw}", n, ho, wo, bias, rowvec, residual, out)
     if out is None:
-        nc = round8(n)
-        out = (torch.zeros if nc != n else torch.empty)((b, ho, wo, nc), device=x.device, dtype=x.dtype)
-    p = _lib.GemmParams()
-    p.dtype = _gemm_dt(x)
-    p.a0, p.a1 = _ptr(x), _ptr(x2)
-    p.c0, p.c1 = c0, c1
-    p.lda0 = _pitch4(x)
-    p.lda1 = 0 if x2 is None else _pitch4(x2)
-    p.batch, p.hin, p.win, p.hout, p.wout = b, h, wd, ho, wo
-    p.kh, p.kw, p.stride, p.pad, p.upsample = kh, kw, stride, pad, int(upsample)
-    p.w, p.ldw = _ptr(w), w.stride(-2)
-    p.M, p.N, p.K = b * ho * wo, n, kh * kw * (c0 + c1)
+        out = _conv_out(x, ho, wo, n)
     if phase:
-        kh = kw = p.kh = p.kw = 2
-        p.upsample, p.K = 2, 4 * c0
-    p.bias = _ptr(bias)
-    p.rowvec = _ptr(rowvec)
-    p.ldrv = 0 if (rowvec is None or rowvec.dim() == 1 or rowvec.shape[0] == 1) else rowvec.stride(0)
-    p.residual = _ptr(residual)
-    p.ldr = 0 if residual is None else _pitch4(residual)
-    p.alpha, p.act = float(alpha), int(act)
+        kh = kw = 2                   # what runs: a 2x2 window (K = 4C) over the low-res rows, SaspaGemmParams.upsample = 2
+    p = _conv_gemm_params(x, x2, w, bias, rowvec, residual, alpha, act, kh, kw, stride, pad, 2 if phase else int(upsample), ho, wo, n)
     p.out, p.ldo = _ptr(out), _pitch4(out)
-    p.nb1 = p.nb2 = 1
     p.variant = int(variant)
     p.korder = int(getattr(w, "saspa_korder", 0)) if korder is None else int(korder)
     if getattr(w, "saspa_wsplit", 0):
@@ -410,52 +523,17 @@ def conv(x, w, bias=None, *, kh=1, kw=1, stride=1, pad=0, upsample=False, x2=Non
         gn_unit = None
     # (phase mode reports what runs: K = 4C, a 2x2 window over M / 4 low-res rows, 2*M*N*4C FLOPs)
     meta = (p.M, p.N, p.K, kh, stride, int(upsample), c1 > 0, residual is not None, n // 2 if act == ACT_GEGLU else n)
-    if fuse_gn is not None:
-        gamma, beta, groups, eps, gact = fuse_gn
-        if splitk_gn_enabled() and residual is None and act == ACT_NONE and out.shape[-1] == n:
-            _ws = _set_splitk(p, p.M, p.N, p.K, x, ksplit)          # the heuristic WITHOUT epilogue statistics: nobody reads them
-            q = _lib.GroupNormParams()
-            q.dtype = _dt(out)
-            q.x0, q.x1, q.c0, q.c1 = _ptr(out), None, n, 0
-            q.ldx0, q.ldx1 = _pitch4(out), 0
-            q.batch, q.hw, q.groups, q.eps = b, ho * wo, int(groups), float(eps)
-            q.gamma, q.beta = _ptr(gamma), _ptr(beta)
-            q.partial, q.nsplit, q.scale_shift = None, 0, None
-            q.act, q.y, q.ldy = int(gact), _ptr(out), _pitch4(out)
-            if p.ksplit > 1 and lib.saspa_splitk_groupnorm_eligible(C.byref(p), C.byref(q)):
-                p.defer_reduce = 1
-                # SASPA_ERANGE: the dispatch would run this problem on ONE slice / a kernel without slabs (a variant pin, an A/B
-                # knob): nothing was launched, fall back to conv + groupnorm below
-                rc = _probe_launch("gemm", 2.0 * p.M * p.N * p.K, lambda: lib.saspa_gemm(C.byref(p), _stream()), _meta_kernel(p, meta))
-                if rc == 0:
-                    _launch("splitk_gn", 0.0, lambda: _lib.check(lib.saspa_splitk_groupnorm(C.byref(p), C.byref(q), _stream()), "saspa_splitk_groupnorm"))
-                    return out
-                if rc != _lib.SASPA_ERANGE:
-                    _lib.check(rc, "saspa_gemm(conv, deferred reduce)")
-            p.ksplit, p.workspace, p.defer_reduce = 1, None, 0
-        h = conv(x, w, bias, kh=kh, kw=kw, stride=stride, pad=pad, upsample=upsample, x2=x2, rowvec=rowvec, residual=residual, alpha=alpha,
-                 act=act, out=out, n_out=n_out, variant=variant, korder=korder, ksplit=ksplit, out_hw=out_hw, gn_unit=gn_unit)
-        return groupnorm(h, gamma, beta, groups, eps, gact)
+    flops = 2.0 * p.M * p.N * p.K
+
+    def launch():
+        return lib.saspa_gemm(C.byref(p), _stream())
+    if fuse_gn is not None and _deferred_reduce_gn(p, lib, out, lambda: _set_splitk(p, p.M, p.N, p.K, x, ksplit), launch,
+                                                   "saspa_gemm(conv, deferred reduce)", fuse_gn, flops, lambda: _meta_kernel(p, meta)):
+        return out
     _gs = _gn_stats_for(p, out, gn_unit, b, ho * wo, n)  # noqa: F841   (set BEFORE the split-K heuristic looks at p)
     _ws = _set_splitk(p, p.M, p.N, p.K, x, ksplit)  # noqa: F841   (ksplit: tuning override of the heuristic)
-    _launch("gemm", 2.0 * p.M * p.N * p.K, lambda: _lib.check(lib.saspa_gemm(C.byref(p), _stream()), "saspa_gemm(conv)"), _meta_kernel(p, meta))
-    return out
-
-
-def _gn_source_stats(x, x2, groups):
-    """Epilogue statistics of the producers of x (| x2), as `groupnorm` would use them: (stats0, stats1, unit) or None."""
-    def _fresh(t):
-        g = getattr(t, "saspa_gn", None) if t is not None else None
-        if g is None or g[2] != t.data_ptr() or g[3] != t._version or g[0].shape[0] * 128 != t.shape[0] * t.shape[1] * t.shape[2]:
-            return None
-        return g
-    b, h, w, c0 = x.shape
-    c1 = 0 if x2 is None else x2.shape[3]
-    g0, g1 = _fresh(x), _fresh(x2)
-    ok = (g0 is not None and (x2 is None or g1 is not None) and gn_fusion_enabled() and (h * w) % 128 == 0
-          and (x2 is None or g1[1] == g0[1]) and c0 % g0[1] == 0 and c1 % g0[1] == 0 and ((c0 + c1) // groups) % g0[1] == 0
-          and g0[0].shape[1] * g0[1] == c0 and (x2 is None or g1[0].shape[1] * g1[1] == c1))
-    return (g0[0], g1[0] if g1 is not None else None, g0[1]) if ok else None
+    _launch("gemm", flops, lambda: _lib.check(launch(), "saspa_gemm(conv)"), _meta_kernel(p, meta))
+    return out if fuse_gn is None else groupnorm(out, *fuse_gn)
 
 
 def conv_gn(x, gn, w32, bias=None, *, x2=None, rowvec=None, residual=None, alpha=1.0, out=None, ksplit=None, gn_unit=None,
@@ -474,115 +552,54 @@ def conv_gn(x, gn, w32, bias=None, *, x2=None, rowvec=None, residual=None, alpha
     b, h, wd, c0 = x.shape
     c1 = 0 if x2 is None else x2.shape[3]
     n = w32.shape[0]
-    if x2 is not None and (tuple(x2.shape[:3]) != (b, h, wd) or x2.dtype != x.dtype):
-        raise ValueError(f"concat source {tuple(x2.shape)} does not match {tuple(x.shape)} (batch / height / width / dtype)")
-    if w32.shape[1] < 9 * (c0 + c1) or w32.dtype != x.dtype:
-        raise ValueError(f"weights {tuple(w32.shape)} {w32.dtype} do not fit a 3x3 window over {c0}+{c1} channels of {x.dtype}")
-    for name, t in (("residual", residual), ("out", out)):
-        if t is not None and (t.dim() != 4 or tuple(t.shape[:3]) != (b, h, wd) or t.shape[3] < n or t.dtype != x.dtype):
-            raise ValueError(f"{name} {tuple(t.shape)} {t.dtype} does not match the output [{b},{h},{wd},>={n}] {x.dtype}")
-    if bias is not None and bias.numel() < n:
-        raise ValueError("bias shorter than N")
-    if rowvec is not None and (rowvec.shape[-1] < n or (rowvec.dim() == 2 and rowvec.shape[0] not in (1, b))):
-        raise ValueError(f"rowvec {tuple(rowvec.shape)} must be [N] or [batch, N]")
-    p = _lib.GemmParams()
-    p.dtype = _lib.SASPA_BF16
-    p.a0, p.a1, p.c0, p.c1 = _ptr(x), _ptr(x2), c0, c1
-    p.lda0 = _pitch4(x)
-    p.lda1 = 0 if x2 is None else _pitch4(x2)
-    p.batch, p.hin, p.win, p.hout, p.wout = b, h, wd, h, wd
-    p.kh, p.kw, p.stride, p.pad, p.upsample = 3, 3, 1, 1, 0
-    p.w, p.ldw = _ptr(w32), w32.stride(0)
-    p.M, p.N, p.K = b * h * wd, n, 9 * (c0 + c1)
-    p.bias, p.rowvec = _ptr(bias), _ptr(rowvec)
-    p.ldrv = 0 if (rowvec is None or rowvec.dim() == 1 or rowvec.shape[0] == 1) else rowvec.stride(0)
-    p.residual = _ptr(residual)
-    p.ldr = 0 if residual is None else _pitch4(residual)
-    p.alpha, p.act = float(alpha), ACT_NONE
-    p.nb1 = p.nb2 = 1
+    _check_conv_operands(x, x2, w32, 9, "3x3", n, h, wd, bias, rowvec, residual, out)
+    p = _conv_gemm_params(x, x2, w32, bias, rowvec, residual, alpha, ACT_NONE, 3, 3, 1, 1, 0, h, wd, n)
     p.korder = 2
     q = None
-    keep = []
     if gn is not None:
         gb32, groups, eps, gact = gn
         q = _lib.ConvGnParams()
         q.gamma_beta32, q.groups, q.eps, q.act = _ptr(gb32), int(groups), float(eps), int(gact)
-        st = _gn_source_stats(x, x2, groups)
-        if st is not None:
-            q.stats0, q.stats1, q.unit = _ptr(st[0]), _ptr(st[1]), int(st[2])
-            keep.append(st)
+        g0, g1 = _epilogue_stats(x, x2, groups)
+        if g0 is not None:
+            q.stats0, q.stats1, q.unit = _ptr(g0.stats), _ptr(None if g1 is None else g1.stats), g0.unit
+    qq = C.byref(q) if q is not None else None
+    own_stats = q is not None and not q.stats0
     # eligibility is decided BEFORE any allocation / statistics launch (out / ldo of a would-be output: dense rows of round8(N))
     p.out, p.ldo = _ptr(x), round8(n) if out is None else _pitch4(out)
-    if q is not None and not q.stats0:
+    if own_stats:
         q.partial, q.nsplit = _ptr(x), 1            # placeholders for the eligibility check
-    if not lib.saspa_conv3x3_halo_eligible(C.byref(p), C.byref(q) if q is not None else None):
+    if not lib.saspa_conv3x3_halo_eligible(C.byref(p), qq):
         return None
-    if q is not None and not q.stats0:
+    if own_stats:
         # no epilogue statistics on the input: the statistics pass of `groupnorm`, then the fused apply + conv
         ctot = c0 + c1
         nsplit = _gn_nsplit(b, h * wd, ctot // 8)
         partial = torch.empty((b * nsplit * ctot * 2,), device=x.device, dtype=torch.float32)
-        g = _lib.GroupNormParams()
-        g.dtype = _dt(x)
-        g.x0, g.x1, g.c0, g.c1 = _ptr(x), _ptr(x2), c0, c1
-        g.ldx0, g.ldx1 = _pitch4(x), (0 if x2 is None else _pitch4(x2))
-        g.batch, g.hw, g.groups, g.eps = b, h * wd, int(groups), float(eps)
-        g.gamma, g.beta = _ptr(gb32), _ptr(gb32)       # not read by the statistics pass
-        g.partial, g.nsplit, g.scale_shift = _ptr(partial), nsplit, None
-        g.act, g.y, g.ldy = 0, None, 0
+        g = _gn_params(x, x2, gb32, gb32, groups, eps, ACT_NONE, None, partial=partial, nsplit=nsplit)   # gamma / beta: not read by the pass
         _launch("gn_stats", 0.0, lambda: _lib.check(lib.saspa_groupnorm_stats(C.byref(g), _stream()), "saspa_groupnorm_stats"))
         q.partial, q.nsplit = _ptr(partial), nsplit
-        keep.append(partial)
     if out is None:
-        nc = round8(n)
-        out = (torch.zeros if nc != n else torch.empty)((b, h, wd, nc), device=x.device, dtype=x.dtype)
+        out = _conv_out(x, h, wd, n)
     p.out, p.ldo = _ptr(out), _pitch4(out)
     meta = (p.M, p.N, p.K, 3, 1, 0, c1 > 0, residual is not None, n)
     flops = 2.0 * p.M * p.N * p.K
 
     def _split(force):
-        p.ksplit, p.workspace = 1, None
-        p.sharing = 1 if _TWIN[0] else 0
         p.korder = 1                                  # the heuristic knows the im2col kernels' orders only; same K
-        ks = lib.saspa_gemm_suggest_ksplit(C.byref(p)) if force is None else int(force)
+        ks = _suggest_ksplit(p, x, force)
         p.korder = 2
-        ks = lib.saspa_conv3x3_halo_ksplit(C.byref(p), ks)
-        if ks > 1:
-            ws = torch.empty((ks * p.M * p.N,), device=x.device, dtype=torch.float32)
-            p.ksplit, p.workspace = ks, C.c_void_p(ws.data_ptr())
-            return ws
-        return None
+        return _alloc_slabs(p, lib.saspa_conv3x3_halo_ksplit(C.byref(p), ks), x)
 
-    qq = C.byref(q) if q is not None else None
-    if defer_to is not None:
-        gamma, beta, groups2, eps2, gact2 = defer_to
-        if splitk_gn_enabled() and residual is None and out.shape[-1] == n:
-            _ws = _split(ksplit)
-            g2 = _lib.GroupNormParams()
-            g2.dtype = _dt(out)
-            g2.x0, g2.x1, g2.c0, g2.c1 = _ptr(out), None, n, 0
-            g2.ldx0, g2.ldx1 = _pitch4(out), 0
-            g2.batch, g2.hw, g2.groups, g2.eps = b, h * wd, int(groups2), float(eps2)
-            g2.gamma, g2.beta = _ptr(gamma), _ptr(beta)
-            g2.partial, g2.nsplit, g2.scale_shift = None, 0, None
-            g2.act, g2.y, g2.ldy = int(gact2), _ptr(out), _pitch4(out)
-            if p.ksplit > 1 and lib.saspa_splitk_groupnorm_eligible(C.byref(p), C.byref(g2)):
-                p.defer_reduce = 1
-                rc = _probe_launch("gemm", flops, lambda: lib.saspa_conv3x3_halo(C.byref(p), qq, _stream()), meta)
-                if rc == 0:
-                    _launch("splitk_gn", 0.0, lambda: _lib.check(lib.saspa_splitk_groupnorm(C.byref(p), C.byref(g2), _stream()), "saspa_splitk_groupnorm"))
-                    return out
-                if rc != _lib.SASPA_ERANGE:
-                    _lib.check(rc, "saspa_conv3x3_halo(deferred reduce)")
-            p.ksplit, p.workspace, p.defer_reduce = 1, None, 0
-        _gs = _gn_stats_for(p, out, gn_unit, b, h * wd, n)  # noqa: F841
-        _ws = _split(ksplit)  # noqa: F841
-        _launch("gemm", flops, lambda: _lib.check(lib.saspa_conv3x3_halo(C.byref(p), qq, _stream()), "saspa_conv3x3_halo"), meta)
-        return groupnorm(out, gamma, beta, groups2, eps2, gact2)
+    def launch():
+        return lib.saspa_conv3x3_halo(C.byref(p), qq, _stream())
+    if defer_to is not None and _deferred_reduce_gn(p, lib, out, lambda: _split(ksplit), launch, "saspa_conv3x3_halo(deferred reduce)",
+                                                    defer_to, flops, lambda: meta):
+        return out
     _gs = _gn_stats_for(p, out, gn_unit, b, h * wd, n)  # noqa: F841
     _ws = _split(ksplit)  # noqa: F841
-    _launch("gemm", flops, lambda: _lib.check(lib.saspa_conv3x3_halo(C.byref(p), qq, _stream()), "saspa_conv3x3_halo"), meta)
-    return out
+    _launch("gemm", flops, lambda: _lib.check(launch(), "saspa_conv3x3_halo"), meta)
+    return out if defer_to is None else groupnorm(out, *defer_to)
 
 
 def _linear_params(x2, w, bias, r2, o2, alpha, act, rowvec, variant, m, n, k):
@@ -825,31 +842,6 @@ def softmax_rows(x, n, scale, causal=False, rows_per_mat=1):
     return x
 
 
-def _gn_nsplit(batch, hw, c8):
-    """Pixel splits of the statistics pass: about 1024 workgroups per channel slab (the apply pass re-reads
-    nsplit * slabs * groups sums per workgroup, so no more than needed to fill the chip)."""
-    want = max(1, int(os.environ.get("SASPA_GN_BLOCKS", "1024")) // max(1, batch))
-    return max(1, min(want, 64, hw // 16 if hw >= 16 else 1))
-
-
-def _epilogue_stats(x, x2, groups):
-    """(stats of x, stats of x2 or None) that the producers' epilogues hung on the tensors (`saspa_gn`, see _gn_stats_for), when
-    they still describe the tensors and a GroupNorm of `groups` groups over cat(x, x2) can use them; else (None, None)."""
-    def _fresh(t):
-        g = getattr(t, "saspa_gn", None) if t is not None else None
-        if g is None or g[2] != t.data_ptr() or g[3] != t._version or g[0].shape[0] * 128 != t.shape[0] * t.shape[1] * t.shape[2]:
-            return None
-        return g
-    b, h, w, c0 = x.shape
-    c1 = 0 if x2 is None else x2.shape[3]
-    ctot = c0 + c1
-    g0, g1 = _fresh(x), _fresh(x2)
-    fused = (g0 is not None and (x2 is None or g1 is not None) and gn_fusion_enabled() and (h * w) % 128 == 0
-             and (x2 is None or g1[1] == g0[1]) and c0 % g0[1] == 0 and c1 % g0[1] == 0 and (ctot // groups) % g0[1] == 0
-             and g0[0].shape[1] * g0[1] == c0 and (x2 is None or g1[0].shape[1] * g1[1] == c1))
-    return (g0, g1) if fused else (None, None)
-
-
 def groupnorm(x, gamma, beta, groups, eps, act=ACT_NONE, x2=None, out=None):
     """GroupNorm(+SiLU) over channels-last x (optionally concatenated with x2) -> [B,H,W,C]."""
     _check_dev(x, gamma, beta, x2, out)
@@ -865,47 +857,20 @@ def groupnorm(x, gamma, beta, groups, eps, act=ACT_NONE, x2=None, out=None):
         raise ValueError("GroupNorm output does not match the input geometry")
     if out is None:
         out = torch.empty((b, h, w, ctot), device=x.device, dtype=x.dtype)
-    # statistics left by the producers' epilogues (conv(..., gn_unit=...)): no statistics pass
-    g0, g1 = _epilogue_stats(x, x2, groups)
-    if g0 is not None:
-        p = _lib.GroupNormParams()
-        p.dtype = _dt(x)
-        p.x0, p.x1, p.c0, p.c1 = _ptr(x), _ptr(x2), c0, c1
-        p.ldx0 = _pitch4(x)
-        p.ldx1 = 0 if x2 is None else _pitch4(x2)
-        p.batch, p.hw, p.groups, p.eps = b, h * w, groups, float(eps)
-        p.gamma, p.beta = _ptr(gamma), _ptr(beta)
-        p.partial, p.nsplit, p.scale_shift = None, 0, None
-        p.act, p.y, p.ldy = int(act), _ptr(out), _pitch4(out)
-        p.stats0, p.stats1, p.unit = _ptr(g0[0]), (_ptr(g1[0]) if g1 is not None else None), g0[1]
-        _lib.check(lib.saspa_groupnorm_apply(C.byref(p), _stream()), "saspa_groupnorm_apply(epilogue statistics)")
+    stats = _epilogue_stats(x, x2, groups)
+    p = _gn_params(x, x2, gamma, beta, groups, eps, act, out, stats=stats)
+    s = _stream()
+    if stats[0] is not None:
+        # statistics left by the producers' epilogues (conv(..., gn_unit=...)): no statistics pass
+        _lib.check(lib.saspa_groupnorm_apply(C.byref(p), s), "saspa_groupnorm_apply(epilogue statistics)")
         return out
-    if gn_onepass_enabled():
-        # small images (the 8x8 level: no 128-row statistics blocks): statistics + apply in one launch
-        p = _lib.GroupNormParams()
-        p.dtype = _dt(x)
-        p.x0, p.x1, p.c0, p.c1 = _ptr(x), _ptr(x2), c0, c1
-        p.ldx0 = _pitch4(x)
-        p.ldx1 = 0 if x2 is None else _pitch4(x2)
-        p.batch, p.hw, p.groups, p.eps = b, h * w, groups, float(eps)
-        p.gamma, p.beta = _ptr(gamma), _ptr(beta)
-        p.partial, p.nsplit, p.scale_shift = None, 0, None
-        p.act, p.y, p.ldy = int(act), _ptr(out), _pitch4(out)
-        if lib.saspa_groupnorm_onepass_eligible(C.byref(p)):
-            _lib.check(lib.saspa_groupnorm_onepass(C.byref(p), _stream()), "saspa_groupnorm_onepass")
-            return out
+    # small images (the 8x8 level: no 128-row statistics blocks): statistics + apply in one launch
+    if gn_onepass_enabled() and lib.saspa_groupnorm_onepass_eligible(C.byref(p)):
+        _lib.check(lib.saspa_groupnorm_onepass(C.byref(p), s), "saspa_groupnorm_onepass")
+        return out
     nsplit = _gn_nsplit(b, h * w, ctot // 8)
     partial = torch.empty((b * nsplit * ctot * 2,), device=x.device, dtype=torch.float32)
-    p = _lib.GroupNormParams()
-    p.dtype = _dt(x)
-    p.x0, p.x1, p.c0, p.c1 = _ptr(x), _ptr(x2), c0, c1
-    p.ldx0 = _pitch4(x)
-    p.ldx1 = 0 if x2 is None else _pitch4(x2)
-    p.batch, p.hw, p.groups, p.eps = b, h * w, groups, float(eps)
-    p.gamma, p.beta = _ptr(gamma), _ptr(beta)
-    p.partial, p.nsplit, p.scale_shift = _ptr(partial), nsplit, None
-    p.act, p.y, p.ldy = int(act), _ptr(out), _pitch4(out)
-    s = _stream()
+    p.partial, p.nsplit = _ptr(partial), nsplit
     _lib.check(lib.saspa_groupnorm_stats(C.byref(p), s), "saspa_groupnorm_stats")
     _lib.check(lib.saspa_groupnorm_apply(C.byref(p), s), "saspa_groupnorm_apply")
     return out
@@ -928,20 +893,10 @@ def groupnorm_quant_mxfp8(x, gamma, beta, groups, eps, act=ACT_NONE, x2=None):
         raise ValueError("GroupNorm parameters / groups do not match the channel count")
     q = torch.empty((b, h, w, ctot), device=x.device, dtype=torch.uint8)
     qs = torch.empty((b, h, w, ctot // 32), device=x.device, dtype=torch.uint8)
-    p = _lib.GroupNormParams()
-    p.dtype = _dt(x)
-    p.x0, p.x1, p.c0, p.c1 = _ptr(x), _ptr(x2), c0, c1
-    p.ldx0 = _pitch4(x)
-    p.ldx1 = 0 if x2 is None else _pitch4(x2)
-    p.batch, p.hw, p.groups, p.eps = b, h * w, groups, float(eps)
-    p.gamma, p.beta = _ptr(gamma), _ptr(beta)
-    p.scale_shift, p.act, p.y, p.ldy = None, int(act), None, 0
+    stats = _epilogue_stats(x, x2, groups)
+    p = _gn_params(x, x2, gamma, beta, groups, eps, act, None, stats=stats)
     s = _stream()
-    g0, g1 = _epilogue_stats(x, x2, groups)
-    if g0 is not None:
-        p.partial, p.nsplit = None, 0
-        p.stats0, p.stats1, p.unit = _ptr(g0[0]), (_ptr(g1[0]) if g1 is not None else None), g0[1]
-    else:
+    if stats[0] is None:
         # pixel splits fixed per image (not _gn_nsplit's share of ~1024 workgroups over the batch): an image's statistics, and so its
         # bytes, do not depend on the batch it is quantised in
         nsplit = max(1, min(64, h * w // 16))
@@ -960,7 +915,7 @@ def _conv_mx_params(q, qs, w8, sw, bias, rowvec, residual, out):
     p.kh, p.kw, p.stride, p.pad, p.upsample = 3, 3, 1, 1, 0
     p.w8, p.ldw, p.N, p.Kp = _ptr(w8), w8.shape[1], w8.shape[0], w8.shape[1]
     p.sw, p.bias = _ptr(sw), _ptr(bias)
-    p.rowvec, p.ldrv = _ptr(rowvec), (0 if rowvec is None or rowvec.dim() == 1 or rowvec.shape[0] == 1 else rowvec.stride(0))
+    p.rowvec, p.ldrv = _ptr(rowvec), _ldrv(rowvec)
     n = w8.shape[0]
     p.residual, p.ldr = _ptr(residual), (0 if residual is None else _pitch4(residual))
     p.out, p.ldo = _ptr(out), n
@@ -1036,6 +991,20 @@ def layernorm_quant_fp8(x, gamma, beta, eps=1e-5):
     return q.view(*x.shape[:-1], c), scale
 
 
+def _gemm_f8_params(x2, wq, wscale, bias, residual, act, out):
+    """SaspaGemmF8Params of e4m3 rows x2 [M, K] @ wq [N, K]^T into the dense rows of `out`; the activation scales (per row, one
+    value, or MX block exponents) are the caller's."""
+    m, k = x2.shape
+    r2 = None if residual is None else residual.reshape(-1, residual.shape[-1])
+    p = _lib.GemmF8Params()
+    p.a, p.lda, p.w, p.ldw = _ptr(x2), x2.stride(0) if m > 1 else k, _ptr(wq), wq.stride(0)
+    p.M, p.N, p.K = m, wq.shape[0], k
+    p.sw, p.bias = _ptr(wscale), _ptr(bias)
+    p.residual, p.ldr = _ptr(r2), 0 if r2 is None else r2.stride(0)
+    p.act, p.out, p.ldo = int(act), _ptr(out), out.shape[1]
+    return p
+
+
 def linear_fp8(xq, xscale, wq, wscale, bias=None, *, residual=None, act=ACT_NONE, out_fp8_scale=None, amax=None, out_mx=False):
     """e4m3 activations (uint8 [..., K] + per-row scale, or ONE scale for the whole tensor: a 1-element `xscale`) @ e4m3 weights
     (uint8 [N, K] + per-channel scale)^T -> bf16 [..., N] (N / 2 with the fused GEGLU): `saspa_gemm_fp8`.
@@ -1054,17 +1023,12 @@ def linear_fp8(xq, xscale, wq, wscale, bias=None, *, residual=None, act=ACT_NONE
     if out_mx and (act != ACT_GEGLU or out_fp8_scale is not None or amax is not None):
         raise ValueError("out_mx exists in the GEGLU epilogue only, and not together with out_fp8_scale / amax")
     out = torch.empty((m, nout), device=xq.device, dtype=torch.uint8 if (out_fp8_scale is not None or out_mx) else torch.bfloat16)
-    r2 = None if residual is None else residual.reshape(-1, residual.shape[-1])
-    p = _lib.GemmF8Params()
-    p.a, p.lda, p.w, p.ldw = _ptr(x2), x2.stride(0) if m > 1 else k, _ptr(wq), wq.stride(0)
-    p.M, p.N, p.K = m, n, k
-    p.sa, p.sw, p.bias = _ptr(xscale), _ptr(wscale), _ptr(bias)
+    p = _gemm_f8_params(x2, wq, wscale, bias, residual, act, out)
+    p.sa = _ptr(xscale)
     if xscale.numel() == 1 and m > 1:
         p.sa_broadcast = 1
     elif xscale.numel() < m:
         raise ValueError(f"{xscale.numel()} activation scales for {m} rows")
-    p.residual, p.ldr = _ptr(r2), 0 if r2 is None else r2.stride(0)
-    p.act, p.out, p.ldo = int(act), _ptr(out), nout
     if out_fp8_scale is not None:
         if out_fp8_scale.dtype != torch.float32 or out_fp8_scale.numel() != 1:
             raise ValueError("out_fp8_scale is one fp32 value on the device")
@@ -1098,13 +1062,7 @@ def linear_mxfp8(q, qs, wq, wscale, bias=None, *, residual=None):
     if qs.dim() != 2 or qs.shape[0] != m or qs.shape[1] < k // 32 or qs.stride(1) != 1:
         raise ValueError(f"block exponents {tuple(qs.shape)} do not cover {m} rows of {k // 32} blocks")
     out = torch.empty((m, n), device=q.device, dtype=torch.bfloat16)
-    r2 = None if residual is None else residual.reshape(-1, residual.shape[-1])
-    p = _lib.GemmF8Params()
-    p.a, p.lda, p.w, p.ldw = _ptr(x2), x2.stride(0) if m > 1 else k, _ptr(wq), wq.stride(0)
-    p.M, p.N, p.K = m, n, k
-    p.sw, p.bias = _ptr(wscale), _ptr(bias)
-    p.residual, p.ldr = _ptr(r2), 0 if r2 is None else r2.stride(0)
-    p.act, p.out, p.ldo = int(ACT_NONE), _ptr(out), n
+    p = _gemm_f8_params(x2, wq, wscale, bias, residual, ACT_NONE, out)
     ldqs = qs.stride(0) if m > 1 else (k // 32 + 3) & ~3      # one row: the pitch is never used
     _launch("gemm", 2.0 * m * n * k, lambda: _lib.check(_L().saspa_gemm_mxfp8(C.byref(p), _ptr(qs), ldqs, _stream()), "saspa_gemm_mxfp8"),
             (m, n, k, 0, 1, 0, False, residual is not None, n, GEMM_FAMILY_FP8, 1))
@@ -1352,12 +1310,18 @@ def gather_row(table, index, dst):
     return dst
 
 
+def _check_table(what, name, table, rows, cols, index):
+    """A step's device table: fp32 [rows, cols], dense, read at row index[0] of a device int32 index."""
+    if table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] != cols or not table.is_contiguous() \
+            or index is None or index.dtype != torch.int32:
+        raise ValueError(f"{what}: {name} fp32 [{rows}, {cols}], int32 index")
+
+
 def ddim_step_dev(eps, x, nimg, hw, c, guidance, coefs, index, cfg=True):
     """(CFG +) DDIM update with the coefficients of row index[0] of the device table coefs [steps, 4]."""
     _check_dev(eps, x, coefs, index)
     lib = _L(x)
-    if coefs.dtype != torch.float32 or coefs.dim() != 2 or coefs.shape[1] != 4 or not coefs.is_contiguous() or index.dtype != torch.int32:
-        raise ValueError("ddim_step_dev: coefs fp32 [steps, 4], int32 index")
+    _check_table("ddim_step_dev", "coefs", coefs, "steps", 4, index)
     _lib.check(lib.saspa_ddim_step_dev(_dt(x), _ptr(eps), _ptr(x), nimg, hw, c, 8, int(bool(cfg)), float(guidance), _ptr(coefs),
                                        _ptr(index), _stream()), "saspa_ddim_step_dev")
     return x
@@ -1385,8 +1349,7 @@ def cfg3_ddim_step_dev(eps, x, nimg, hw, c, guidance, image_guidance, coefs, ind
     _check_dev(eps, x, coefs, index)
     _cfg3_shapes("cfg3_ddim_step_dev", eps, x, nimg, hw)
     lib = _L(x)
-    if coefs.dtype != torch.float32 or coefs.dim() != 2 or coefs.shape[1] != 4 or not coefs.is_contiguous() or index.dtype != torch.int32:
-        raise ValueError("cfg3_ddim_step_dev: coefs fp32 [steps, 4], int32 index")
+    _check_table("cfg3_ddim_step_dev", "coefs", coefs, "steps", 4, index)
     _lib.check(lib.saspa_cfg3_ddim_step_dev(_dt(x), _ptr(eps), _ptr(x), nimg, hw, c, 8, float(guidance), float(image_guidance),
                                             _ptr(coefs), _ptr(index), _stream()), "saspa_cfg3_ddim_step_dev")
     return x
@@ -1395,8 +1358,7 @@ def cfg3_ddim_step_dev(eps, x, nimg, hw, c, guidance, image_guidance, coefs, ind
 def cfg_plms_step_dev(eps, x, hist, saved, nimg, hw, c, guidance, table, index):
     """PLMS update with the evaluation's parameters read from row index[0] of the device table [evaluations, 10]."""
     _check_dev(eps, x, hist, saved, table, index)
-    if table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] != 10 or not table.is_contiguous() or index.dtype != torch.int32:
-        raise ValueError("cfg_plms_step_dev: table fp32 [evaluations, 10], int32 index")
+    _check_table("cfg_plms_step_dev", "table", table, "evaluations", 10, index)
     _lib.check(_L(x).saspa_cfg_plms_step_dev(_dt(x), _ptr(eps), _ptr(x), _ptr(hist), _ptr(saved), nimg, hw, c, 8, float(guidance),
                                                    _ptr(table), _ptr(index), _stream()), "saspa_cfg_plms_step_dev")
     return x
@@ -1406,9 +1368,8 @@ def cfg_unipc_step(eps, x, state, nimg, hw, c, guidance, row=None, table=None, i
     """CFG + one UniPC step; state [3, nimg, hw, 8] (last | m0 | m1).  `row`: 12 host floats, or (`table` fp32 [steps, 12],
     `index` int32 [1]) on the device."""
     _check_dev(eps, x, state, table, index)
-    if table is not None and (table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] != 12 or not table.is_contiguous()
-                              or index is None or index.dtype != torch.int32):
-        raise ValueError("cfg_unipc_step: table fp32 [steps, 12], int32 index")
+    if table is not None:
+        _check_table("cfg_unipc_step", "table", table, "steps", 12, index)
     r = None if row is None else (C.c_float * 12)(*[float(v) for v in row])
     _lib.check(_L(x).saspa_cfg_unipc_step(_dt(x), _ptr(eps), _ptr(x), _ptr(state), nimg, hw, c, 8, float(guidance), r,
                                                 _ptr(table), _ptr(index), _stream()), "saspa_cfg_unipc_step")
@@ -1418,9 +1379,8 @@ def cfg_unipc_step(eps, x, state, nimg, hw, c, guidance, row=None, table=None, i
 def unipc_step(eps, x, state, nimg, hw, c, row=None, table=None, index=None):
     """One UniPC step WITHOUT classifier-free guidance (sd_xl-turbo): eps / x [nimg, hw, 8]; state [3, nimg, hw, 8]."""
     _check_dev(eps, x, state, table, index)
-    if table is not None and (table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] != 12 or not table.is_contiguous()
-                              or index is None or index.dtype != torch.int32):
-        raise ValueError("unipc_step: table fp32 [steps, 12], int32 index")
+    if table is not None:
+        _check_table("unipc_step", "table", table, "steps", 12, index)
     r = None if row is None else (C.c_float * 12)(*[float(v) for v in row])
     _lib.check(_L(x).saspa_unipc_step(_dt(x), _ptr(eps), _ptr(x), _ptr(state), nimg, hw, c, 8, r, _ptr(table), _ptr(index),
                                             _stream()), "saspa_unipc_step")

@@ -18,13 +18,14 @@ end-to-end parity gate against the CPU oracle.  `pipe.enable_fp16()` before `.to
 SASPA_FP16=1) makes `torch.float16` mean IEEE fp16 for the text tower, UNet, ControlNet and
 scheduler steps (the f16-MFMA build of the kernels); the VAE and the safety checker stay out
 of fp16 (`enable_fp16` docstring).  Off by default."""
+import contextlib
 import os
 
 import numpy as np
 import torch
 from PIL import Image
 
-from . import models, ops
+from . import imageproc, models, ops
 from . import weights as W
 from .config import BLIP_DIFFUSION, BLIP_IMAGE_MEAN, BLIP_IMAGE_STD, IP2P, SD15, SDXL_TURBO
 from .scheduler import SDXL_TURBO_SCHEDULER_CONFIG, DDIMScheduler, PNDMScheduler, UniPCMultistepScheduler
@@ -35,6 +36,24 @@ class PipelineOutput:
     def __init__(self, images, nsfw_content_detected=None):
         self.images = images
         self.nsfw_content_detected = nsfw_content_detected
+
+
+_WEIGHTS = ("diffusion_pytorch_model.safetensors", "diffusion_pytorch_model.fp16.safetensors")
+_TEXT_WEIGHTS = ("model.safetensors", "model.fp16.safetensors")
+
+
+def _first_safetensors(d, names):
+    """The state dict of the first of `names` that exists in the directory d."""
+    for n in names:
+        p = os.path.join(d, n)
+        if os.path.exists(p):
+            return W.load_safetensors(p)
+    raise FileNotFoundError(f"no safetensors weights in {d}")
+
+
+def _rgb_u8(image):
+    """PIL image or array -> u8 [H,W,3] array."""
+    return np.asarray(image.convert("RGB") if isinstance(image, Image.Image) else image, dtype=np.uint8)
 
 
 def graphs_enabled():
@@ -66,6 +85,113 @@ def replay_queue_depth():
 
 
 side_stream = ops.side_stream          # one capture side stream per process and device (ops.side_stream)
+_GATES = {}                            # device -> the int64 pair a twin recorder's ops.clock_probe writes (nothing reads it)
+
+
+def _evaluate(unet, controlnet, x, cemb, step, cscale, cfg_pair, out, side=None):
+    """ONE network evaluation, eps(x) into `out`: UNet encoder, ControlNet, UNet decoder -- the captured step (step = None: the step
+    state is bound, _StepGraph._bind) and the eager loop (step = i) make the same launches with the same dispatch decisions.
+    cfg_pair: the encoders take the B rows the two CFG halves share (the halves of x are equal, the update keeps them so).
+    The UNet encoder and the ControlNet encoder are independent until the zero convs add the two.  The ControlNet
+    encoder runs
+      * on `side`, the capturing caller's second stream (fork_enabled): two branches of the captured graph.  Same kernels on the
+        same inputs as on one stream; one branch's launch gaps / tile tails / small deep-level kernels are filled by the other's work;
+      * under a launch recorder that wants the TIMED path's dispatch (bench.Recorder(twin=True)): on the shared side stream, between
+        begin_twin / end_twin.  Both streams are held behind one sleeping wave (ops.clock_probe, ~40 ms) until the host has enqueued
+        both launch sequences, so that they really run side by side;
+      * on the current stream otherwise.
+    The paired encoders walk the same shapes side by side, so their split-K is sized for half the chip each (ops.twin_branch) --
+    except under any other launch recorder, which times every launch ALONE and therefore gets the full-chip dispatch."""
+    xe = x[:x.shape[0] // 2] if cfg_pair else x
+    if controlnet is None:                                 # img2img baseline, InstructPix2Pix
+        mid, skips = unet.encode(xe, step, cfg_pair=cfg_pair)
+        if cfg_pair:
+            skips[0] = ops.dup_rows(skips[0])
+        return unet.decode(mid, skips, step, out=out)
+    ce = cemb[:cemb.shape[0] // 2] if cfg_pair else cemb
+    rec = ops._RECORDER
+    twin_rec = side is None and getattr(rec, "twin", False) and fork_enabled()
+    if twin_rec:
+        side = side_stream(x.device)
+        if x.device not in _GATES:
+            _GATES[x.device] = torch.zeros(2, dtype=torch.int64, device=x.device)
+        ops.clock_probe(_GATES[x.device], 10000)
+    if side is not None:
+        main = torch.cuda.current_stream()
+        side.wait_stream(main)
+    if twin_rec:
+        rec.begin_twin()
+    with ops.twin_branch(twin_rec or (fork_enabled() and rec is None)):
+        with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
+            cmid, cfeats = controlnet.encode(xe, step, conv_in_residual=ce, cfg_pair=cfg_pair)
+        mid, skips = unet.encode(xe, step, cfg_pair=cfg_pair)
+    if twin_rec:
+        rec.end_twin()
+    if side is not None:
+        main.wait_stream(side)
+    if twin_rec:
+        for t in (cmid, *cfeats):
+            t.record_stream(main)
+    skips, mid = controlnet.zero_convs(cmid, cfeats, cscale, skips, mid, cfg_pair=cfg_pair)
+    return unet.decode(mid, skips, step, out=out)
+
+
+def _schedule(sch, steps, t_start=0, branches=2):
+    """(timesteps of the network evaluations, plan rows | None) of a `steps`-step run.  PLMS: N + 1 evaluations, the second timestep
+    twice, a dict per evaluation; UniPC: a coefficient row per evaluation; DDIM: no plan, and t_start > 0 (img2img / SDEdit) keeps
+    the timesteps from that index on."""
+    if branches == 3 and isinstance(sch, (PNDMScheduler, UniPCMultistepScheduler)):
+        raise NotImplementedError("three guidance branches (InstructPix2Pix) run on DDIM only")
+    if t_start and isinstance(sch, PNDMScheduler):
+        raise NotImplementedError("img2img runs on DDIM / UniPC (the reference switches non-BLIP pipelines away from PNDM)")
+    if t_start and isinstance(sch, UniPCMultistepScheduler):
+        raise NotImplementedError("img2img with UniPC: the multistep history would have to start mid-schedule")
+    if isinstance(sch, (PNDMScheduler, UniPCMultistepScheduler)):
+        plan = sch.plan(steps)
+        return [t for t, _ in plan], [r for _, r in plan]
+    return list(sch.set_timesteps(steps))[t_start:], None
+
+
+def _multistep_state(sch, x, nimg, static=False):
+    """What a multistep update keeps between evaluations, zeroed: UniPC's last sample + two x0-predictions in one buffer; PLMS's
+    4-slot history ring and, for the captured step (static), the buffer of the saved sample (the eager update clones it)."""
+    def z(*lead):
+        return torch.zeros(lead + (nimg,) + tuple(x.shape[1:]), device=x.device, dtype=x.dtype)
+    if isinstance(sch, UniPCMultistepScheduler):
+        return dict(state=z(3))
+    if isinstance(sch, PNDMScheduler):
+        return dict(hist=z(4), saved=z()) if static else dict(hist=z(4))
+    return {}
+
+
+def _update(sch, eps, x, mem, nimg, hw, nc, cfg, guidance, branches=2, image_guidance=1.0, row=None, table=None, index=None):
+    """The scheduler update that closes an evaluation, (guided) eps -> x in place, in one of two forms: `table` + `index` (the
+    captured step: the evaluation's coefficients are read on the device) or `row` (the eager loop: the plan's entry of the
+    evaluation; for DDIM, which has no plan, its timestep).  branches = 3: x holds the groups (uncond | image | text)."""
+    if isinstance(sch, UniPCMultistepScheduler):
+        if cfg:
+            ops.cfg_unipc_step(eps, x, mem["state"], nimg, hw, nc, guidance, row=row, table=table, index=index)
+        else:
+            ops.unipc_step(eps, x, mem["state"], nimg, hw, nc, row=row, table=table, index=index)
+    elif isinstance(sch, PNDMScheduler):
+        if table is not None:
+            ops.cfg_plms_step_dev(eps, x, mem["hist"], mem["saved"], nimg, hw, nc, guidance, table, index)
+        else:
+            if row["save_sample"]:
+                mem["saved"] = x[:nimg].clone()
+            ops.cfg_plms_step(eps, x, mem["hist"], mem["saved"] if row["use_saved"] else None, nimg, hw, nc, guidance,
+                              row["store_slot"], row["w_cur"], row["w_hist"], row["coef_sample"], row["coef_model"])
+    elif table is not None:
+        if branches == 3:
+            ops.cfg3_ddim_step_dev(eps, x, nimg, hw, nc, guidance, image_guidance, table, index)
+        else:
+            ops.ddim_step_dev(eps, x, nimg, hw, nc, guidance, table, index, cfg=cfg)
+    elif branches == 3:
+        ops.cfg3_ddim_step(eps, x, nimg, hw, nc, guidance, image_guidance, *sch.step_coefficients(row))
+    elif cfg:
+        ops.cfg_ddim_step(eps, x, nimg, hw, nc, guidance, *sch.step_coefficients(row))
+    else:
+        ops.ddim_step(eps, x, nimg, hw, nc, *sch.step_coefficients(row))
 
 
 class _StepGraph:
@@ -86,20 +212,13 @@ class _StepGraph:
         self.eps = torch.zeros(x_shape, device=dev, dtype=dt)
         self.cemb = torch.zeros(cemb_shape, device=dev, dtype=dt)
         self.idx = torch.zeros((1,), device=dev, dtype=torch.int32)
-        self.plms = isinstance(pipe.scheduler, PNDMScheduler)
-        self.unipc = isinstance(pipe.scheduler, UniPCMultistepScheduler)
-        if self.unipc:      # per-step coefficient rows; last sample + two x0-predictions in one static buffer
-            self.evals = steps
-            self.coefs = torch.zeros((steps, UniPCMultistepScheduler.ROW), device=dev, dtype=torch.float32)
-            self.state = torch.zeros((3, x_shape[0] // 2 if cfg else x_shape[0]) + tuple(x_shape[1:]), device=dev, dtype=dt)
-        elif self.plms:       # N + 1 evaluations; per-evaluation parameters, the 4-slot history ring and the saved sample
-            self.evals = steps + 1
-            self.coefs = torch.zeros((self.evals, 10), device=dev, dtype=torch.float32)
-            self.hist = torch.zeros((4, x_shape[0] // 2) + tuple(x_shape[1:]), device=dev, dtype=dt)
-            self.saved = torch.zeros((x_shape[0] // 2,) + tuple(x_shape[1:]), device=dev, dtype=dt)
-        else:
-            self.evals = steps
-            self.coefs = torch.zeros((steps, 4), device=dev, dtype=torch.float32)
+        self.nimg = x_shape[0] // self.branches if cfg else x_shape[0]
+        self.sch = sch = pipe.scheduler
+        # per-evaluation coefficient rows (PLMS: N + 1 evaluations) and the multistep history, in static buffers
+        self.evals = steps + 1 if isinstance(sch, PNDMScheduler) else steps
+        width = UniPCMultistepScheduler.ROW if isinstance(sch, UniPCMultistepScheduler) else 10 if isinstance(sch, PNDMScheduler) else 4
+        self.coefs = torch.zeros((self.evals, width), device=dev, dtype=torch.float32)
+        self.mem = _multistep_state(sch, self.x, self.nimg, static=True)
         self.nets = (pipe.unet,) if pipe.controlnet is None else (pipe.unet, pipe.controlnet)   # ControlNet-free: img2img baseline
         self.tables, self.curs, self.ctx_kv = [], [], []
         self.graph = None
@@ -135,63 +254,32 @@ class _StepGraph:
                             dst.copy_(src)
         self.x.copy_(x)
         self.cemb.copy_(cemb)
-        if self.unipc:
-            if first:
-                self.coefs.copy_(torch.tensor(self.plan, dtype=torch.float32))
-            self.state.zero_()
-        elif self.plms:
-            if first:
+        if first:
+            if isinstance(self.sch, PNDMScheduler):
                 rows = [[d["store_slot"], d["w_cur"], *d["w_hist"], d["coef_sample"], d["coef_model"], float(d["save_sample"]),
                          float(d["use_saved"])] for d in self.plan]
-                self.coefs.copy_(torch.tensor(rows, dtype=torch.float32))
-            self.hist.zero_()
-        elif first:
-            self.coefs.copy_(torch.tensor([sch.step_coefficients(t) for t in ts], dtype=torch.float32))
-        self.idx.zero_()
+            else:
+                rows = self.plan if self.plan is not None else [sch.step_coefficients(t) for t in ts]
+            self.coefs.copy_(torch.tensor(rows, dtype=torch.float32))
+        self._rewind()
         self._bind()
+
+    def _rewind(self):
+        """Back to the first evaluation: the step counter and the multistep history."""
+        self.idx.zero_()
+        for buf in self.mem.values():
+            buf.zero_()
 
     def _step(self):
         pipe, x = self.pipe, self.x
         for net, tab, cur in zip(self.nets, self.tables, self.curs):
             ops.gather_row(tab, self.idx, cur)
-        pair = self.cfg_pair
-        # (pair: the encoders take the B rows the two CFG halves share -- the halves of x are equal, the update keeps them so)
-        xe = x[:x.shape[0] // 2] if pair else x
-        ce = self.cemb[:self.cemb.shape[0] // 2] if pair and pipe.controlnet is not None else self.cemb
-        if pipe.controlnet is None:
-            mid2, skips2 = pipe.unet.encode(xe, None, cfg_pair=pair)
-            if pair:
-                skips2[0] = ops.dup_rows(skips2[0])
-        elif fork_enabled():
-            # the UNet encoder and the ControlNet encoder are independent until the zero convs add the two: two
-            # branches of the captured graph.  Same kernels on the same inputs -> bit-identical to the single-stream order; what
-            # changes is that one branch's launch gaps / tile tails / small deep-level kernels are filled by the other's work.
-            main = torch.cuda.current_stream()
-            if self.side is None:
-                self.side = side_stream(x.device)
-            self.side.wait_stream(main)
-            with ops.twin_branch(ops._RECORDER is None):   # both encoders walk the same shapes side by side: half the K slices each
-                with torch.cuda.stream(self.side):
-                    cmid, cfeats = pipe.controlnet.encode(xe, None, conv_in_residual=ce, cfg_pair=pair)
-                mid, skips = pipe.unet.encode(xe, None, cfg_pair=pair)
-            main.wait_stream(self.side)
-            skips2, mid2 = pipe.controlnet.zero_convs(cmid, cfeats, self.cscale, skips, mid, cfg_pair=pair)
-        else:
-            mid, skips = pipe.unet.encode(xe, None, cfg_pair=pair)
-            skips2, mid2 = pipe.controlnet.forward(xe, None, ce, self.cscale, skips, mid, cfg_pair=pair)
-        pipe.unet.decode(mid2, skips2, None, out=self.eps)
-        nimg = x.shape[0] // self.branches if self.cfg else x.shape[0]
-        nc, hw = pipe.cfgs["unet"]["out_channels"], x.shape[1] * x.shape[2]
-        if self.branches == 3:
-            ops.cfg3_ddim_step_dev(self.eps, x, nimg, hw, nc, self.guidance, self.image_guidance, self.coefs, self.idx)
-        elif self.unipc and self.cfg:
-            ops.cfg_unipc_step(self.eps, x, self.state, nimg, hw, nc, self.guidance, table=self.coefs, index=self.idx)
-        elif self.unipc:
-            ops.unipc_step(self.eps, x, self.state, nimg, hw, nc, table=self.coefs, index=self.idx)
-        elif self.plms:
-            ops.cfg_plms_step_dev(self.eps, x, self.hist, self.saved, nimg, hw, nc, self.guidance, self.coefs, self.idx)
-        else:
-            ops.ddim_step_dev(self.eps, x, nimg, hw, nc, self.guidance, self.coefs, self.idx, cfg=self.cfg)
+        if pipe.controlnet is not None and fork_enabled() and self.side is None:
+            self.side = side_stream(x.device)
+        _evaluate(pipe.unet, pipe.controlnet, x, self.cemb, None, self.cscale, self.cfg_pair, self.eps,
+                  side=self.side if fork_enabled() else None)
+        _update(self.sch, self.eps, x, self.mem, self.nimg, x.shape[1] * x.shape[2], pipe.cfgs["unet"]["out_channels"], self.cfg,
+                self.guidance, self.branches, self.image_guidance, table=self.coefs, index=self.idx)
         ops.index_add(self.idx, 1)
 
     def run_on(self, x, cemb, ctx, ts, added=None, plan=None):
@@ -207,11 +295,7 @@ class _StepGraph:
             self._step()                                   # eager warm-up step (also validates every launch argument)
             torch.cuda.synchronize()
             self.x.copy_(x0)
-            self.idx.zero_()
-            if self.plms:
-                self.hist.zero_()
-            if self.unipc:
-                self.state.zero_()
+            self._rewind()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
                 self._step()
@@ -269,22 +353,19 @@ class StableDiffusionControlNetPipeline:
     def from_pretrained(cls, base_dir, controlnet_dir, cfgs=SD15):
         """Local diffusers-format checkpoints (the layout `from_pretrained` downloads):
         {base}/unet, {base}/vae, {base}/text_encoder, {base}/tokenizer and the ControlNet dir."""
-        def f(d, *names):
-            for n in names:
-                p = os.path.join(d, n)
-                if os.path.exists(p):
-                    return W.load_safetensors(p)
-            raise FileNotFoundError(f"no safetensors weights in {d}")
-        sds = dict(
-            unet=f(os.path.join(base_dir, "unet"), "diffusion_pytorch_model.safetensors", "diffusion_pytorch_model.fp16.safetensors"),
-            vae=f(os.path.join(base_dir, "vae"), "diffusion_pytorch_model.safetensors", "diffusion_pytorch_model.fp16.safetensors"),
-            text=f(os.path.join(base_dir, "text_encoder"), "model.safetensors", "model.fp16.safetensors"),
-            controlnet=f(controlnet_dir, "diffusion_pytorch_model.safetensors", "diffusion_pytorch_model.fp16.safetensors"),
-        )
+        sds = cls._base_state_dicts(base_dir, cfgs)
+        sds["controlnet"] = _first_safetensors(controlnet_dir, _WEIGHTS)
+        return cls(sds, cfgs, tokenizer=make_tokenizer(os.path.join(base_dir, "tokenizer"), cfgs["text"]["vocab"]))
+
+    @staticmethod
+    def _base_state_dicts(base_dir, cfgs):
+        sds = dict(unet=_first_safetensors(os.path.join(base_dir, "unet"), _WEIGHTS),
+                   vae=_first_safetensors(os.path.join(base_dir, "vae"), _WEIGHTS),
+                   text=_first_safetensors(os.path.join(base_dir, "text_encoder"), _TEXT_WEIGHTS))
         sc = os.path.join(base_dir, "safety_checker")
         if "safety" in cfgs and os.path.isdir(sc):
-            sds["safety"] = f(sc, "model.safetensors", "model.fp16.safetensors")
-        return cls(sds, cfgs, tokenizer=make_tokenizer(os.path.join(base_dir, "tokenizer"), cfgs["text"]["vocab"]))
+            sds["safety"] = _first_safetensors(sc, _TEXT_WEIGHTS)
+        return sds
 
     def to(self, device, dtype=None):
         device = torch.device(device)
@@ -427,111 +508,72 @@ class StableDiffusionControlNetPipeline:
     def _positive_context(self, prompt_ids, query_embeds=None):
         return self.encode_prompts(prompt_ids)
 
-    def _sample(self, x2, b, hw, ctx, cemb2, steps, guidance_scale, cscale, t_start=0, branches=2, image_guidance=1.0):
-        """The denoising loop on the CFG-doubled latents x2 [2B,h,w,8] (in place).  t_start > 0 (img2img / SDEdit): only the
-        timesteps from index t_start of the `steps`-step schedule run (DDIM only).  branches = 3 (InstructPix2Pix): x2 is
-        [3B,h,w,8] in the groups (uncond | image | text) and every update is ops.cfg3_ddim_step (DDIM only)."""
+    @staticmethod
+    def _guidance_context(neg, pos, branches=2):
+        """Negative [1 | B,77,C] and positive [B,77,C] contexts -> [branches * B,77,C], unconditional groups first."""
+        if neg.shape[0] == 1 and pos.shape[0] > 1:
+            neg = neg.expand(pos.shape[0], -1, -1)
+        if neg.shape[1] != pos.shape[1]:
+            raise ValueError(f"negative context has {neg.shape[1]} tokens, positive {pos.shape[1]}")
+        return torch.cat([neg] * (branches - 1) + [pos], 0).contiguous()
+
+    def _device_u8(self, images_u8):
+        """u8 [B,H,W,3], numpy or tensor -> contiguous device tensor."""
+        # (np.array: a writable copy -- arrays that come out of PIL are read-only and torch warns about wrapping those)
+        t = images_u8 if torch.is_tensor(images_u8) else torch.from_numpy(np.array(images_u8))
+        return ops.h2d(t, self.device).contiguous()
+
+    def _check_sides(self, images, what):
+        """The UNet halves the latent (H/8 x W/8) once per level below the first and doubles it back exactly; the reference only
+        ever feeds multiples of 64 (all_utils/utils.py:65-77 rounds both sides to 64)."""
+        hh, ww = images.shape[1:3]
+        mult = 8 << (len(self.cfgs["unet"]["block_out"]) - 1)
+        if hh % mult or ww % mult:
+            raise ValueError(f"{what} sides must be multiples of {mult} (got {hh}x{ww})")
+
+    @staticmethod
+    def _check_latents(latents, channels, images, what, on_device=False):
+        b, hh, ww, _ = images.shape
+        want = (b, hh // 8, ww // 8, 8) if on_device else (b, channels, hh // 8, ww // 8)
+        if tuple(latents.shape) != want:
+            raise ValueError(f"latents shape {tuple(latents.shape)} does not match the {what} image {hh}x{ww}")
+
+    def _decode(self, x, return_latents=False):
+        """Final latents [B,h,w,8] -> device u8 images [B,H,W,3] through the VAE decoder and the safety checker (flags in
+        `last_nsfw`; None for a family without one); with return_latents also the latents and the decoder's output."""
+        z = ops.scale(x, 1.0 / self.cfgs["vae"]["scaling_factor"])
+        # (fp16 compute, SDXL's upcast_vae(): the hand-off to the bf16 / fp32 VAE; a no-op otherwise)
+        img = self.vae.decode(z.to(self.vae.dtype))
+        out, self.last_nsfw = self.run_safety_checker(ops.act_to_u8(img))
+        return (out, x, img) if return_latents else out
+
+    def _sample(self, x2, b, hw, ctx, cemb2, steps, guidance_scale, cscale, t_start=0, branches=2, image_guidance=1.0, cfg=True,
+                added=None):
+        """The denoising loop on the CFG-doubled latents x2 [2B,h,w,8] of b images (in place): the captured step replayed, or with
+        SASPA_GRAPH=0 / under a launch recorder the same evaluation and update launched from Python.  t_start > 0 (img2img /
+        SDEdit): only the timesteps from index t_start of the `steps`-step schedule run (DDIM only).  branches = 3
+        (InstructPix2Pix): x2 is [3B,h,w,8] in the groups (uncond | image | text) and every update is ops.cfg3_ddim_step (DDIM
+        only).  cfg = False (SDXL-Turbo): x2 is [B,h,w,8], no guidance.  added: SDXL's (pooled text embeddings, time ids)."""
         sch = self.scheduler
-        nc = self.cfgs["unet"]["out_channels"]
-        pair = self.CFG_PREFIX and cfg_prefix_enabled() and branches == 2
-        if branches == 3 and isinstance(sch, (PNDMScheduler, UniPCMultistepScheduler)):
-            raise NotImplementedError("three guidance branches (InstructPix2Pix) run on DDIM only")
-        if t_start and isinstance(sch, PNDMScheduler):
-            raise NotImplementedError("img2img runs on DDIM / UniPC (the reference switches non-BLIP pipelines away from PNDM)")
+        pair = cfg and self.CFG_PREFIX and cfg_prefix_enabled() and branches == 2
+        guidance_scale = guidance_scale if cfg else 0.0
+        ts, plan = _schedule(sch, steps, t_start, branches)
         if graphs_enabled():
-            if isinstance(sch, PNDMScheduler):
-                plan = sch.plan(steps)                 # N+1 evaluations, the second timestep twice
-                ts, plan = [t for t, _ in plan], [d for _, d in plan]
-            elif isinstance(sch, UniPCMultistepScheduler):
-                if t_start:
-                    raise NotImplementedError("img2img with UniPC: the multistep history would have to start mid-schedule")
-                plan = sch.plan(steps)
-                ts, plan = [t for t, _ in plan], [r for _, r in plan]
-            else:
-                ts, plan = list(sch.set_timesteps(steps))[t_start:], None
-            g = self._step_graph(x2, cemb2, ctx, len(ts) if t_start else steps, True, guidance_scale, cscale, ts, cfg_pair=pair,
+            g = self._step_graph(x2, cemb2, ctx, len(ts) if t_start else steps, cfg, guidance_scale, cscale, ts, cfg_pair=pair,
                                  branches=branches, image_guidance=image_guidance)
-            x2.copy_(g.run_on(x2, cemb2, ctx, ts, plan=plan))
+            x2.copy_(g.run_on(x2, cemb2, ctx, ts, added, plan=plan))
             return
         nets = [self.unet] + ([self.controlnet] if self.controlnet is not None else [])
         for net in nets:
             net.prepare_context(ctx)
+        for net in nets:
+            net.prepare_timesteps(ts, added)
         eps = torch.zeros_like(x2)
-
-        rec = ops._RECORDER
-        twin_rec = rec is not None and getattr(rec, "twin", False) and self.controlnet is not None and fork_enabled()
-        gate = torch.zeros(2, dtype=torch.int64, device=x2.device) if twin_rec else None
-
-        # (pair: the same launches as _StepGraph._step -- the encoders take the B rows the two CFG halves share)
-        xe = x2[:b] if pair else x2
-        ce = cemb2[:b] if pair and self.controlnet is not None else cemb2
-
-        def evaluate(i):
-            if self.controlnet is None:
-                mid, skips = self.unet.encode(xe, i, cfg_pair=pair)
-                if pair:
-                    skips[0] = ops.dup_rows(skips[0])
-            elif twin_rec:
-                # a launch recorder that wants the TIMED path's dispatch (bench.Recorder(twin=True)): the two encoders on two streams
-                # with the shared-chip hint, as the captured step runs them.  Both streams are held behind one sleeping wave
-                # (ops.clock_probe, ~40 ms) until the host has enqueued both launch sequences, so that they really run side by side
-                main, side = torch.cuda.current_stream(), side_stream(x2.device)
-                ops.clock_probe(gate, 10000)
-                side.wait_stream(main)
-                rec.begin_twin()
-                with ops.twin_branch(True):
-                    with torch.cuda.stream(side):
-                        cmid, cfeats = self.controlnet.encode(xe, i, conv_in_residual=ce, cfg_pair=pair)
-                    mid, skips = self.unet.encode(xe, i, cfg_pair=pair)
-                rec.end_twin()
-                main.wait_stream(side)
-                for t in (cmid, *cfeats):
-                    t.record_stream(main)
-                skips, mid = self.controlnet.zero_convs(cmid, cfeats, cscale, skips, mid, cfg_pair=pair)
-            else:
-                # the same launches, with the same dispatch decisions, as the two-branch graph step (_StepGraph._step): the
-                # split-K of the paired encoders is sized for two concurrent branches (ops.twin_branch) -- except under a
-                # launch recorder, which times every launch ALONE and therefore gets the full-chip dispatch
-                with ops.twin_branch(fork_enabled() and ops._RECORDER is None):
-                    cmid, cfeats = self.controlnet.encode(xe, i, conv_in_residual=ce, cfg_pair=pair)
-                    mid, skips = self.unet.encode(xe, i, cfg_pair=pair)
-                skips, mid = self.controlnet.zero_convs(cmid, cfeats, cscale, skips, mid, cfg_pair=pair)
-            self.unet.decode(mid, skips, i, out=eps)
-
-        if isinstance(sch, PNDMScheduler):
-            plan = sch.plan(steps)                     # N+1 evaluations, the second timestep twice
-            ts = [t for t, _ in plan]
-            for net in nets:
-                net.prepare_timesteps(ts)
-            hist = torch.zeros((4,) + tuple(x2[:b].shape), device=x2.device, dtype=x2.dtype)
-            saved = None
-            for i, (t, d) in enumerate(plan):
-                if d["save_sample"]:
-                    saved = x2[:b].clone()
-                evaluate(i)
-                ops.cfg_plms_step(eps, x2, hist, saved if d["use_saved"] else None, b, hw, nc, guidance_scale,
-                                  d["store_slot"], d["w_cur"], d["w_hist"], d["coef_sample"], d["coef_model"])
-        elif isinstance(sch, UniPCMultistepScheduler):
-            if t_start:
-                raise NotImplementedError("img2img with UniPC: the multistep history would have to start mid-schedule")
-            plan = sch.plan(steps)
-            ts = [t for t, _ in plan]
-            for net in nets:
-                net.prepare_timesteps(ts)
-            state = torch.zeros((3,) + tuple(x2[:b].shape), device=x2.device, dtype=x2.dtype)
-            for i, (t, row) in enumerate(plan):
-                evaluate(i)
-                ops.cfg_unipc_step(eps, x2, state, b, hw, nc, guidance_scale, row=row)
-        else:
-            ts = list(sch.set_timesteps(steps))[t_start:]
-            for net in nets:
-                net.prepare_timesteps(ts)
-            for i, t in enumerate(ts):
-                evaluate(i)
-                if branches == 3:
-                    ops.cfg3_ddim_step(eps, x2, b, hw, nc, guidance_scale, image_guidance, *sch.step_coefficients(t))
-                else:
-                    ops.cfg_ddim_step(eps, x2, b, hw, nc, guidance_scale, *sch.step_coefficients(t))
+        mem = _multistep_state(sch, x2, b)
+        for i, t in enumerate(ts):
+            _evaluate(self.unet, self.controlnet, x2, cemb2, i, cscale, pair, eps)
+            _update(sch, eps, x2, mem, b, hw, self.cfgs["unet"]["out_channels"], cfg, guidance_scale, branches, image_guidance,
+                    row=t if plan is None else plan[i])
 
     def _step_graph(self, x, cemb, ctx, steps, cfg, guidance, cscale, ts, cfg_pair=False, branches=2, image_guidance=1.0):
         # the timesteps are part of the key: the cached time tables / coefficients follow the scheduler's configuration
@@ -556,39 +598,18 @@ class StableDiffusionControlNetPipeline:
         self._need_device()
         if guidance_scale <= 1.0:
             raise NotImplementedError("guidance_scale <= 1 (no CFG) belongs to the SDXL-Turbo branch (SURVEY a9)")
-        dev, dt = self.device, self.dtype
-        # (np.array: a writable copy -- arrays that come out of PIL are read-only and torch warns about wrapping those)
-        ctrl = torch.from_numpy(np.array(control_u8)) if not torch.is_tensor(control_u8) else control_u8
-        ctrl = ops.h2d(ctrl, dev).contiguous()
+        ctrl = self._device_u8(control_u8)
         b, hh, ww, _ = ctrl.shape
-        mult = 8 << (len(self.cfgs["unet"]["block_out"]) - 1)
-        if hh % mult or ww % mult:
-            # the UNet halves the latent (H/8 x W/8) once per level below the first and doubles it back exactly; the
-            # reference only ever feeds multiples of 64 (all_utils/utils.py:65-77 rounds both sides to 64)
-            raise ValueError(f"control image sides must be multiples of {mult} (got {hh}x{ww})")
-        want = (b, hh // 8, ww // 8, 8) if latents_on_device else (b, self.cfgs["unet"]["in_channels"], hh // 8, ww // 8)
-        if tuple(latents.shape) != want:
-            raise ValueError(f"latents shape {tuple(latents.shape)} does not match the control image {hh}x{ww}")
+        self._check_sides(ctrl, "control image")
+        self._check_latents(latents, self.cfgs["unet"]["in_channels"], ctrl, "control", latents_on_device)
         pos = self._positive_context(prompt_ids, query_embeds)
-        neg = self._negative_context(negative_ids)
-        if neg.shape[0] == 1 and b > 1:
-            neg = neg.expand(b, -1, -1)
-        if neg.shape[1] != pos.shape[1]:
-            raise ValueError(f"negative context has {neg.shape[1]} tokens, positive {pos.shape[1]}")
-        ctx = torch.cat([neg, pos], 0).contiguous()                       # [2B,77,C]: uncond first
-        cond = ops.u8_to_act(ctrl, dt)
-        cemb = self.controlnet.cond_embedding(cond)
+        ctx = self._guidance_context(self._negative_context(negative_ids), pos)
+        cemb = self.controlnet.cond_embedding(ops.u8_to_act(ctrl, self.dtype))
         cemb2 = torch.cat([cemb, cemb], 0)
         x = latents if latents_on_device else self.latents_to_device(latents)
         x2 = torch.cat([x, x], 0).contiguous()
-        h8, w8 = hh // 8, ww // 8
-        self._sample(x2, b, h8 * w8, ctx, cemb2, num_inference_steps, guidance_scale, controlnet_conditioning_scale)
-        z = ops.scale(x2[:b], 1.0 / self.cfgs["vae"]["scaling_factor"])
-        img = self.vae.decode(z.to(self.vae.dtype))          # (fp16 compute: the hand-off to the bf16 / fp32 VAE; a no-op otherwise)
-        out, self.last_nsfw = self.run_safety_checker(ops.act_to_u8(img))
-        if return_latents:
-            return out, x2[:b], img
-        return out
+        self._sample(x2, b, (hh // 8) * (ww // 8), ctx, cemb2, num_inference_steps, guidance_scale, controlnet_conditioning_scale)
+        return self._decode(x2[:b], return_latents)
 
     # ---- the reference's call form ----------------------------------------------------
     def __call__(self, prompt=None, image=None, num_inference_steps=50, generator=None, guidance_scale=7.5,
@@ -596,21 +617,25 @@ class StableDiffusionControlNetPipeline:
         self._need_device()
         if image is None or prompt is None:
             raise ValueError("`prompt` and `image` (the control image) are required")
-        ctrl = np.asarray(image.convert("RGB") if isinstance(image, Image.Image) else image, dtype=np.uint8)
+        ctrl = _rgb_u8(image)
         if ctrl.ndim != 3 or ctrl.shape[2] != 3:
             raise ValueError("control image must be RGB")
-        hh, ww = ctrl.shape[:2]
-        if generator is not None and generator.device.type != "cpu":
-            raise NotImplementedError("the reference passes the global CPU generator (run_aug/run_aug.py:324)")
-        lat = torch.randn((1, self.cfgs["unet"]["in_channels"], hh // 8, ww // 8), generator=generator,
-                          dtype=self.noise_dtype)
+        lat = self._noise(ctrl, generator)
         ids = self.tokenizer(str(prompt))
         neg = self.tokenizer(negative_prompt if negative_prompt is not None else "")
-        out = self.generate_batch(ids, neg, ctrl[None], lat, num_inference_steps, guidance_scale,
-                                  controlnet_conditioning_scale)
-        arr = out.cpu().numpy()
+        return self._output(self.generate_batch(ids, neg, ctrl[None], lat, num_inference_steps, guidance_scale,
+                                                controlnet_conditioning_scale))
+
+    def _noise(self, image, generator, channels=None):
+        """One [1,C,H/8,W/8] draw for an [H,W,3] image, in the reference's pipeline dtype, from its CPU generator."""
+        if generator is not None and generator.device.type != "cpu":
+            raise NotImplementedError("the reference passes the global CPU generator (run_aug/run_aug.py:324)")
+        shape = (1, channels or self.cfgs["unet"]["in_channels"], image.shape[0] // 8, image.shape[1] // 8)
+        return torch.randn(shape, generator=generator, dtype=self.noise_dtype)
+
+    def _output(self, images):
         nsfw = None if self.last_nsfw is None else [bool(v) for v in self.last_nsfw.cpu().tolist()]
-        return PipelineOutput([Image.fromarray(a) for a in arr], nsfw)
+        return PipelineOutput([Image.fromarray(a) for a in images.cpu().numpy()], nsfw)
 
 
 class StableDiffusionControlNetImg2ImgPipeline(StableDiffusionControlNetPipeline):
@@ -649,32 +674,22 @@ class StableDiffusionControlNetImg2ImgPipeline(StableDiffusionControlNetPipeline
             raise ValueError(f"After adjusting the num_inference_steps by strength parameter: {strength}, the number of pipeline "
                              f"steps is {kept} which is < 1 and not appropriate for this pipeline.")
         dev, dt = self.device, self.dtype
-        to_dev = lambda a: ops.h2d(a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a)), dev).contiguous()   # noqa: E731
         if (control_u8 is None) != (self.controlnet is None):
             raise ValueError("a control image is required by the ControlNet pipelines and refused by the ControlNet-free one")
-        src = to_dev(source_u8)
-        ctrl = to_dev(control_u8) if control_u8 is not None else src
+        src = self._device_u8(source_u8)
+        ctrl = self._device_u8(control_u8) if control_u8 is not None else src
         b, hh, ww, _ = ctrl.shape
         if tuple(src.shape) != tuple(ctrl.shape):
             raise ValueError("source and control images must have the same size")
-        mult = 8 << (len(self.cfgs["unet"]["block_out"]) - 1)
-        if hh % mult or ww % mult:
-            raise ValueError(f"image sides must be multiples of {mult} (got {hh}x{ww})")
-        from . import imageproc
-        vdt = self.vae_encoder.dtype                   # == dt unless fp16 compute is on (the VAE stays bf16 / fp32 then)
-        px = imageproc.normalize_u8(src, vdt, (0.5, 0.5, 0.5), (0.5, 0.5, 0.5))         # VaeImageProcessor: [0,255] -> [-1,1]
-        with ops.f32_gemm_mode(self.vae.f32_gemm):
-            moments = self.vae_encoder.encode(px).to(dt)
+        self._check_sides(ctrl, "image")
+        moments = self._encode_image(src)
         sch = self.scheduler
         ts = list(sch.set_timesteps(num_inference_steps))
         a_t = float(sch.alphas_cumprod[int(ts[t_start])])
         x = ops.vae_sample_noise(moments, self.latents_to_device(sample_noise), self.latents_to_device(noise),
                                  self.cfgs["vae"]["scaling_factor"], a_t ** 0.5, (1.0 - a_t) ** 0.5)
         pos = self._positive_context(prompt_ids)
-        neg = self._negative_context(negative_ids)
-        if neg.shape[0] == 1 and b > 1:
-            neg = neg.expand(b, -1, -1)
-        ctx = torch.cat([neg, pos], 0).contiguous()
+        ctx = self._guidance_context(self._negative_context(negative_ids), pos)
         if self.controlnet is not None:
             cemb = self.controlnet.cond_embedding(ops.u8_to_act(ctrl, dt))
             cemb2 = torch.cat([cemb, cemb], 0)
@@ -683,31 +698,27 @@ class StableDiffusionControlNetImg2ImgPipeline(StableDiffusionControlNetPipeline
         x2 = torch.cat([x, x], 0).contiguous()
         self._sample(x2, b, (hh // 8) * (ww // 8), ctx, cemb2, num_inference_steps, guidance_scale,
                      controlnet_conditioning_scale, t_start=t_start)
-        img = self.vae.decode(ops.scale(x2[:b], 1.0 / self.cfgs["vae"]["scaling_factor"]).to(self.vae.dtype))
-        out, self.last_nsfw = self.run_safety_checker(ops.act_to_u8(img))
-        if return_latents:
-            return out, x2[:b], img
-        return out
+        return self._decode(x2[:b], return_latents)
+
+    def _encode_image(self, images_u8):
+        """Device u8 [B,H,W,3] -> the VAE posterior's moments [B,H/8,W/8,8] (mean | logvar) in the compute dtype."""
+        # VaeImageProcessor: [0,255] -> [-1,1], in the encoder's dtype (== the compute dtype unless fp16 compute is on)
+        px = imageproc.normalize_u8(images_u8, self.vae_encoder.dtype, (0.5, 0.5, 0.5), (0.5, 0.5, 0.5))
+        with ops.f32_gemm_mode(self.vae.f32_gemm):
+            return self.vae_encoder.encode(px).to(self.dtype)
 
     def __call__(self, prompt=None, image=None, control_image=None, strength=0.8, num_inference_steps=50, generator=None,
                  guidance_scale=7.5, negative_prompt=None, controlnet_conditioning_scale=0.8, **unused):
         self._need_device()
         if image is None or control_image is None or prompt is None:
             raise ValueError("`prompt`, `image` (the source image) and `control_image` are required")
-        as_u8 = lambda im: np.asarray(im.convert("RGB") if isinstance(im, Image.Image) else im, dtype=np.uint8)   # noqa: E731
-        src, ctrl = as_u8(image), as_u8(control_image)
-        hh, ww = ctrl.shape[:2]
-        if generator is not None and generator.device.type != "cpu":
-            raise NotImplementedError("the reference passes the global CPU generator (run_aug/run_aug.py:324)")
-        shape = (1, self.cfgs["unet"]["in_channels"], hh // 8, ww // 8)
-        e1 = torch.randn(shape, generator=generator, dtype=self.noise_dtype)             # latent_dist.sample(generator)
-        e2 = torch.randn(shape, generator=generator, dtype=self.noise_dtype)             # randn_tensor for add_noise
+        src, ctrl = _rgb_u8(image), _rgb_u8(control_image)
+        e1 = self._noise(ctrl, generator)                                                # latent_dist.sample(generator)
+        e2 = self._noise(ctrl, generator)                                                # randn_tensor for add_noise
         ids = self.tokenizer(str(prompt))
         neg = self.tokenizer(negative_prompt if negative_prompt is not None else "")
-        out = self.generate_batch_img2img(ids, neg, src[None], ctrl[None], e1, e2, num_inference_steps, strength, guidance_scale,
-                                          controlnet_conditioning_scale)
-        nsfw = None if self.last_nsfw is None else [bool(v) for v in self.last_nsfw.cpu().tolist()]
-        return PipelineOutput([Image.fromarray(a) for a in out.cpu().numpy()], nsfw)
+        return self._output(self.generate_batch_img2img(ids, neg, src[None], ctrl[None], e1, e2, num_inference_steps, strength,
+                                                        guidance_scale, controlnet_conditioning_scale))
 
 
 class StableDiffusionImg2ImgPipeline(StableDiffusionControlNetImg2ImgPipeline):
@@ -720,19 +731,8 @@ class StableDiffusionImg2ImgPipeline(StableDiffusionControlNetImg2ImgPipeline):
 
     @classmethod
     def from_pretrained(cls, base_dir, cfgs=SD15):
-        def f(d, *names):
-            for n in names:
-                p = os.path.join(d, n)
-                if os.path.exists(p):
-                    return W.load_safetensors(p)
-            raise FileNotFoundError(f"no safetensors weights in {d}")
-        w = ("diffusion_pytorch_model.safetensors", "diffusion_pytorch_model.fp16.safetensors")
-        sds = dict(unet=f(os.path.join(base_dir, "unet"), *w), vae=f(os.path.join(base_dir, "vae"), *w),
-                   text=f(os.path.join(base_dir, "text_encoder"), "model.safetensors", "model.fp16.safetensors"))
-        sc = os.path.join(base_dir, "safety_checker")
-        if "safety" in cfgs and os.path.isdir(sc):
-            sds["safety"] = f(sc, "model.safetensors", "model.fp16.safetensors")
-        return cls(sds, cfgs, tokenizer=make_tokenizer(os.path.join(base_dir, "tokenizer"), cfgs["text"]["vocab"]))
+        return cls(cls._base_state_dicts(base_dir, cfgs), cfgs,
+                   tokenizer=make_tokenizer(os.path.join(base_dir, "tokenizer"), cfgs["text"]["vocab"]))
 
     def generate_batch_img2img(self, prompt_ids, negative_ids, source_u8, sample_noise, noise, num_inference_steps, strength,
                                guidance_scale=7.5, return_latents=False):
@@ -745,18 +745,12 @@ class StableDiffusionImg2ImgPipeline(StableDiffusionControlNetImg2ImgPipeline):
         self._need_device()
         if image is None or prompt is None:
             raise ValueError("`prompt` and `image` (the source image) are required")
-        src = np.asarray(image.convert("RGB") if isinstance(image, Image.Image) else image, dtype=np.uint8)
-        hh, ww = src.shape[:2]
-        if generator is not None and generator.device.type != "cpu":
-            raise NotImplementedError("the reference passes the global CPU generator (run_aug/run_aug.py:324)")
-        shape = (1, self.cfgs["unet"]["in_channels"], hh // 8, ww // 8)
-        e1 = torch.randn(shape, generator=generator, dtype=self.noise_dtype)             # latent_dist.sample(generator)
-        e2 = torch.randn(shape, generator=generator, dtype=self.noise_dtype)             # randn_tensor for add_noise
+        src = _rgb_u8(image)
+        e1 = self._noise(src, generator)                                                 # latent_dist.sample(generator)
+        e2 = self._noise(src, generator)                                                 # randn_tensor for add_noise
         ids = self.tokenizer(str(prompt))
         neg = self.tokenizer(negative_prompt if negative_prompt is not None else "")
-        out = self.generate_batch_img2img(ids, neg, src[None], e1, e2, num_inference_steps, strength, guidance_scale)
-        nsfw = None if self.last_nsfw is None else [bool(v) for v in self.last_nsfw.cpu().tolist()]
-        return PipelineOutput([Image.fromarray(a) for a in out.cpu().numpy()], nsfw)
+        return self._output(self.generate_batch_img2img(ids, neg, src[None], e1, e2, num_inference_steps, strength, guidance_scale))
 
 
 class StableDiffusionInstructPix2PixPipeline(StableDiffusionImg2ImgPipeline):
@@ -808,20 +802,13 @@ class StableDiffusionInstructPix2PixPipeline(StableDiffusionImg2ImgPipeline):
             raise NotImplementedError("guidance is on for guidance_scale > 1 and image_guidance_scale >= 1; the guidance-free "
                                       "form (one evaluation per step) is not built")
         dev, dt = self.device, self.dtype
-        src = source_u8 if torch.is_tensor(source_u8) else torch.from_numpy(np.array(source_u8))
-        src = ops.h2d(src, dev).contiguous()
+        src = self._device_u8(source_u8)
         b, hh, ww, _ = src.shape
-        mult = 8 << (len(self.cfgs["unet"]["block_out"]) - 1)
-        if hh % mult or ww % mult:
-            raise ValueError(f"image sides must be multiples of {mult} (got {hh}x{ww})")
+        self._check_sides(src, "image")
         h8, w8 = hh // 8, ww // 8
         nl = self.cfgs["vae"]["latent_channels"]
-        if tuple(latents.shape) != (b, nl, h8, w8):
-            raise ValueError(f"latents shape {tuple(latents.shape)} does not match the source image {hh}x{ww}")
-        from . import imageproc
-        px = imageproc.normalize_u8(src, self.vae_encoder.dtype, (0.5, 0.5, 0.5), (0.5, 0.5, 0.5))     # [0,255] -> [-1,1]
-        with ops.f32_gemm_mode(self.vae.f32_gemm):
-            moments = self.vae_encoder.encode(px).to(dt)            # mean in channels 0..3: latent_dist.mode()
+        self._check_latents(latents, nl, src, "source")
+        moments = self._encode_image(src)                           # mean in channels 0..3: latent_dist.mode()
         x = self.latents_to_device(latents)
         # the UNet input of the three groups, built once: the sampling step rewrites channels < 4 only
         x3 = torch.zeros((3, b, h8, w8, 8), device=dev, dtype=dt)
@@ -829,41 +816,27 @@ class StableDiffusionInstructPix2PixPipeline(StableDiffusionImg2ImgPipeline):
         x3[1:, ..., nl:2 * nl] = moments[..., :nl]
         x3 = x3.view(3 * b, h8, w8, 8)
         pos = self._positive_context(prompt_ids)
-        neg = self._negative_context(negative_ids)
-        if neg.shape[0] == 1 and b > 1:
-            neg = neg.expand(b, -1, -1)
-        ctx = torch.cat([neg, neg, pos], 0).contiguous()             # [3B,77,C]: uncond | image | text
+        ctx = self._guidance_context(self._negative_context(negative_ids), pos, branches=3)     # [3B,77,C]: uncond | image | text
         cemb = torch.zeros((1,), device=dev, dtype=dt)               # placeholder: nothing reads it
         self._sample(x3, b, h8 * w8, ctx, cemb, num_inference_steps, guidance_scale, 0.0, branches=3,
                      image_guidance=image_guidance_scale)
-        # (group 0 carries zeros next to the latents: the layout the VAE decoder takes)
-        img = self.vae.decode(ops.scale(x3[:b], 1.0 / self.cfgs["vae"]["scaling_factor"]).to(self.vae.dtype))
-        out, self.last_nsfw = self.run_safety_checker(ops.act_to_u8(img))
-        if return_latents:
-            return out, x3[:b], img
-        return out
+        return self._decode(x3[:b], return_latents)                  # (group 0 carries zeros next to the latents: the VAE's layout)
 
     def __call__(self, prompt=None, image=None, num_inference_steps=100, generator=None, guidance_scale=7.5,
                  image_guidance_scale=1.5, negative_prompt=None, **unused):
         self._need_device()
         if image is None or prompt is None:
             raise ValueError("`prompt` and `image` (the image to edit) are required")
-        src = np.asarray(image.convert("RGB") if isinstance(image, Image.Image) else image, dtype=np.uint8)
-        hh, ww = src.shape[:2]
-        if generator is not None and generator.device.type != "cpu":
-            raise NotImplementedError("the reference passes the global CPU generator (run_aug/run_aug.py:324)")
+        src = _rgb_u8(image)
         # (the noise has the VAE's latent channels, not the UNet's 8 input channels)
-        lat = torch.randn((1, self.cfgs["vae"]["latent_channels"], hh // 8, ww // 8), generator=generator, dtype=self.noise_dtype)
+        lat = self._noise(src, generator, self.cfgs["vae"]["latent_channels"])
         ids = self.tokenizer(str(prompt))
         neg = self.tokenizer(negative_prompt if negative_prompt is not None else "")
-        out = self.generate_batch_ip2p(ids, neg, src[None], lat, num_inference_steps, guidance_scale, image_guidance_scale)
-        nsfw = None if self.last_nsfw is None else [bool(v) for v in self.last_nsfw.cpu().tolist()]
-        return PipelineOutput([Image.fromarray(a) for a in out.cpu().numpy()], nsfw)
+        return self._output(self.generate_batch_ip2p(ids, neg, src[None], lat, num_inference_steps, guidance_scale,
+                                                     image_guidance_scale))
 
 
 class BlipDiffusionControlNetPipeline(StableDiffusionControlNetPipeline):
-    SUPPORTS_FP16 = False
-    CFG_PREFIX = False                # (the multimodal context keeps today's evaluation)
     """Drop-in for diffusers' `BlipDiffusionControlNetPipeline` as the reference builds and calls it for every dataset
     but planes (run_aug/run_aug.py:181, :211, :243-250, :262-265, :521; SURVEY 8a a8):
 
@@ -877,6 +850,8 @@ class BlipDiffusionControlNetPipeline(StableDiffusionControlNetPipeline):
     "a {category} {prompt}" and repeated prompt_strength * prompt_reps (= 20) times, tokenised to 77 - 16 tokens,
     and the 16 subject tokens of the Q-Former front-end (saspa_aug_amd.blip.Blip2QFormer) are spliced into the
     CLIP token embeddings at position 2.  UNet / ControlNet / VAE are the SD-1.5 architectures (shared kernels)."""
+    SUPPORTS_FP16 = False
+    CFG_PREFIX = False                # (the multimodal context keeps today's evaluation)
 
     def __init__(self, state_dicts, cfgs=BLIP_DIFFUSION, tokenizer=None, scheduler=None, qformer_tokenizer=None):
         super().__init__(state_dicts, cfgs, tokenizer, scheduler or PNDMScheduler())
@@ -890,15 +865,9 @@ class BlipDiffusionControlNetPipeline(StableDiffusionControlNetPipeline):
     @classmethod
     def from_pretrained(cls, repo_dir, cfgs=BLIP_DIFFUSION):
         """Local copy of Salesforce/blipdiffusion-controlnet: unet/ vae/ text_encoder/ controlnet/ qformer/ tokenizer/."""
-        def f(sub, *names):
-            for n in names:
-                p = os.path.join(repo_dir, sub, n)
-                if os.path.exists(p):
-                    return W.load_safetensors(p)
-            raise FileNotFoundError(f"no safetensors weights in {os.path.join(repo_dir, sub)}")
-        names = ("diffusion_pytorch_model.safetensors", "diffusion_pytorch_model.fp16.safetensors", "model.safetensors")
-        sds = dict(unet=f("unet", *names), vae=f("vae", *names), text=f("text_encoder", *names),
-                   controlnet=f("controlnet", *names), qformer=f("qformer", *names))
+        names = _WEIGHTS + ("model.safetensors",)
+        sds = {k: _first_safetensors(os.path.join(repo_dir, sub), names)
+               for k, sub in (("unet", "unet"), ("vae", "vae"), ("text", "text_encoder"), ("controlnet", "controlnet"), ("qformer", "qformer"))}
         return cls(sds, cfgs, tokenizer=make_tokenizer(os.path.join(repo_dir, "tokenizer"), cfgs["text"]["vocab"]),
                    qformer_tokenizer=make_bert_tokenizer(os.path.join(repo_dir, "qformer"), cfgs["qformer"]["vocab"]))
 
@@ -922,8 +891,7 @@ class BlipDiffusionControlNetPipeline(StableDiffusionControlNetPipeline):
         qc = self.cfgs["qformer"]
         def one(im):
             if torch.is_tensor(im) and im.is_cuda:          # device u8 [H,W,3] (run_aug): Pillow-exact bicubic on the device
-                from . import imageproc
-                x = imageproc.resize_u8(im[None].contiguous(), qc["image_size"], qc["image_size"], filt="bicubic")
+                x =imageproc.resize_u8(im[None].contiguous(), qc["image_size"], qc["image_size"], filt="bicubic")
                 return imageproc.normalize_u8(x, torch.float32, BLIP_IMAGE_MEAN, BLIP_IMAGE_STD)[0, :, :, :3].permute(2, 0, 1)
             return preprocess_reference(im, qc, BLIP_IMAGE_MEAN, BLIP_IMAGE_STD).to(self.device)
         px = torch.stack([one(im) for im in reference_images])
@@ -952,21 +920,15 @@ class BlipDiffusionControlNetPipeline(StableDiffusionControlNetPipeline):
         if ctrl.size != (width, height):        # prepare_control_image resizes the control image to (width, height)
             ctrl = ctrl.resize((width, height), resample=Image.LANCZOS)
         ctrl = np.asarray(ctrl, dtype=np.uint8)
-        if generator is not None and generator.device.type != "cpu":
-            raise NotImplementedError("the reference passes the global CPU generator (run_aug/run_aug.py:324)")
-        lat = torch.randn((1, self.cfgs["unet"]["in_channels"], height // 8, width // 8), generator=generator, dtype=self.noise_dtype)
+        lat = self._noise(ctrl, generator)
         text = self.build_prompt(prompt, target_subject_category, prompt_strength, prompt_reps)
         ids = self.tokenizer(text, max_len=self.prompt_token_count())
         neg = self.tokenizer(neg_prompt or "")
         q = self.get_query_embeddings([reference_image], [source_subject_category])
-        out = self.generate_batch(ids, neg, ctrl[None], lat, num_inference_steps, guidance_scale, 1.0, query_embeds=q)
-        arr = out.cpu().numpy()
-        return PipelineOutput([Image.fromarray(a) for a in arr], None)
+        return self._output(self.generate_batch(ids, neg, ctrl[None], lat, num_inference_steps, guidance_scale, 1.0, query_embeds=q))
 
 
 class StableDiffusionXLControlNetPipeline(StableDiffusionControlNetPipeline):
-    SUPPORTS_FP16 = False
-    CFG_PREFIX = False                # (with guidance the added conditioning differs between the halves)
     """Drop-in for diffusers' `StableDiffusionXLControlNetPipeline` as the reference builds and calls it for
     `BASE_MODEL = "sd_xl-turbo"` (its choice for CUB; run_aug/run_aug.py:189-201, :223-228, :564-571; SURVEY 8a a9):
 
@@ -982,6 +944,8 @@ class StableDiffusionXLControlNetPipeline(StableDiffusionControlNetPipeline):
     embedding of the `text_time` conditioning together with add_time_ids = (H, W, 0, 0, H, W); three-level UNet /
     ControlNet with transformer depths (2, 10) and linear projections; VAE scaling factor 0.13025, decoded in fp32
     after `upcast_vae()` (the exact-fp32 MFMA kernels) even when the denoiser runs in bf16."""
+    SUPPORTS_FP16 = False
+    CFG_PREFIX = False                # (with guidance the added conditioning differs between the halves)
 
     def __init__(self, state_dicts, cfgs=SDXL_TURBO, tokenizer=None, scheduler=None, tokenizer_2=None):
         super().__init__(state_dicts, cfgs, tokenizer, scheduler or DDIMScheduler(**SDXL_TURBO_SCHEDULER_CONFIG))
@@ -999,15 +963,8 @@ class StableDiffusionXLControlNetPipeline(StableDiffusionControlNetPipeline):
     def from_pretrained(cls, base_dir, controlnet_dir, vae_dir=None, cfgs=SDXL_TURBO):
         """Local copies of stabilityai/sdxl-turbo (unet/ text_encoder/ text_encoder_2/ tokenizer/ tokenizer_2/ vae/),
         diffusers/controlnet-canny-sdxl-1.0 and (optionally) madebyollin/sdxl-vae-fp16-fix."""
-        names = ("diffusion_pytorch_model.safetensors", "diffusion_pytorch_model.fp16.safetensors", "model.safetensors",
-                 "model.fp16.safetensors")
-
         def f(d):
-            for n in names:
-                p = os.path.join(d, n)
-                if os.path.exists(p):
-                    return W.load_safetensors(p)
-            raise FileNotFoundError(f"no safetensors weights in {d}")
+            return _first_safetensors(d, _WEIGHTS + _TEXT_WEIGHTS)
         sds = dict(unet=f(os.path.join(base_dir, "unet")), vae=f(vae_dir or os.path.join(base_dir, "vae")),
                    text=f(os.path.join(base_dir, "text_encoder")), text2=f(os.path.join(base_dir, "text_encoder_2")),
                    controlnet=f(controlnet_dir))
@@ -1066,19 +1023,10 @@ class StableDiffusionXLControlNetPipeline(StableDiffusionControlNetPipeline):
         of the first tokenizer's ids."""
         self._need_device()
         cfg = guidance_scale > 1.0                         # diffusers: do_classifier_free_guidance = guidance_scale > 1
-        dev, dt = self.device, self.dtype
-        # (np.array: a writable copy -- arrays that come out of PIL are read-only and torch warns about wrapping those)
-        ctrl = torch.from_numpy(np.array(control_u8)) if not torch.is_tensor(control_u8) else control_u8
-        ctrl = ops.h2d(ctrl, dev).contiguous()
+        ctrl = self._device_u8(control_u8)
         b, hh, ww, _ = ctrl.shape
-        mult = 8 << (len(self.cfgs["unet"]["block_out"]) - 1)
-        if hh % mult or ww % mult:
-            # the UNet halves the latent (H/8 x W/8) once per level below the first and doubles it back exactly; the
-            # reference only ever feeds multiples of 64 (all_utils/utils.py:65-77 rounds both sides to 64)
-            raise ValueError(f"control image sides must be multiples of {mult} (got {hh}x{ww})")
-        want = (b, hh // 8, ww // 8, 8) if latents_on_device else (b, self.cfgs["unet"]["in_channels"], hh // 8, ww // 8)
-        if tuple(latents.shape) != want:
-            raise ValueError(f"latents shape {tuple(latents.shape)} does not match the control image {hh}x{ww}")
+        self._check_sides(ctrl, "control image")
+        self._check_latents(latents, self.cfgs["unet"]["in_channels"], ctrl, "control", latents_on_device)
         ids1 = np.asarray(prompt_ids.cpu() if torch.is_tensor(prompt_ids) else prompt_ids)
         ids2 = self.pad_ids_2(ids1) if prompt_ids_2 is None else prompt_ids_2
         ctx, pooled = self.encode_prompts_xl(ids1, ids2)
@@ -1091,81 +1039,35 @@ class StableDiffusionXLControlNetPipeline(StableDiffusionControlNetPipeline):
                 n1 = np.asarray(negative_ids.cpu() if torch.is_tensor(negative_ids) else negative_ids)
                 n2 = self.pad_ids_2(n1) if negative_ids_2 is None else negative_ids_2
                 nctx, npooled = self.encode_prompts_xl(n1, n2)
-                if nctx.shape[0] == 1 and b > 1:
-                    nctx, npooled = nctx.expand(b, -1, -1), npooled.expand(b, -1)
-            ctx = torch.cat([nctx, ctx], 0).contiguous()
-            pooled = torch.cat([npooled, pooled], 0).contiguous()
-        nb = 2 * b if cfg else b
-        time_ids = [[hh, ww, 0, 0, hh, ww]] * nb           # original_size + crops_coords_top_left + target_size
-        cond = ops.u8_to_act(ctrl, dt)
-        cemb = self.controlnet.cond_embedding(cond)
-        x = (latents if latents_on_device else self.latents_to_device(latents)).contiguous()
+            ctx = self._guidance_context(nctx, ctx)
+            pooled = torch.cat([npooled.expand(b, -1), pooled], 0).contiguous()
+        time_ids = [[hh, ww, 0, 0, hh, ww]] * ctx.shape[0]       # original_size + crops_coords_top_left + target_size
+        cemb = self.controlnet.cond_embedding(ops.u8_to_act(ctrl, self.dtype))
+        x = latents if latents_on_device else self.latents_to_device(latents)
         if cfg:
             x = torch.cat([x, x], 0).contiguous()
             cemb = torch.cat([cemb, cemb], 0)
-        sch = self.scheduler
-        unipc = isinstance(sch, UniPCMultistepScheduler)        # run_aug/run_aug.py:223-226 with sampler = "unipcmultistep"
-        if unipc:
-            plan = sch.plan(num_inference_steps)
-            ts, rows = [t for t, _ in plan], [r for _, r in plan]
-        else:
-            ts, rows = sch.set_timesteps(num_inference_steps), None
-        if graphs_enabled():
-            g = self._step_graph(x, cemb, ctx, num_inference_steps, cfg, float(guidance_scale) if cfg else 0.0,
-                                 controlnet_conditioning_scale, ts)
-            x = g.run_on(x, cemb, ctx, ts, (pooled, time_ids), plan=rows).clone()
-        else:
-            for net in (self.unet, self.controlnet):
-                net.prepare_context(ctx)
-                net.prepare_timesteps(ts, (pooled, time_ids))
-            eps = torch.zeros_like(x)
-            nc, hw = self.cfgs["unet"]["out_channels"], (hh // 8) * (ww // 8)
-            state = torch.zeros((3, b) + tuple(x.shape[1:]), device=x.device, dtype=x.dtype) if unipc else None
-            for i, t in enumerate(ts):
-                # the same launches, with the same dispatch decisions, as the two-branch graph step (_StepGraph._step): the paired
-                # encoders carry the shared-chip hint (ops.twin_branch) -- except under a launch recorder (every launch alone)
-                with ops.twin_branch(fork_enabled() and ops._RECORDER is None):
-                    cmid, cfeats = self.controlnet.encode(x, i, conv_in_residual=cemb)
-                    mid, skips = self.unet.encode(x, i)
-                skips2, mid2 = self.controlnet.zero_convs(cmid, cfeats, controlnet_conditioning_scale, skips, mid)
-                self.unet.decode(mid2, skips2, i, out=eps)
-                if unipc and cfg:
-                    ops.cfg_unipc_step(eps, x, state, b, hw, nc, guidance_scale, row=rows[i])
-                elif unipc:
-                    ops.unipc_step(eps, x, state, b, hw, nc, row=rows[i])
-                elif cfg:
-                    ops.cfg_ddim_step(eps, x, b, hw, nc, guidance_scale, *sch.step_coefficients(t))
-                else:
-                    ops.ddim_step(eps, x, b, hw, nc, *sch.step_coefficients(t))
-        x = x[:b].contiguous() if cfg else x
-        z = ops.scale(x, 1.0 / self.cfgs["vae"]["scaling_factor"])
-        if self.vae.dtype != z.dtype:
-            z = z.to(self.vae.dtype)                      # upcast_vae(): latents follow the VAE dtype
-        img = self.vae.decode(z)
-        out = ops.act_to_u8(img)
-        if return_latents:
-            return out, x, img
-        return out
+        elif latents_on_device:
+            x = x.clone(memory_format=torch.contiguous_format)     # (the loop runs in place: not on the caller's tensor)
+        # (DDIM, or UniPC: run_aug/run_aug.py:223-226 with sampler = "unipcmultistep")
+        self._sample(x, b, (hh // 8) * (ww // 8), ctx, cemb, num_inference_steps, guidance_scale, controlnet_conditioning_scale,
+                     cfg=cfg, added=(pooled, time_ids))
+        return self._decode(x[:b], return_latents)
 
     def __call__(self, prompt=None, image=None, num_inference_steps=50, generator=None, guidance_scale=5.0,
                  negative_prompt=None, controlnet_conditioning_scale=1.0, **unused):
         self._need_device()
         if image is None or prompt is None:
             raise ValueError("`prompt` and `image` (the control image) are required")
-        ctrl = np.asarray(image.convert("RGB") if isinstance(image, Image.Image) else image, dtype=np.uint8)
+        ctrl = _rgb_u8(image)
         if ctrl.ndim != 3 or ctrl.shape[2] != 3:
             raise ValueError("control image must be RGB")
-        hh, ww = ctrl.shape[:2]
-        if generator is not None and generator.device.type != "cpu":
-            raise NotImplementedError("the reference passes the global CPU generator (run_aug/run_aug.py:324)")
-        lat = torch.randn((1, self.cfgs["unet"]["in_channels"], hh // 8, ww // 8), generator=generator, dtype=self.noise_dtype)
+        lat = self._noise(ctrl, generator)
         ids1 = self.tokenizer(str(prompt))
         ids2 = self.pad_ids_2(self.tokenizer_2(str(prompt)))
         n1 = n2 = None
         if negative_prompt is not None and guidance_scale > 1.0:
             n1 = self.tokenizer(str(negative_prompt))
             n2 = self.pad_ids_2(self.tokenizer_2(str(negative_prompt)))
-        out = self.generate_batch(ids1, n1, ctrl[None], lat, num_inference_steps, guidance_scale,
-                                  controlnet_conditioning_scale, prompt_ids_2=ids2, negative_ids_2=n2)
-        arr = out.cpu().numpy()
-        return PipelineOutput([Image.fromarray(a) for a in arr], None)
+        return self._output(self.generate_batch(ids1, n1, ctrl[None], lat, num_inference_steps, guidance_scale,
+                                                controlnet_conditioning_scale, prompt_ids_2=ids2, negative_ids_2=n2))

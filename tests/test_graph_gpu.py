@@ -53,6 +53,20 @@ def test_graph_replay_equals_eager_sd15(dev, dtype, monkeypatch):
         ops.set_recorder(None)
 
 
+def test_single_stream_capture_equals_eager(dev, monkeypatch):
+    """SASPA_FORK=0 (the supervised launcher's fallback): the step captured on one stream, without the shared-chip hint, reproduces
+    the eager loop of the same setting bit for bit."""
+    cfgs = CFG.tiny()
+    pipe = StableDiffusionControlNetPipeline(W.synth_family(cfgs, seed=3), cfgs).to(dev, torch.bfloat16)
+    monkeypatch.setenv("SASPA_FORK", "0")
+    monkeypatch.setenv("SASPA_GRAPH", "0")
+    eager = pipe.generate_batch(*_inputs(cfgs, 2, 64, 64, 51), 3, return_latents=True)[1].clone()
+    monkeypatch.setenv("SASPA_GRAPH", "1")
+    got = pipe.generate_batch(*_inputs(cfgs, 2, 64, 64, 51), 3, return_latents=True)[1]
+    assert all(g.graph is not None and g.side is None for g in pipe._graphs.values()) and len(pipe._graphs) == 1
+    assert torch.equal(got, eager)
+
+
 def test_replay_throttle_and_clock_probe(dev, monkeypatch):
     """Round 6 host side: (a) the replay loop with at most 3 step-graph launches outstanding behind sleeping waits
     (SASPA_REPLAY_DEPTH, the default) produces the same latents as the unthrottled loop; (b) `saspa_clock_probe` measures a

@@ -11,7 +11,7 @@ from PIL import Image
 
 from . import ops
 from . import weights as W
-from .models import _Packed, _f32, attention_core, project_vt
+from .models import _Packed, _f32, _norm, attention_core, encoder_layer, project_vt
 
 
 def preprocess_reference(img, cfg, mean, std):
@@ -41,18 +41,7 @@ class Blip2QFormer:
         pk.norm(v + ".pre_layernorm")
         for i in range(cfg["vis_layers"]):
             lp = f"{v}.encoder.layers.{i}"
-            a = lp + ".self_attn"
-            wqkv, bqkv = sd[a + ".qkv.weight"], sd[a + ".qkv.bias"]
-            p[a + ".qk.w"] = wqkv[:2 * vw].contiguous().to(dev, dtype)
-            p[a + ".qk.b"] = _f32(bqkv[:2 * vw], dev)
-            p[a + ".v.w"] = wqkv[2 * vw:].contiguous().to(dev, dtype)
-            wo = sd[a + ".projection.weight"]
-            p[a + ".o.w"] = wo.contiguous().to(dev, dtype)
-            p[a + ".o.b"] = _f32(sd[a + ".projection.bias"] + wo @ bqkv[2 * vw:], dev)   # softmax rows sum to 1
-            pk.norm(lp + ".layer_norm1")
-            pk.norm(lp + ".layer_norm2")
-            pk.linear(lp + ".mlp.fc1")
-            pk.linear(lp + ".mlp.fc2")
+            pk.encoder_layer(lp, lp + ".self_attn", "projection", qkv="qkv")
         pk.norm(v + ".post_layernorm")
         p["query_tokens"] = sd["query_tokens"].to(dev, dtype).contiguous()
         p["word"] = sd["embeddings.word_embeddings.weight"].to(dev, dtype).contiguous()
@@ -102,22 +91,13 @@ class Blip2QFormer:
         pos = p["patch_pos"][None].expand(b, -1, -1).reshape(b * g * g, vw).contiguous()
         tok = ops.linear(patches.contiguous(), p["patch.w"], None, residual=pos).view(b, g * g, vw)
         x = torch.cat([p["cls_pos"].expand(b, -1, -1), tok], 1).contiguous()
-        n = x.shape[1]
         v = "visual_encoder"
         eps = cfg["vis_eps"]
-        x = ops.layernorm(x, p[v + ".pre_layernorm.g"], p[v + ".pre_layernorm.b"], eps)
+        x = ops.layernorm(x, *_norm(p, v + ".pre_layernorm", eps))
         for i in range(cfg["vis_layers"]):
             lp = f"{v}.encoder.layers.{i}"
-            a = lp + ".self_attn"
-            h = ops.layernorm(x, p[lp + ".layer_norm1.g"], p[lp + ".layer_norm1.b"], eps)
-            qk = ops.linear(h, p[a + ".qk.w"], p[a + ".qk.b"])
-            vt = project_vt(h, p[a + ".v.w"], n)
-            o = attention_core(qk[:, :, :vw], qk[:, :, vw:], vt, cfg["vis_heads"], n, n)
-            x = ops.linear(o, p[a + ".o.w"], p[a + ".o.b"], residual=x)
-            h = ops.layernorm(x, p[lp + ".layer_norm2.g"], p[lp + ".layer_norm2.b"], eps)
-            h = ops.activation(ops.linear(h, p[lp + ".mlp.fc1.w"], p[lp + ".mlp.fc1.b"]), ops.ACT_QUICK_GELU)
-            x = ops.linear(h, p[lp + ".mlp.fc2.w"], p[lp + ".mlp.fc2.b"], residual=x)
-        return ops.layernorm(x, p[v + ".post_layernorm.g"], p[v + ".post_layernorm.b"], eps)
+            x = encoder_layer(p, lp, lp + ".self_attn", x, cfg["vis_heads"], ops.ACT_QUICK_GELU, eps=eps)
+        return ops.layernorm(x, *_norm(p, v + ".post_layernorm", eps))
 
     # ---- Q-Former ----------------------------------------------------------------------
     def _attention(self, pfx, x, kv, heads):

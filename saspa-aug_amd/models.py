@@ -27,6 +27,7 @@ from . import ops
 from . import weights as W
 
 SILU = ops.ACT_SILU
+ATTN_LOG2E = 1.4426950408889634
 
 
 def _is_half(dtype):
@@ -36,6 +37,22 @@ def _is_half(dtype):
 
 def _f32(t, dev):
     return t.detach().to(dev, torch.float32).contiguous()
+
+
+def _wb(p, name):
+    """(weight, bias) of a packed conv / linear: the operand pair of ops.conv / ops.linear."""
+    return p[name + ".w"], p[name + ".b"]
+
+
+def _norm(p, name, *rest):
+    """(gamma, beta) + rest of a packed norm: with eps the LayerNorm triple of the fused launches (ops.linear(ln=), ops.xattn_block,
+    ops.ff_block), with (groups, eps, act) the operands of ops.groupnorm / ops.conv(fuse_gn=)."""
+    return (p[name + ".g"], p[name + ".b"]) + rest
+
+
+def _geglu8(p, t):
+    """(e4m3 weight, its scales, bias) of block t's GEGLU projection: ops.linear_fp8's operands behind the activations."""
+    return p[t + ".ff.net.0.proj.w8"], p[t + ".ff.net.0.proj.sw"], p[t + ".ff.net.0.proj.b8"]
 
 
 class _Packed:
@@ -60,9 +77,12 @@ class _Packed:
         chunk = W.chunk_major_ok(kh, kw, c0p, c1p, self.dtype)
         if chunk:       # the taps of one channel chunk become consecutive K-tiles (input rows re-read from L2)
             pk = W.to_chunk_major(pk, kh * kw, self.dtype)
-        t = pk.to(self.dev, self.dtype)
+        self._put_conv(name, pk, chunk, c0p + c1p)
+
+    def _put_conv(self, name, pk, chunk, cin):
+        t = pk.to(self.dev, self.dtype)             # (conv_up2x: the one rounding of the summed taps)
         t.saspa_korder = 1 if chunk else 0          # read by ops.conv -> SaspaGemmParams.korder
-        t.saspa_cin = c0p + c1p                     # padded input channels per tap (VAEDecoder._presplit)
+        t.saspa_cin = cin                           # padded input channels per tap (VAEDecoder._presplit)
         self.p[name + ".w"] = t
         if name + ".bias" in self.sd:
             self.p[name + ".b"] = _f32(self.sd[name + ".bias"], self.dev)
@@ -79,12 +99,7 @@ class _Packed:
         chunk = W.chunk_major_ok(2, 2, c0p, 0, self.dtype)
         if chunk:
             pk = torch.stack([W.to_chunk_major(pk[i], 4, self.dtype) for i in range(4)])
-        t = pk.to(self.dev, self.dtype)             # the one rounding of the summed taps
-        t.saspa_korder = 1 if chunk else 0
-        t.saspa_cin = c0p
-        self.p[name + ".w"] = t
-        if name + ".bias" in self.sd:
-            self.p[name + ".b"] = _f32(self.sd[name + ".bias"], self.dev)
+        self._put_conv(name, pk, chunk, c0p)
 
     def linear(self, name, dtype=None):
         self.p[name + ".w"] = W.pack_linear(self.sd[name + ".weight"]).to(self.dev, dtype or self.dtype)
@@ -94,6 +109,15 @@ class _Packed:
     def norm(self, name):
         self.p[name + ".g"] = _f32(self.sd[name + ".weight"], self.dev)
         self.p[name + ".b"] = _f32(self.sd[name + ".bias"], self.dev)
+
+    def resnet(self, pfx, split=None):
+        """norm1, conv1, norm2, conv2 and the 1x1 shortcut where the checkpoint has one (split: over a skip concat)."""
+        self.norm(pfx + ".norm1")
+        self.conv(pfx + ".conv1")
+        self.norm(pfx + ".norm2")
+        self.conv(pfx + ".conv2")
+        if pfx + ".conv_shortcut.weight" in self.sd:
+            self.conv(pfx + ".conv_shortcut", split)
 
     def attn(self, name, self_attn, has_bias=False, qscale=None):
         """Fused [to_q; to_k] for self-attention, to_v kept separate (consumed as the A
@@ -121,6 +145,25 @@ class _Packed:
             bo = bo + wo @ sd[name + ".to_v.bias"]
         self.p[name + ".o.w"] = wo.contiguous().to(self.dev, self.dtype)
         self.p[name + ".o.b"] = _f32(bo, self.dev)
+
+    def encoder_layer(self, lp, a, out, qkv=None):
+        """A pre-LN encoder layer (CLIP text / vision towers): `lp`.layer_norm1 / 2 and .mlp.fc1 / fc2, attention under `a` with
+        the output projection `a`.`out`; q / k / v as `a`.q_proj / k_proj / v_proj or fused as `a`.`qkv`.  Packed like attn():
+        fused [q; k], v on its own (the A operand of the transposed projection), the v bias folded into the out bias."""
+        sd, p, dev = self.sd, self.p, self.dev
+        names = [f"{a}.{qkv}"] if qkv else [f"{a}.{n}_proj" for n in "qkv"]
+        w, b = (torch.cat([sd[n + s] for n in names], 0) for s in (".weight", ".bias"))
+        c = w.shape[0] // 3
+        p[a + ".qk.w"] = w[:2 * c].contiguous().to(dev, self.dtype)
+        p[a + ".qk.b"] = _f32(b[:2 * c], dev)
+        p[a + ".v.w"] = w[2 * c:].contiguous().to(dev, self.dtype)
+        wo = sd[f"{a}.{out}.weight"]
+        p[a + ".o.w"] = wo.contiguous().to(dev, self.dtype)
+        p[a + ".o.b"] = _f32(sd[f"{a}.{out}.bias"] + wo @ b[2 * c:], dev)         # softmax rows sum to 1
+        self.norm(lp + ".layer_norm1")
+        self.norm(lp + ".layer_norm2")
+        self.linear(lp + ".mlp.fc1")
+        self.linear(lp + ".mlp.fc2")
 
 
 # ------------------------------------------------------------------------------------------
@@ -165,12 +208,8 @@ def project_vt(x, wv, nk):
     return vt
 
 
-ATTN_LOG2E = 1.4426950408889634
-
-
 def rowmajor_v_enabled():
     """SASPA_ATTN_VROW=0: self-attention goes back to the separate transposed value projection (A/B knob)."""
-    import os
     return os.environ.get("SASPA_ATTN_VROW", "1") != "0"
 
 
@@ -197,6 +236,20 @@ def attention_core(q, k, vt, heads, nq, nk, causal=False, prescaled=False, v_row
     ops.gemm_batched(scores, lds, (heads * nq * lds, nq * lds), vt, vt.stride(1), (vt.stride(0), d * vt.stride(1)), out, c,
                      (nq * c, d), nq, d, lds, b, heads)
     return out
+
+
+def encoder_layer(p, lp, a, x, heads, act, eps=1e-5, causal=False):
+    """One layer packed by _Packed.encoder_layer on x [B,n,C]: LN, fused q | k projection, V^T projection, attention, out
+    projection + residual, LN, fc1, activation, fc2 + residual."""
+    n, c = x.shape[1], x.shape[2]
+    h = ops.layernorm(x, *_norm(p, lp + ".layer_norm1", eps))
+    qk = ops.linear(h, *_wb(p, a + ".qk"))
+    vt = project_vt(h, p[a + ".v.w"], n)
+    o = attention_core(qk[:, :, :c], qk[:, :, c:], vt, heads, n, n, causal=causal)
+    x = ops.linear(o, *_wb(p, a + ".o"), residual=x)
+    h = ops.layernorm(x, *_norm(p, lp + ".layer_norm2", eps))
+    h = ops.activation(ops.linear(h, *_wb(p, lp + ".mlp.fc1")), act)
+    return ops.linear(h, *_wb(p, lp + ".mlp.fc2"), residual=x)
 
 
 # ------------------------------------------------------------------------------------------
@@ -247,22 +300,20 @@ class _Net:
         # GroupNorm statistics out of the producers' epilogues (ops.conv(..., gn_unit=...)): every GroupNorm of the network
         # has groups of a multiple of block_out[0] / groups channels (10 for SD-1.5 / SDXL), also across a skip concat
         self.gn_unit = cfg["block_out"][0] // cfg["groups"] if _is_half(dtype) else None
+        self._pack_encoder()
+        self._pack_rest()
+        self.pk.sd = None                 # drop the fp32 host copy reference
 
     # ---- packing helpers ----
     def _pack_resnet(self, pfx, split=None):
         pk = self.pk
-        pk.norm(pfx + ".norm1")
-        pk.conv(pfx + ".conv1")
-        pk.norm(pfx + ".norm2")
-        pk.conv(pfx + ".conv2")
+        pk.resnet(pfx, split)
         if self.fp8_conv:
             for name in (pfx + ".conv1", pfx + ".conv2"):
                 w = pk.sd[name + ".weight"]
                 if ops.conv3x3_mxfp8_eligible(w.shape[1], w.shape[0]):
                     w8, sw = W.pack_conv_mxfp8(w)
                     self.p[name + ".w8"], self.p[name + ".sw"] = w8.to(self.dev), sw.to(self.dev)
-        if pfx + ".conv_shortcut.weight" in pk.sd:
-            pk.conv(pfx + ".conv_shortcut", split)
         if pfx + ".time_emb_proj.weight" in pk.sd:
             pk.linear(pfx + ".time_emb_proj", torch.float32)
             self.resnets_with_temb.append(pfx)
@@ -341,13 +392,21 @@ class _Net:
             pk.linear("add_embedding.linear_1", torch.float32)
             pk.linear("add_embedding.linear_2", torch.float32)
         n_lvl = len(cfg["block_out"])
+        # the down path in execution order, walked by this loop and by encode(): ("layer", resnet, transformer or None, level) and
+        # ("down", stride-2 conv, None, level); every entry leaves one skip behind conv_in's
+        self.down_layout = []
         for i in range(n_lvl):
-            for j in range(cfg["layers"]):
-                self._pack_resnet(f"down_blocks.{i}.resnets.{j}")
-                if cfg["attn"][i]:
-                    self._pack_transformer(f"down_blocks.{i}.attentions.{j}", i)
+            self.down_layout += [("layer", f"down_blocks.{i}.resnets.{j}", f"down_blocks.{i}.attentions.{j}" if cfg["attn"][i] else None, i)
+                                 for j in range(cfg["layers"])]
             if i != n_lvl - 1:
-                pk.conv(f"down_blocks.{i}.downsamplers.0.conv")
+                self.down_layout.append(("down", f"down_blocks.{i}.downsamplers.0.conv", None, i))
+        for kind, name, attn, lvl in self.down_layout:
+            if kind == "down":
+                pk.conv(name)
+                continue
+            self._pack_resnet(name)
+            if attn:
+                self._pack_transformer(attn, lvl)
         self._pack_resnet("mid_block.resnets.0")
         self._pack_transformer("mid_block.attentions.0", n_lvl - 1)
         self._pack_resnet("mid_block.resnets.1")
@@ -370,8 +429,8 @@ class _Net:
         the per-sample text_time embedding, so the tables become [steps, B, Cout] (row vector per batch sample)."""
         sinus = ops.h2d(self._sinusoid(timesteps, self.cfg["block_out"][0]), self.dev)
         p = self.p
-        e = ops.linear(sinus, p["time_embedding.linear_1.w"], p["time_embedding.linear_1.b"], act=SILU)
-        e = ops.linear(e, p["time_embedding.linear_2.w"], p["time_embedding.linear_2.b"])       # [S, temb]
+        e = ops.linear(sinus, *_wb(p, "time_embedding.linear_1"), act=SILU)
+        e = ops.linear(e, *_wb(p, "time_embedding.linear_2"))       # [S, temb]
         if "add_embed" in self.cfg:
             if added is None:
                 raise ValueError("this network needs the SDXL added conditioning (text_embeds, time_ids)")
@@ -380,12 +439,12 @@ class _Net:
             b = text_embeds.shape[0]
             te = ops.h2d(self._sinusoid(torch.as_tensor(time_ids, dtype=torch.float32), ae["time_dim"]).reshape(b, -1), self.dev)
             a_in = torch.cat([text_embeds.to(torch.float32), te], -1).contiguous()
-            a = ops.linear(a_in, p["add_embedding.linear_1.w"], p["add_embedding.linear_1.b"], act=SILU)
+            a = ops.linear(a_in, *_wb(p, "add_embedding.linear_1"), act=SILU)
             # emb[s][b] = time_emb[s] + aug[b]: the aug row block is the GEMM's residual, once per step
             s_n = e.shape[0]
             e_rep = e[:, None, :].expand(s_n, b, e.shape[1]).reshape(s_n * b, -1).contiguous()
             a_rep = a[None].expand(s_n, b, a.shape[1]).reshape(s_n * b, -1).contiguous()
-            e = ops.linear(a_rep, p["add_embedding.linear_2.w"], p["add_embedding.linear_2.b"], residual=e_rep)
+            e = ops.linear(a_rep, *_wb(p, "add_embedding.linear_2"), residual=e_rep)
             shape = (s_n, b, -1)
         else:
             shape = (e.shape[0], -1)
@@ -400,10 +459,9 @@ class _Net:
                 c = p[pfx + ".time_emb_proj.w"].shape[0]
                 self.temb_off[pfx] = (off, c)
                 off += c
+                del p[pfx + ".time_emb_proj.w"], p[pfx + ".time_emb_proj.b"]        # the per-resnet copies are no longer needed
             self.temb_total = off
-            for pfx in self.resnets_with_temb:                  # the per-resnet copies are no longer needed
-                del p[pfx + ".time_emb_proj.w"], p[pfx + ".time_emb_proj.b"]
-        tab = ops.linear(se, p["temb_cat.w"], p["temb_cat.b"])
+        tab = ops.linear(se, *_wb(p, "temb_cat"))
         self.temb_all = tab[:, :self.temb_total].contiguous().view(*shape[:-1], self.temb_total)
         self.temb_tables = {pfx: self.temb_all[..., o:o + c] for pfx, (o, c) in self.temb_off.items()}
 
@@ -434,38 +492,37 @@ class _Net:
         rv = None
         if pfx in self.temb_tables:
             rv = self.temb_cur_views[pfx] if step is None else self.temb_tables[pfx][step]
-        # (round 6: the halo-tiled conv with the GroupNorm applied in LDS -- saspa_conv3x3_halo, SASPA_HALO=1 in round 5 -- is no longer
-        # reachable from the pipeline: parity-green, -1.4 % end to end, both arms in profiles/EXPERIMENTS.md; the kernel stays a tested
-        # library entry point)
+        # (not reachable from here since round 6: the halo-tiled conv with the GroupNorm applied in LDS, saspa_conv3x3_halo -- parity-green,
+        # -1.4 % end to end, profiles/EXPERIMENTS.md; the kernel stays a tested library entry point)
         m = x.shape[0] * x.shape[1] * x.shape[2]
         c1 = x.shape[3] + (0 if x2 is None else x2.shape[3])
         mx1 = (pfx + ".conv1.w8") in p and mxfp8_conv_takes(m, p[pfx + ".conv1.w8"].shape[0], c1)
         mx2 = (pfx + ".conv2.w8") in p and mxfp8_conv_takes(m, p[pfx + ".conv2.w8"].shape[0], p[pfx + ".conv2.w8"].shape[0])
         if mx1:
             # fp8 conv path: norm1 + SiLU quantised to MX-fp8 (one exponent per pixel and 32 channels), the conv on block-scaled tiles
-            q, qs = ops.groupnorm_quant_mxfp8(x, p[pfx + ".norm1.g"], p[pfx + ".norm1.b"], g, eps, SILU, x2=x2)
+            q, qs = ops.groupnorm_quant_mxfp8(x, *_norm(p, pfx + ".norm1", g, eps, SILU), x2=x2)
             h = ops.conv3x3_mxfp8(q, qs, p[pfx + ".conv1.w8"], p[pfx + ".conv1.sw"], p[pfx + ".conv1.b"], rowvec=rv, gn_unit=self.gn_unit)
             self.fp8_convs.add(pfx + ".conv1")
             if not mx2:
-                h = ops.groupnorm(h, p[pfx + ".norm2.g"], p[pfx + ".norm2.b"], g, eps, SILU)
+                h = ops.groupnorm(h, *_norm(p, pfx + ".norm2", g, eps, SILU))
         else:
-            h = ops.groupnorm(x, p[pfx + ".norm1.g"], p[pfx + ".norm1.b"], g, eps, SILU, x2=x2)
+            h = ops.groupnorm(x, *_norm(p, pfx + ".norm1", g, eps, SILU), x2=x2)
             # conv1 -> norm2 -> SiLU: conv1's output has no other reader (fuse_gn: one launch for reduce + GroupNorm at the small levels)
-            h = ops.conv(h, p[pfx + ".conv1.w"], p[pfx + ".conv1.b"], kh=3, kw=3, pad=1, rowvec=rv, gn_unit=self.gn_unit,
-                         fuse_gn=None if mx2 else (p[pfx + ".norm2.g"], p[pfx + ".norm2.b"], g, eps, SILU))
+            h = ops.conv(h, *_wb(p, pfx + ".conv1"), kh=3, kw=3, pad=1, rowvec=rv, gn_unit=self.gn_unit,
+                         fuse_gn=None if mx2 else _norm(p, pfx + ".norm2", g, eps, SILU))
         # (the 1x1 shortcut conv on the side stream beside norm1 / conv1 -- MFMA-bound next to an HBM-bound pass -- measured +-0.1 % at
         # 512x512 / 512x704 / 512x768 in round 6, like round 4's finer forks: profiles/r6_sc_fork_ab.txt; not kept)
         if pfx + ".conv_shortcut.w" in p:
-            sc = ops.conv(x, p[pfx + ".conv_shortcut.w"], p[pfx + ".conv_shortcut.b"], x2=x2)
+            sc = ops.conv(x, *_wb(p, pfx + ".conv_shortcut"), x2=x2)
         else:
             assert x2 is None
             sc = x
         if mx2:
-            q, qs = ops.groupnorm_quant_mxfp8(h, p[pfx + ".norm2.g"], p[pfx + ".norm2.b"], g, eps, SILU)
+            q, qs = ops.groupnorm_quant_mxfp8(h, *_norm(p, pfx + ".norm2", g, eps, SILU))
             self.fp8_convs.add(pfx + ".conv2")
             return ops.conv3x3_mxfp8(q, qs, p[pfx + ".conv2.w8"], p[pfx + ".conv2.sw"], p[pfx + ".conv2.b"], residual=sc,
                                      gn_unit=self.gn_unit)
-        return ops.conv(h, p[pfx + ".conv2.w"], p[pfx + ".conv2.b"], kh=3, kw=3, pad=1, residual=sc, gn_unit=self.gn_unit)
+        return ops.conv(h, *_wb(p, pfx + ".conv2"), kh=3, kw=3, pad=1, residual=sc, gn_unit=self.gn_unit)
 
     def _quantize_block(self, t):
         """e4m3 copies (per-output-channel scales) of a transformer block's projections for saspa_gemm_fp8.
@@ -508,138 +565,170 @@ class _Net:
             p[t + ".ff.scale"] = torch.ones(1, device=self.dev, dtype=torch.float32)
             self.fp8_ffout[t] = False          # -> True once the scale has been calibrated (first execution of the block)
 
+    # ---- transformer blocks: which form each half takes (named, asking ops' predicates in a fixed order), then the launches ----
+    def _fusable(self, t, h, n, asked):
+        """Can the A-stationary kernel take block t's rows h (LayerNorm inside the projection: level 0 of a full-size batch)?  `asked`
+        keeps ops' answers of one transformer() call by row count: the three halves share one, rows doubled under cfg_pair are asked again."""
+        rows = h.shape[0] * n
+        if (t, rows) not in asked:
+            wqkv, c = self.p.get(t + ".attn1.qkv.w"), h.shape[-1]
+            asked[t, rows] = wqkv is not None and c == 320 and t not in self.fp8_blocks and n % 32 == 0 and \
+                bool(ops.linear_ln_fusable(h, wqkv, n_out=2 * c))
+        return asked[t, rows]
+
+    def _attn1_form(self, t, h, n, asked):
+        if t in self.fp8_qkv:
+            return "fp8"                # LayerNorm + per-token quantisation in one pass, ONE e4m3 projection launch for Q | K | V
+        if self._fusable(t, h, n, asked):
+            return "as_fused"           # LayerNorm + Q | K + V^T in ONE launch of the A-stationary kernel (saspa_gemm_as.hip)
+        if (t + ".attn1.qkv.w") in self.p and rowmajor_v_enabled():
+            return "qkv_rowmajor"       # one projection launch; the attention kernel takes its V columns as they are
+        return "qk_vt"                  # Q | K projection and the transposed value projection
+
+    def _attn2_form(self, t, h, n, asked, shared=False):
+        """shared: can ONE launch read the rows both CFG halves share (h at B rows, the context at 2B samples)?  "xattn_block" or None:
+        a condition of its own, `_fusable` asks for row blocks that half a batch does not have."""
+        kv = self.ctx_kv[t]
+        one_launch = len(kv) == 5 and n % 256 == 0 and kv[2] <= 96          # (fragments: prepare_context)
+        if shared:
+            return "xattn_block" if (_is_half(h.dtype) and h.shape[-1] == 320 and one_launch and t not in self.fp8_blocks) else None
+        if t in self.fp8_blocks:
+            return "fp8"
+        fuse = self._fusable(t, h, n, asked)
+        if fuse and one_launch:
+            return "xattn_block"        # LayerNorm + to_q + attention + to_out + residual in one launch
+        if fuse and ops.linear_ln_fusable(h, self.p[t + ".attn2.q.w"]):
+            return "ln_fused"
+        return "plain"
+
+    def _ff_form(self, t, h, n, asked):
+        p = self.p
+        if t in self.fp8_blocks:
+            return "fp8_mx" if t in self.fp8_ff_mx else "fp8_calibrated" if t in self.fp8_ffout else "fp8_bf16_out"
+        fuse = self._fusable(t, h, n, asked)
+        # (with a ragged last round of row blocks -- 512x704 -- the wave-specialised kernel + LayerNorm is as fast: ff_block_takes)
+        if t in self.ff_blocks and ff_block_takes(h.shape[0] * n) and ops.ff_block_eligible(h, p[t + ".ffb.w1"], p[t + ".ffb.w2f"]):
+            return "ff_block"
+        if fuse and t in self.fused_geglu and ops.linear_ln_fusable(h, p[t + ".ff.net.0.proj.w"], act=ops.ACT_GEGLU):
+            return "ln_fused_geglu"
+        return "geglu" if t in self.fused_geglu else "geglu_unfused"
+
+    def which(self, pfx, b, hh, ww, cfg_pair=False):
+        """[(attn1, attn2, ff) form names] of the blocks of transformer `pfx` on b samples of hh x ww tokens, without a launch (after
+        prepare_context: the context decides too).  "xattn_block shared": the one launch that reads the rows both CFG halves share."""
+        n, asked, out = hh * ww, {}, []
+        # (the predicates read shape, pitch, dtype and placement of the rows: one uninitialised buffer at 2B rows serves every question)
+        h2 = torch.empty(((2 if cfg_pair else 1) * b, n, self.p[pfx + ".norm.g"].numel()), device=self.dev, dtype=self.dtype)
+        for d in range(self.tr_info[pfx][1]):
+            t = f"{pfx}.transformer_blocks.{d}"
+            h = h2[:b] if d == 0 else h2                # block 0's self-attention runs before the rows double
+            shared = cfg_pair and d == 0 and self._attn2_form(t, h, n, asked, shared=True)
+            out.append((self._attn1_form(t, h, n, asked), "xattn_block shared" if shared else self._attn2_form(t, h2, n, asked),
+                        self._ff_form(t, h2, n, asked)))
+        return out
+
+    def _self_attention(self, t, h, heads, n, asked):
+        p, (b, _, c), pre = self.p, h.shape, t in self.qscaled
+        form = self._attn1_form(t, h, n, asked)
+        if form == "fp8":
+            qkv = ops.linear_fp8(*ops.layernorm_quant_fp8(h, *_norm(p, t + ".norm1")), p[t + ".attn1.qkv.w8"], p[t + ".attn1.qkv.sw"])
+            o = attention_core(qkv[:, :, :c], qkv[:, :, c:2 * c], qkv[:, :, 2 * c:3 * c], heads, n, n, prescaled=pre, v_rowmajor=True)
+        elif form == "as_fused":
+            vt = torch.empty((b, c, n), device=h.device, dtype=h.dtype)
+            qk = ops.linear(h, p[t + ".attn1.qkv.w"], None, ln=_norm(p, t + ".norm1", 1e-5), out_t=vt, n_split=2 * c, rows_per_batch=n)
+            o = attention_core(qk[:, :, :c], qk[:, :, c:], vt, heads, n, n, prescaled=pre)
+        elif form == "qkv_rowmajor":
+            qkv = ops.linear(ops.layernorm(h, *_norm(p, t + ".norm1")), p[t + ".attn1.qkv.w"])         # [B,N,3C]
+            o = attention_core(qkv[:, :, :c], qkv[:, :, c:2 * c], qkv[:, :, 2 * c:3 * c], heads, n, n, prescaled=pre, v_rowmajor=True)
+        else:
+            n1 = ops.layernorm(h, *_norm(p, t + ".norm1"))
+            qk = ops.linear(n1, p[t + ".attn1.qk.w"])                                           # [B,N,2C]
+            vt = project_vt(n1, p[t + ".attn1.v.w"], n)
+            o = attention_core(qk[:, :, :c], qk[:, :, c:], vt, heads, n, n, prescaled=pre)
+        return ops.linear(o, *_wb(p, t + ".attn1.o"), residual=h)
+
+    def _cross_attention(self, t, h, heads, n, asked, pair=False):
+        """Against the cached text K / V^T.  pair: h holds the B rows the two CFG halves share and the context 2B samples; they part
+        here -- inside the one launch that reads the shared rows, or by one copy in front of every other form -- and 2B rows leave."""
+        p, kv = self.p, self.ctx_kv[t]
+        if pair and kv[0].shape[0] != 2 * h.shape[0]:
+            raise ValueError(f"cfg_pair: {h.shape[0]} shared samples need a context of {2 * h.shape[0]} samples, not {kv[0].shape[0]}")
+        x_rows = h.shape[0] * n if (pair and self._attn2_form(t, h, n, asked, shared=True)) else None
+        if pair and x_rows is None:
+            h = ops.dup_rows(h)         # every form but the shared one: one copy, then the launches at 2B rows
+        form = "xattn_block" if x_rows else self._attn2_form(t, h, n, asked)
+        if form == "xattn_block":
+            return ops.xattn_block(h, _norm(p, t + ".norm2", 1e-5), p[t + ".attn2.xw"], p[t + ".attn2.xb"], kv[3], kv[4], kv[2], n,
+                                   x_rows=x_rows).view(-1, n, h.shape[-1])
+        if form == "fp8":
+            # W8A8: LayerNorm + per-token quantisation in one pass, e4m3 x e4m3 MFMA, scales applied in the epilogue
+            q = ops.linear_fp8(*ops.layernorm_quant_fp8(h, *_norm(p, t + ".norm2")), p[t + ".attn2.q.w8"], p[t + ".attn2.q.sw"])
+        elif form == "ln_fused":
+            q = ops.linear(h, p[t + ".attn2.q.w"], ln=_norm(p, t + ".norm2", 1e-5))
+        else:
+            q = ops.linear(ops.layernorm(h, *_norm(p, t + ".norm2")), p[t + ".attn2.q.w"])
+        o = attention_core(q, kv[0], kv[1], heads, n, kv[2], prescaled=t in self.qscaled)
+        return ops.linear(o, *_wb(p, t + ".attn2.o"), residual=h)
+
+    def _ff_scale(self, t, q8, s8):
+        """The tensor-wide e4m3 scale of block t's feed-forward hidden state, calibrated the first time the block runs (always an
+        eager launch: a step graph is captured after an eager warm-up step): one extra GEGLU launch measures max |value|, the scale
+        becomes the power of two >= 16 * max / 448 -- e4m3 is a floating format, a power-of-two scale only shifts exponents, so the
+        bytes do not depend on the calibration batch short of overflow (4 binades of head room, saturating)."""
+        p = self.p
+        if not self.fp8_ffout[t]:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("fp8 feed-forward scale of %s is not calibrated: run one eager evaluation before capture" % t)
+            ops.linear_fp8(q8, s8, *_geglu8(p, t), act=ops.ACT_GEGLU, amax=p[t + ".ff.amax"])
+            p[t + ".ff.scale"].copy_(ops.fp8_pow2_scale(p[t + ".ff.amax"]))
+            self.fp8_ffout[t] = True
+        return p[t + ".ff.scale"]
+
+    def _feed_forward(self, t, h, n, asked):
+        p = self.p
+        form = self._ff_form(t, h, n, asked)
+        if form == "ff_block":
+            f = t + ".ffb"
+            return ops.ff_block(h, _norm(p, t + ".norm3", 1e-5), p[f + ".w1"], p[f + ".b1"], p[f + ".w2f"], p[f + ".b2"], residual=h)
+        if form == "fp8_mx":
+            # the hidden state leaves the GEGLU epilogue as MX e4m3 (an exponent per row and 32 columns, from that row's own
+            # values) and the output projection applies the exponents inside its MFMAs: nothing to calibrate
+            ff8, ffs = ops.linear_fp8(*ops.layernorm_quant_fp8(h, *_norm(p, t + ".norm3")), *_geglu8(p, t), act=ops.ACT_GEGLU, out_mx=True)
+            return ops.linear_mxfp8(ff8, ffs, p[t + ".ff.net.2.w8"], p[t + ".ff.net.2.sw"], p[t + ".ff.net.2.b"], residual=h)
+        if form == "fp8_calibrated":
+            # the hidden state leaves the GEGLU epilogue as e4m3 under ONE tensor-wide scale and the output projection reads the bytes
+            q8, s8 = ops.layernorm_quant_fp8(h, *_norm(p, t + ".norm3"))
+            scale = self._ff_scale(t, q8, s8)
+            ff8 = ops.linear_fp8(q8, s8, *_geglu8(p, t), act=ops.ACT_GEGLU, out_fp8_scale=scale)
+            return ops.linear_fp8(ff8, scale, p[t + ".ff.net.2.w8"], p[t + ".ff.net.2.sw"], p[t + ".ff.net.2.b"], residual=h)
+        if form == "fp8_bf16_out":
+            ff = ops.linear_fp8(*ops.layernorm_quant_fp8(h, *_norm(p, t + ".norm3")), *_geglu8(p, t), act=ops.ACT_GEGLU)
+        elif form == "ln_fused_geglu":
+            ff = ops.linear(h, *_wb(p, t + ".ff.net.0.proj"), act=ops.ACT_GEGLU, ln=_norm(p, t + ".norm3", 1e-5))
+        elif form == "geglu":
+            ff = ops.linear(ops.layernorm(h, *_norm(p, t + ".norm3")), *_wb(p, t + ".ff.net.0.proj"), act=ops.ACT_GEGLU)
+        else:
+            ff = ops.geglu(ops.linear(ops.layernorm(h, *_norm(p, t + ".norm3")), *_wb(p, t + ".ff.net.0.proj")))
+        return ops.linear(ff, *_wb(p, t + ".ff.net.2"), residual=h)
+
     def transformer(self, pfx, x, cfg_pair=False):
         """Transformer2DModel.  cfg_pair: x holds the B rows both CFG halves share and the cached context 2B samples (uncond
         first).  GroupNorm, proj_in and the first block's self-attention run once at B rows; the rows double where the context
-        enters -- in the fused cross-attention launch itself (ops.xattn_block(x_rows=...)) or by one copy in front of the
-        existing code -- and the result has 2B rows."""
-        p, g = self.p, self.cfg["groups"]
+        enters (_cross_attention(pair=True)) and the result has 2B rows.  Which form each half of a block takes: which()."""
+        p = self.p
         heads, depth = self.tr_info[pfx]
         b, hh, ww, c = x.shape
-        n = hh * ww
-        h = ops.groupnorm(x, p[pfx + ".norm.g"], p[pfx + ".norm.b"], g, 1e-6)
-        h = ops.conv(h, p[pfx + ".proj_in.w"], p[pfx + ".proj_in.b"]).view(b, n, c)
+        n, asked = hh * ww, {}
+        h = ops.groupnorm(x, *_norm(p, pfx + ".norm", self.cfg["groups"], 1e-6))
+        h = ops.conv(h, *_wb(p, pfx + ".proj_in")).view(b, n, c)
         for d in range(depth):
             t = f"{pfx}.transformer_blocks.{d}"
-            # self-attention.  Level 0 of a full-size batch: LayerNorm + Q | K + V^T in ONE launch of the A-stationary kernel
-            # (saspa_gemm_as.hip) instead of three launches that each re-read the tokens
-            wqkv = p.get(t + ".attn1.qkv.w")
-
-            def fusable(rows):
-                return wqkv is not None and c == 320 and t not in self.fp8_blocks and n % 32 == 0 and \
-                    ops.linear_ln_fusable(rows, wqkv, n_out=2 * c)
-            fuse = fusable(h)
-            pre = t in self.qscaled
-            if t in self.fp8_qkv:
-                # W8A8 (round 6): LayerNorm + per-token quantisation in one pass, ONE e4m3 projection launch for Q | K | V
-                q8, s8 = ops.layernorm_quant_fp8(h, p[t + ".norm1.g"], p[t + ".norm1.b"])
-                qkv = ops.linear_fp8(q8, s8, p[t + ".attn1.qkv.w8"], p[t + ".attn1.qkv.sw"])          # [B,N,3C] bf16
-                o = attention_core(qkv[:, :, :c], qkv[:, :, c:2 * c], qkv[:, :, 2 * c:3 * c], heads, n, n, prescaled=pre, v_rowmajor=True)
-            elif fuse:
-                vt = torch.empty((b, c, n), device=h.device, dtype=h.dtype)
-                qk = ops.linear(h, wqkv, None, ln=(p[t + ".norm1.g"], p[t + ".norm1.b"], 1e-5), out_t=vt, n_split=2 * c, rows_per_batch=n)
-                o = attention_core(qk[:, :, :c], qk[:, :, c:], vt, heads, n, n, prescaled=pre)
-            elif wqkv is not None and rowmajor_v_enabled():
-                # one projection launch; the attention kernel takes its V columns as they are
-                n1 = ops.layernorm(h, p[t + ".norm1.g"], p[t + ".norm1.b"])
-                qkv = ops.linear(n1, wqkv)                                     # [B,N,3C]
-                o = attention_core(qkv[:, :, :c], qkv[:, :, c:2 * c], qkv[:, :, 2 * c:3 * c], heads, n, n, prescaled=pre, v_rowmajor=True)
-            else:
-                n1 = ops.layernorm(h, p[t + ".norm1.g"], p[t + ".norm1.b"])
-                qk = ops.linear(n1, p[t + ".attn1.qk.w"])                     # [B,N,2C]
-                vt = project_vt(n1, p[t + ".attn1.v.w"], n)
-                o = attention_core(qk[:, :, :c], qk[:, :, c:], vt, heads, n, n, prescaled=pre)
-            h = ops.linear(o, p[t + ".attn1.o.w"], p[t + ".attn1.o.b"], residual=h)
-            if cfg_pair and d == 0:
-                # the two CFG halves part here: everything above ran once on the rows they share
-                kv = self.ctx_kv[t]
-                if kv[0].shape[0] != 2 * b:
-                    raise ValueError(f"cfg_pair: {b} shared samples need a context of {2 * b} samples, not {kv[0].shape[0]}")
-                if _is_half(h.dtype) and c == 320 and len(kv) == 5 and n % 256 == 0 and kv[2] <= 96 and t not in self.fp8_blocks:
-                    # LayerNorm + to_q + attention + to_out + residual of BOTH halves in one launch that reads the shared rows
-                    # (a condition of its own: `fuse` asks for row blocks that half a batch does not have)
-                    h = ops.xattn_block(h, (p[t + ".norm2.g"], p[t + ".norm2.b"], 1e-5), p[t + ".attn2.xw"], p[t + ".attn2.xb"],
-                                        kv[3], kv[4], kv[2], n, x_rows=b * n).view(2 * b, n, c)
-                    shared_xattn = True
-                else:
-                    h = ops.dup_rows(h)         # every other form: one copy, then the existing code at 2B rows
-                    shared_xattn = False
-                b *= 2
-                fuse = fusable(h)
-            else:
-                shared_xattn = False
-            if t in self.fp8_blocks:
-                # W8A8: LayerNorm + per-token quantisation in one pass, e4m3 x e4m3 MFMA, scales applied in the epilogue
-                q8, s8 = ops.layernorm_quant_fp8(h, p[t + ".norm2.g"], p[t + ".norm2.b"])
-                q = ops.linear_fp8(q8, s8, p[t + ".attn2.q.w8"], p[t + ".attn2.q.sw"])
-                k, vtc, nk = self.ctx_kv[t][:3]
-                o = attention_core(q, k, vtc, heads, n, nk, prescaled=pre)
-                h = ops.linear(o, p[t + ".attn2.o.w"], p[t + ".attn2.o.b"], residual=h)
-                q8, s8 = ops.layernorm_quant_fp8(h, p[t + ".norm3.g"], p[t + ".norm3.b"])
-                if t in self.fp8_ff_mx:
-                    # the hidden state leaves the GEGLU epilogue as MX e4m3 (an exponent per row and 32 columns, from that row's own
-                    # values) and the output projection applies the exponents inside its MFMAs: nothing to calibrate
-                    ff8, ffs = ops.linear_fp8(q8, s8, p[t + ".ff.net.0.proj.w8"], p[t + ".ff.net.0.proj.sw"], p[t + ".ff.net.0.proj.b8"],
-                                              act=ops.ACT_GEGLU, out_mx=True)
-                    h = ops.linear_mxfp8(ff8, ffs, p[t + ".ff.net.2.w8"], p[t + ".ff.net.2.sw"], p[t + ".ff.net.2.b"], residual=h)
-                    continue
-                if t in self.fp8_ffout:
-                    # the hidden state leaves the GEGLU epilogue as e4m3 under ONE tensor-wide scale and the output projection
-                    # reads the bytes.  The scale is calibrated the first time the block runs (always an eager launch: a step graph
-                    # is captured after an eager warm-up step): one extra GEGLU launch measures max |value|, the scale becomes the
-                    # power of two >= 16 * max / 448 -- e4m3 is a floating format, a power-of-two scale only shifts exponents, so
-                    # the bytes do not depend on the calibration batch short of overflow (4 binades of head room, saturating)
-                    if not self.fp8_ffout[t]:
-                        if torch.cuda.is_current_stream_capturing():
-                            raise RuntimeError("fp8 feed-forward scale of %s is not calibrated: run one eager evaluation before capture" % t)
-                        ops.linear_fp8(q8, s8, p[t + ".ff.net.0.proj.w8"], p[t + ".ff.net.0.proj.sw"], p[t + ".ff.net.0.proj.b8"],
-                                       act=ops.ACT_GEGLU, amax=p[t + ".ff.amax"])
-                        p[t + ".ff.scale"].copy_(ops.fp8_pow2_scale(p[t + ".ff.amax"]))
-                        self.fp8_ffout[t] = True
-                    ff8 = ops.linear_fp8(q8, s8, p[t + ".ff.net.0.proj.w8"], p[t + ".ff.net.0.proj.sw"], p[t + ".ff.net.0.proj.b8"],
-                                         act=ops.ACT_GEGLU, out_fp8_scale=p[t + ".ff.scale"])
-                    h = ops.linear_fp8(ff8, p[t + ".ff.scale"], p[t + ".ff.net.2.w8"], p[t + ".ff.net.2.sw"], p[t + ".ff.net.2.b"], residual=h)
-                    continue
-                ff = ops.linear_fp8(q8, s8, p[t + ".ff.net.0.proj.w8"], p[t + ".ff.net.0.proj.sw"], p[t + ".ff.net.0.proj.b8"],
-                                    act=ops.ACT_GEGLU)
-                h = ops.linear(ff, p[t + ".ff.net.2.w"], p[t + ".ff.net.2.b"], residual=h)
-                continue
-            # cross-attention against the cached text K / V^T
-            kv = self.ctx_kv[t]
-            if shared_xattn:
-                pass
-            elif fuse and len(kv) == 5 and n % 256 == 0 and kv[2] <= 96:
-                # level 0 of a full-size batch: LayerNorm + to_q + attention + to_out + residual in one launch
-                h = ops.xattn_block(h, (p[t + ".norm2.g"], p[t + ".norm2.b"], 1e-5), p[t + ".attn2.xw"], p[t + ".attn2.xb"], kv[3], kv[4],
-                                    kv[2], n)
-            else:
-                if fuse and ops.linear_ln_fusable(h, p[t + ".attn2.q.w"]):
-                    q = ops.linear(h, p[t + ".attn2.q.w"], ln=(p[t + ".norm2.g"], p[t + ".norm2.b"], 1e-5))
-                else:
-                    n2 = ops.layernorm(h, p[t + ".norm2.g"], p[t + ".norm2.b"])
-                    q = ops.linear(n2, p[t + ".attn2.q.w"])
-                k, vtc, nk = kv[:3]
-                o = attention_core(q, k, vtc, heads, n, nk, prescaled=pre)
-                h = ops.linear(o, p[t + ".attn2.o.w"], p[t + ".attn2.o.b"], residual=h)
-            # GEGLU feed-forward
-            # (with a ragged last round of row blocks -- 512x704 -- the wave-specialised kernel + LayerNorm is as fast)
-            if t in self.ff_blocks and ff_block_takes(b * n) and ops.ff_block_eligible(h, p[t + ".ffb.w1"], p[t + ".ffb.w2f"]):
-                h = ops.ff_block(h, (p[t + ".norm3.g"], p[t + ".norm3.b"], 1e-5), p[t + ".ffb.w1"], p[t + ".ffb.b1"], p[t + ".ffb.w2f"],
-                                 p[t + ".ffb.b2"], residual=h)
-                continue
-            if fuse and t in self.fused_geglu and ops.linear_ln_fusable(h, p[t + ".ff.net.0.proj.w"], act=ops.ACT_GEGLU):
-                ff = ops.linear(h, p[t + ".ff.net.0.proj.w"], p[t + ".ff.net.0.proj.b"], act=ops.ACT_GEGLU,
-                                ln=(p[t + ".norm3.g"], p[t + ".norm3.b"], 1e-5))
-            else:
-                n3 = ops.layernorm(h, p[t + ".norm3.g"], p[t + ".norm3.b"])
-                if t in self.fused_geglu:
-                    ff = ops.linear(n3, p[t + ".ff.net.0.proj.w"], p[t + ".ff.net.0.proj.b"], act=ops.ACT_GEGLU)
-                else:
-                    ff = ops.geglu(ops.linear(n3, p[t + ".ff.net.0.proj.w"], p[t + ".ff.net.0.proj.b"]))
-            h = ops.linear(ff, p[t + ".ff.net.2.w"], p[t + ".ff.net.2.b"], residual=h)
+            h = self._self_attention(t, h, heads, n, asked)
+            h = self._cross_attention(t, h, heads, n, asked, pair=cfg_pair and d == 0)
+            h = self._feed_forward(t, h, n, asked)
         if cfg_pair:
             x = ops.dup_rows(x)                 # the proj_out residual, at 2B rows like h
-        return ops.conv(h.view(b, hh, ww, c), p[pfx + ".proj_out.w"], p[pfx + ".proj_out.b"], residual=x, gn_unit=self.gn_unit)
+        return ops.conv(h.view(x.shape), *_wb(p, pfx + ".proj_out"), residual=x, gn_unit=self.gn_unit)
 
     def encode(self, sample, step, conv_in_residual=None, cfg_pair=False):
         """conv_in + down blocks + mid block.  Returns (mid, [skips]).
@@ -649,25 +738,22 @@ class _Net:
         back at 2B rows as from encode(cat([sample, sample])), except skips[0] (conv_in's output), which stays at B rows
         (ControlNet.zero_convs(cfg_pair=True) / ops.dup_rows).  Only for networks whose time-embedding row is one for the whole
         batch (prepare_timesteps without added conditioning)."""
-        cfg, p = self.cfg, self.p
-        if cfg_pair and "add_embed" in cfg:
+        p = self.p
+        if cfg_pair and "add_embed" in self.cfg:
             raise ValueError("cfg_pair: the added conditioning gives the two halves different time embeddings (SDXL)")
-        s = ops.conv(sample, p["conv_in.w"], p["conv_in.b"], kh=3, kw=3, pad=1, residual=conv_in_residual, gn_unit=self.gn_unit)
+        s = ops.conv(sample, *_wb(p, "conv_in"), kh=3, kw=3, pad=1, residual=conv_in_residual, gn_unit=self.gn_unit)
         skips = [s]
-        n_lvl = len(cfg["block_out"])
-        for i in range(n_lvl):
-            for j in range(cfg["layers"]):
-                s = self.resnet(f"down_blocks.{i}.resnets.{j}", s, step, 1e-5)
-                first = cfg_pair and i == 0 and j == 0
-                if cfg["attn"][i]:
-                    s = self.transformer(f"down_blocks.{i}.attentions.{j}", s, cfg_pair=first)
+        for k, (kind, name, attn, _) in enumerate(self.down_layout):
+            first = cfg_pair and k == 0
+            if kind == "down":
+                s = ops.conv(s, *_wb(p, name), kh=3, kw=3, stride=2, pad=1, gn_unit=self.gn_unit)
+            else:
+                s = self.resnet(name, s, step, 1e-5)
+                if attn:
+                    s = self.transformer(attn, s, cfg_pair=first)
                 elif first:
                     s = ops.dup_rows(s)         # no attention at level 0: the halves part behind the first resnet
-                skips.append(s)
-            if i != n_lvl - 1:
-                d = f"down_blocks.{i}.downsamplers.0.conv"
-                s = ops.conv(s, p[d + ".w"], p[d + ".b"], kh=3, kw=3, stride=2, pad=1, gn_unit=self.gn_unit)
-                skips.append(s)
+            skips.append(s)
         s = self.resnet("mid_block.resnets.0", s, step, 1e-5)
         s = self.transformer("mid_block.attentions.0", s)
         s = self.resnet("mid_block.resnets.1", s, step, 1e-5)
@@ -677,50 +763,42 @@ class _Net:
 class UNet(_Net):
     """UNet2DConditionModel (SD-1.5 topology)."""
 
-    def __init__(self, sd, cfg, dev, dtype, fp8=False, fp8_conv=False, fp8_ff="calibrated"):
-        super().__init__(sd, cfg, dev, dtype, fp8, fp8_conv, fp8_ff)
-        self._pack_encoder()
-        pk = self.pk
+    def _pack_rest(self):
+        pk, cfg = self.pk, self.cfg
         bo = cfg["block_out"]
-        # skip channel bookkeeping (mirrors the encoder)
-        skip_ch = [bo[0]]
-        for i, c in enumerate(bo):
-            skip_ch += [c] * cfg["layers"]
-            if i != len(bo) - 1:
-                skip_ch.append(c)
-        rev = list(reversed(bo))
-        prev = rev[0]
         n_lvl = len(bo)
-        for i, c in enumerate(rev):
+        # the up path in execution order, walked by this loop and by decode(): ("layer", resnet, transformer or None, level, (channels
+        # from below, channels of the skip it pops)) and ("up", x2 conv, None, level, None); the skips are the encoder's, last first
+        skip_ch = [bo[0]] + [bo[lvl] for _, _, _, lvl in self.down_layout]
+        self.up_layout, prev = [], bo[-1]
+        for i, lvl in enumerate(reversed(range(n_lvl))):
             for j in range(cfg["layers"] + 1):
-                sk = skip_ch.pop()
-                self._pack_resnet(f"up_blocks.{i}.resnets.{j}", split=(prev, sk))
-                if list(reversed(cfg["attn"]))[i]:
-                    self._pack_transformer(f"up_blocks.{i}.attentions.{j}", n_lvl - 1 - i)
-                prev = c
+                self.up_layout.append(("layer", f"up_blocks.{i}.resnets.{j}", f"up_blocks.{i}.attentions.{j}" if cfg["attn"][lvl] else None,
+                                       lvl, (prev, skip_ch.pop())))
+                prev = bo[lvl]
             if i != n_lvl - 1:
-                pk.conv_up2x(f"up_blocks.{i}.upsamplers.0.conv")
+                self.up_layout.append(("up", f"up_blocks.{i}.upsamplers.0.conv", None, lvl, None))
+        for kind, name, attn, lvl, split in self.up_layout:
+            if kind == "up":
+                pk.conv_up2x(name)
+                continue
+            self._pack_resnet(name, split=split)
+            if attn:
+                self._pack_transformer(attn, lvl)
         pk.norm("conv_norm_out")
         pk.conv("conv_out")
-        pk.sd = None  # drop the fp32 host copy reference
 
     def decode(self, mid, skips, step, out=None):
-        cfg, p = self.cfg, self.p
-        s = mid
-        skips = list(skips)
-        n_lvl = len(cfg["block_out"])
-        rev_attn = list(reversed(cfg["attn"]))
-        for i in range(n_lvl):
-            for j in range(cfg["layers"] + 1):
-                sk = skips.pop()
-                s = self.resnet(f"up_blocks.{i}.resnets.{j}", s, step, 1e-5, x2=sk)
-                if rev_attn[i]:
-                    s = self.transformer(f"up_blocks.{i}.attentions.{j}", s)
-            if i != n_lvl - 1:
-                u = f"up_blocks.{i}.upsamplers.0.conv"
-                s = ops.conv(s, p[u + ".w"], p[u + ".b"], kh=3, kw=3, pad=1, upsample=True, gn_unit=self.gn_unit)
-        s = ops.groupnorm(s, p["conv_norm_out.g"], p["conv_norm_out.b"], cfg["groups"], 1e-5, SILU)
-        return ops.conv(s, p["conv_out.w"], p["conv_out.b"], kh=3, kw=3, pad=1, out=out)
+        p, s, skips = self.p, mid, list(skips)
+        for kind, name, attn, _, _ in self.up_layout:
+            if kind == "up":
+                s = ops.conv(s, *_wb(p, name), kh=3, kw=3, pad=1, upsample=True, gn_unit=self.gn_unit)
+                continue
+            s = self.resnet(name, s, step, 1e-5, x2=skips.pop())
+            if attn:
+                s = self.transformer(attn, s)
+        s = ops.groupnorm(s, *_norm(p, "conv_norm_out", self.cfg["groups"], 1e-5, SILU))
+        return ops.conv(s, *_wb(p, "conv_out"), kh=3, kw=3, pad=1, out=out)
 
     def forward(self, sample, step):
         """UNet forward without ControlNet residuals."""
@@ -731,34 +809,28 @@ class UNet(_Net):
 class ControlNet(_Net):
     """ControlNetModel (control_v11p_sd15_canny topology)."""
 
-    def __init__(self, sd, cfg, dev, dtype, fp8=False, fp8_conv=False, fp8_ff="calibrated"):
-        super().__init__(sd, cfg, dev, dtype, fp8, fp8_conv, fp8_ff)
-        self._pack_encoder()
-        pk = self.pk
-        ce = cfg["cond_embed"]
+    def _pack_rest(self):
+        pk, ce = self.pk, self.cfg["cond_embed"]
         e = "controlnet_cond_embedding"
         pk.conv(e + ".conv_in")
         for i in range(2 * (len(ce) - 1)):
             pk.conv(f"{e}.blocks.{i}")
         pk.conv(e + ".conv_out")
-        n_skips = 1 + sum(cfg["layers"] + (1 if i != len(cfg["block_out"]) - 1 else 0) for i in range(len(cfg["block_out"])))
-        self.n_skips = n_skips
-        for i in range(n_skips):
+        self.n_skips = 1 + len(self.down_layout)
+        for i in range(self.n_skips):
             pk.conv(f"controlnet_down_blocks.{i}")
         pk.conv("controlnet_mid_block")
-        pk.sd = None
 
     def cond_embedding(self, cond):
         """ControlNetConditioningEmbedding on [B,H,W,8] control images in [0,1]; time-invariant,
         computed once per image (diffusers recomputes it every step)."""
         p = self.p
         e = "controlnet_cond_embedding"
-        h = ops.conv(cond, p[e + ".conv_in.w"], p[e + ".conv_in.b"], kh=3, kw=3, pad=1, act=SILU)
+        h = ops.conv(cond, *_wb(p, e + ".conv_in"), kh=3, kw=3, pad=1, act=SILU)
         for i in range(len(self.cfg["cond_embed"]) - 1):
-            h = ops.conv(h, p[f"{e}.blocks.{2 * i}.w"], p[f"{e}.blocks.{2 * i}.b"], kh=3, kw=3, pad=1, act=SILU)
-            h = ops.conv(h, p[f"{e}.blocks.{2 * i + 1}.w"], p[f"{e}.blocks.{2 * i + 1}.b"], kh=3, kw=3, stride=2, pad=1,
-                         act=SILU)
-        return ops.conv(h, p[e + ".conv_out.w"], p[e + ".conv_out.b"], kh=3, kw=3, pad=1)
+            h = ops.conv(h, *_wb(p, f"{e}.blocks.{2 * i}"), kh=3, kw=3, pad=1, act=SILU)
+            h = ops.conv(h, *_wb(p, f"{e}.blocks.{2 * i + 1}"), kh=3, kw=3, stride=2, pad=1, act=SILU)
+        return ops.conv(h, *_wb(p, e + ".conv_out"), kh=3, kw=3, pad=1)
 
     def forward(self, sample, step, cond_emb, scale, unet_skips=None, unet_mid=None, cfg_pair=False):
         """Returns ([12 residuals], mid residual), each scale*(zero_conv(feature)) and, when the
@@ -774,13 +846,10 @@ class ControlNet(_Net):
         outs = []
         for i, f in enumerate(feats):
             r = None if unet_skips is None else unet_skips[i]
-            outs.append(ops.conv(f, p[f"controlnet_down_blocks.{i}.w"], p[f"controlnet_down_blocks.{i}.b"], alpha=scale,
-                                 residual=r, gn_unit=self.gn_unit))
+            outs.append(ops.conv(f, *_wb(p, f"controlnet_down_blocks.{i}"), alpha=scale, residual=r, gn_unit=self.gn_unit))
             if cfg_pair and i == 0:
                 outs[0] = ops.dup_rows(outs[0])
-        m = ops.conv(mid, p["controlnet_mid_block.w"], p["controlnet_mid_block.b"], alpha=scale, residual=unet_mid,
-                     gn_unit=self.gn_unit)
-        return outs, m
+        return outs, ops.conv(mid, *_wb(p, "controlnet_mid_block"), alpha=scale, residual=unet_mid, gn_unit=self.gn_unit)
 
 
 class VAEDecoder:
@@ -794,15 +863,11 @@ class VAEDecoder:
         self.p = pk.p
         pk.conv("post_quant_conv")
         pk.conv("decoder.conv_in")
-        self._pack_resnet("decoder.mid_block.resnets.0")
-        a = "decoder.mid_block.attentions.0"
-        pk.norm(a + ".group_norm")
-        pk.attn(a, True, has_bias=True)
-        self._pack_resnet("decoder.mid_block.resnets.1")
+        self._pack_mid("decoder.mid_block")
         n_lvl = len(cfg["block_out"])
         for i in range(n_lvl):
             for j in range(cfg["layers"] + 1):
-                self._pack_resnet(f"decoder.up_blocks.{i}.resnets.{j}")
+                pk.resnet(f"decoder.up_blocks.{i}.resnets.{j}")
             if i != n_lvl - 1:
                 pk.conv_up2x(f"decoder.up_blocks.{i}.upsamplers.0.conv")
         pk.norm("decoder.conv_norm_out")
@@ -825,24 +890,21 @@ class VAEDecoder:
             t2.saspa_korder, t2.saspa_cin, t2.saspa_wsplit = t.saspa_korder, cin, 1
             self.p[k] = t2
 
-    def _pack_resnet(self, pfx):
-        pk = self.pk
-        pk.norm(pfx + ".norm1")
-        pk.conv(pfx + ".conv1")
-        pk.norm(pfx + ".norm2")
-        pk.conv(pfx + ".conv2")
-        if pfx + ".conv_shortcut.weight" in pk.sd:
-            pk.conv(pfx + ".conv_shortcut")
+    def _pack_mid(self, m):
+        self.pk.resnet(m + ".resnets.0")
+        self.pk.norm(m + ".attentions.0.group_norm")
+        self.pk.attn(m + ".attentions.0", True, has_bias=True)
+        self.pk.resnet(m + ".resnets.1")
 
     def resnet(self, pfx, x):
         p, g = self.p, self.cfg["groups"]
-        h = ops.groupnorm(x, p[pfx + ".norm1.g"], p[pfx + ".norm1.b"], g, 1e-6, SILU)
-        h = ops.conv(h, p[pfx + ".conv1.w"], p[pfx + ".conv1.b"], kh=3, kw=3, pad=1)
-        h = ops.groupnorm(h, p[pfx + ".norm2.g"], p[pfx + ".norm2.b"], g, 1e-6, SILU)
+        h = ops.groupnorm(x, *_norm(p, pfx + ".norm1", g, 1e-6, SILU))
+        h = ops.conv(h, *_wb(p, pfx + ".conv1"), kh=3, kw=3, pad=1)
+        h = ops.groupnorm(h, *_norm(p, pfx + ".norm2", g, 1e-6, SILU))
         sc = x
         if pfx + ".conv_shortcut.w" in p:
-            sc = ops.conv(x, p[pfx + ".conv_shortcut.w"], p[pfx + ".conv_shortcut.b"])
-        return ops.conv(h, p[pfx + ".conv2.w"], p[pfx + ".conv2.b"], kh=3, kw=3, pad=1, residual=sc)
+            sc = ops.conv(x, *_wb(p, pfx + ".conv_shortcut"))
+        return ops.conv(h, *_wb(p, pfx + ".conv2"), kh=3, kw=3, pad=1, residual=sc)
 
     def mid_attention(self, x):
         return self._mid_attention(x, "decoder.mid_block.attentions.0")
@@ -851,11 +913,11 @@ class VAEDecoder:
         p = self.p
         b, hh, ww, c = x.shape
         n = hh * ww
-        h = ops.groupnorm(x, p[a + ".group_norm.g"], p[a + ".group_norm.b"], self.cfg["groups"], 1e-6).view(b, n, c)
-        qk = ops.linear(h, p[a + ".qk.w"], p[a + ".qk.b"])
+        h = ops.groupnorm(x, *_norm(p, a + ".group_norm", self.cfg["groups"], 1e-6)).view(b, n, c)
+        qk = ops.linear(h, *_wb(p, a + ".qk"))
         vt = project_vt(h, p[a + ".v.w"], n)
         o = attention_core(qk[:, :, :c], qk[:, :, c:], vt, 1, n, n)
-        return ops.linear(o, p[a + ".o.w"], p[a + ".o.b"], residual=x.view(b, n, c)).view(b, hh, ww, c)
+        return ops.linear(o, *_wb(p, a + ".o"), residual=x.view(b, n, c)).view(b, hh, ww, c)
 
     def decode(self, z):
         """z: [B,h,w,8] latents ALREADY divided by the scaling factor -> [B,8h,8w,8] (3 live).  The kernels address
@@ -872,8 +934,8 @@ class VAEDecoder:
 
     def _decode(self, z):
         p, cfg = self.p, self.cfg
-        h = ops.conv(z, p["post_quant_conv.w"], p["post_quant_conv.b"])
-        h = ops.conv(h, p["decoder.conv_in.w"], p["decoder.conv_in.b"], kh=3, kw=3, pad=1)
+        h = ops.conv(z, *_wb(p, "post_quant_conv"))
+        h = ops.conv(h, *_wb(p, "decoder.conv_in"), kh=3, kw=3, pad=1)
         h = self.resnet("decoder.mid_block.resnets.0", h)
         h = self.mid_attention(h)
         h = self.resnet("decoder.mid_block.resnets.1", h)
@@ -882,10 +944,9 @@ class VAEDecoder:
             for j in range(cfg["layers"] + 1):
                 h = self.resnet(f"decoder.up_blocks.{i}.resnets.{j}", h)
             if i != n_lvl - 1:
-                u = f"decoder.up_blocks.{i}.upsamplers.0.conv"
-                h = ops.conv(h, p[u + ".w"], p[u + ".b"], kh=3, kw=3, pad=1, upsample=True)
-        h = ops.groupnorm(h, p["decoder.conv_norm_out.g"], p["decoder.conv_norm_out.b"], cfg["groups"], 1e-6, SILU)
-        return ops.conv(h, p["decoder.conv_out.w"], p["decoder.conv_out.b"], kh=3, kw=3, pad=1)
+                h = ops.conv(h, *_wb(p, f"decoder.up_blocks.{i}.upsamplers.0.conv"), kh=3, kw=3, pad=1, upsample=True)
+        h = ops.groupnorm(h, *_norm(p, "decoder.conv_norm_out", cfg["groups"], 1e-6, SILU))
+        return ops.conv(h, *_wb(p, "decoder.conv_out"), kh=3, kw=3, pad=1)
 
 
 class VAEEncoder(VAEDecoder):
@@ -901,14 +962,10 @@ class VAEEncoder(VAEDecoder):
         n_lvl = len(cfg["block_out"])
         for i in range(n_lvl):
             for j in range(cfg["layers"]):
-                self._pack_resnet(f"encoder.down_blocks.{i}.resnets.{j}")
+                pk.resnet(f"encoder.down_blocks.{i}.resnets.{j}")
             if i != n_lvl - 1:
                 pk.conv(f"encoder.down_blocks.{i}.downsamplers.0.conv")
-        self._pack_resnet("encoder.mid_block.resnets.0")
-        a = "encoder.mid_block.attentions.0"
-        pk.norm(a + ".group_norm")
-        pk.attn(a, True, has_bias=True)
-        self._pack_resnet("encoder.mid_block.resnets.1")
+        self._pack_mid("encoder.mid_block")
         pk.norm("encoder.conv_norm_out")
         pk.conv("encoder.conv_out")
         pk.conv("quant_conv")
@@ -917,20 +974,20 @@ class VAEEncoder(VAEDecoder):
     def encode(self, x):
         """x: [B,H,W,8] pixels in [-1,1] (3 live channels) -> moments [B,H/8,W/8,8]."""
         p, cfg = self.p, self.cfg
-        h = ops.conv(x, p["encoder.conv_in.w"], p["encoder.conv_in.b"], kh=3, kw=3, pad=1)
+        h = ops.conv(x, *_wb(p, "encoder.conv_in"), kh=3, kw=3, pad=1)
         n_lvl = len(cfg["block_out"])
         for i in range(n_lvl):
             for j in range(cfg["layers"]):
                 h = self.resnet(f"encoder.down_blocks.{i}.resnets.{j}", h)
             if i != n_lvl - 1:
-                d = f"encoder.down_blocks.{i}.downsamplers.0.conv"
-                h = ops.conv(h, p[d + ".w"], p[d + ".b"], kh=3, kw=3, stride=2, pad=0, out_hw=(h.shape[1] // 2, h.shape[2] // 2))
+                h = ops.conv(h, *_wb(p, f"encoder.down_blocks.{i}.downsamplers.0.conv"), kh=3, kw=3, stride=2, pad=0,
+                             out_hw=(h.shape[1] // 2, h.shape[2] // 2))
         h = self.resnet("encoder.mid_block.resnets.0", h)
         h = self._mid_attention(h, "encoder.mid_block.attentions.0")
         h = self.resnet("encoder.mid_block.resnets.1", h)
-        h = ops.groupnorm(h, p["encoder.conv_norm_out.g"], p["encoder.conv_norm_out.b"], cfg["groups"], 1e-6, SILU)
-        h = ops.conv(h, p["encoder.conv_out.w"], p["encoder.conv_out.b"], kh=3, kw=3, pad=1)
-        return ops.conv(h, p["quant_conv.w"], p["quant_conv.b"])
+        h = ops.groupnorm(h, *_norm(p, "encoder.conv_norm_out", cfg["groups"], 1e-6, SILU))
+        h = ops.conv(h, *_wb(p, "encoder.conv_out"), kh=3, kw=3, pad=1)
+        return ops.conv(h, *_wb(p, "quant_conv"))
 
 
 class CLIPText:
@@ -945,17 +1002,7 @@ class CLIPText:
         p["pos"] = sd[e + ".position_embedding.weight"].to(dev, dtype).contiguous()
         for i in range(cfg["layers"]):
             lp = f"text_model.encoder.layers.{i}"
-            a = lp + ".self_attn"
-            p[a + ".qk.w"] = torch.cat([sd[a + ".q_proj.weight"], sd[a + ".k_proj.weight"]], 0).contiguous().to(dev, dtype)
-            p[a + ".qk.b"] = _f32(torch.cat([sd[a + ".q_proj.bias"], sd[a + ".k_proj.bias"]]), dev)
-            p[a + ".v.w"] = sd[a + ".v_proj.weight"].contiguous().to(dev, dtype)
-            wo = sd[a + ".out_proj.weight"]
-            p[a + ".o.w"] = wo.contiguous().to(dev, dtype)
-            p[a + ".o.b"] = _f32(sd[a + ".out_proj.bias"] + wo @ sd[a + ".v_proj.bias"], dev)
-            pk.norm(lp + ".layer_norm1")
-            pk.norm(lp + ".layer_norm2")
-            pk.linear(lp + ".mlp.fc1")
-            pk.linear(lp + ".mlp.fc2")
+            pk.encoder_layer(lp, lp + ".self_attn", "out_proj")
         pk.norm("text_model.final_layer_norm")
         if "text_projection.weight" in sd:      # CLIPTextModelWithProjection (SDXL text_encoder_2)
             p["text_projection.w"] = sd["text_projection.weight"].contiguous().to(dev, dtype)
@@ -978,27 +1025,18 @@ class CLIPText:
             x = ops.embed_tokens(ids, p["tok"], p["pos"], n).view(b, n, c)
         else:
             x = ops.embed_tokens_ctx(ids, ctx.to(self.dtype), ctx_begin, p["tok"], p["pos"])
-            n = x.shape[1]
         for i in range(n_run):
             if i == cfg["layers"] - 1:
                 hidden2 = x
             lp = f"text_model.encoder.layers.{i}"
-            a = lp + ".self_attn"
-            h = ops.layernorm(x, p[lp + ".layer_norm1.g"], p[lp + ".layer_norm1.b"])
-            qk = ops.linear(h, p[a + ".qk.w"], p[a + ".qk.b"])
-            vt = project_vt(h, p[a + ".v.w"], n)
-            o = attention_core(qk[:, :, :c], qk[:, :, c:], vt, cfg["heads"], n, n, causal=True)
-            x = ops.linear(o, p[a + ".o.w"], p[a + ".o.b"], residual=x)
-            h = ops.layernorm(x, p[lp + ".layer_norm2.g"], p[lp + ".layer_norm2.b"])
-            h = ops.activation(ops.linear(h, p[lp + ".mlp.fc1.w"], p[lp + ".mlp.fc1.b"]), mlp_act)
-            x = ops.linear(h, p[lp + ".mlp.fc2.w"], p[lp + ".mlp.fc2.b"], residual=x)
+            x = encoder_layer(p, lp, lp + ".self_attn", x, cfg["heads"], mlp_act, causal=True)
         if not penultimate:
-            return ops.layernorm(x, p["text_model.final_layer_norm.g"], p["text_model.final_layer_norm.b"])
+            return ops.layernorm(x, *_norm(p, "text_model.final_layer_norm"))
         if not want_pooled:
             return x, None
         eos = ids.argmax(dim=-1)                                        # index bookkeeping only
         rows = x[torch.arange(b, device=x.device), eos].contiguous()    # gather of the EOS rows (data movement)
-        rows = ops.layernorm(rows, p["text_model.final_layer_norm.g"], p["text_model.final_layer_norm.b"])
+        rows = ops.layernorm(rows, *_norm(p, "text_model.final_layer_norm"))
         return hidden2, ops.linear(rows, p["text_projection.w"])
 
 
@@ -1022,17 +1060,7 @@ class SafetyChecker:
         pk.norm(v + ".pre_layrnorm")
         for i in range(cfg["layers"]):
             lp = f"{v}.encoder.layers.{i}"
-            a = lp + ".self_attn"
-            p[a + ".qk.w"] = torch.cat([sd[a + ".q_proj.weight"], sd[a + ".k_proj.weight"]], 0).contiguous().to(dev, dtype)
-            p[a + ".qk.b"] = _f32(torch.cat([sd[a + ".q_proj.bias"], sd[a + ".k_proj.bias"]]), dev)
-            p[a + ".v.w"] = sd[a + ".v_proj.weight"].contiguous().to(dev, dtype)
-            wo = sd[a + ".out_proj.weight"]
-            p[a + ".o.w"] = wo.contiguous().to(dev, dtype)
-            p[a + ".o.b"] = _f32(sd[a + ".out_proj.bias"] + wo @ sd[a + ".v_proj.bias"], dev)
-            pk.norm(lp + ".layer_norm1")
-            pk.norm(lp + ".layer_norm2")
-            pk.linear(lp + ".mlp.fc1")
-            pk.linear(lp + ".mlp.fc2")
+            pk.encoder_layer(lp, lp + ".self_attn", "out_proj")
         pk.norm(v + ".post_layernorm")
         # projection + similarity stay fp32 (20 thresholds decide on the third decimal)
         p["proj.w"] = sd["visual_projection.weight"].contiguous().to(dev, torch.float32)
@@ -1065,21 +1093,12 @@ class SafetyChecker:
         tok = ops.conv(strips, p[v + ".embeddings.patch_embedding.w"], None, kh=ps, kw=1, stride=1, pad=0,
                        residual=pos.view(b * g, 1, g, w)).view(b, g, g, -1)
         x = torch.cat([p["cls_pos"].expand(b, -1, -1), tok.view(b, g * g, w)], 1).contiguous()
-        n = x.shape[1]
-        x = ops.layernorm(x, p[v + ".pre_layrnorm.g"], p[v + ".pre_layrnorm.b"])
+        x = ops.layernorm(x, *_norm(p, v + ".pre_layrnorm"))
         for i in range(cfg["layers"]):
             lp = f"{v}.encoder.layers.{i}"
-            a = lp + ".self_attn"
-            h = ops.layernorm(x, p[lp + ".layer_norm1.g"], p[lp + ".layer_norm1.b"])
-            qk = ops.linear(h, p[a + ".qk.w"], p[a + ".qk.b"])
-            vt = project_vt(h, p[a + ".v.w"], n)
-            o = attention_core(qk[:, :, :w], qk[:, :, w:], vt, heads, n, n)
-            x = ops.linear(o, p[a + ".o.w"], p[a + ".o.b"], residual=x)
-            h = ops.layernorm(x, p[lp + ".layer_norm2.g"], p[lp + ".layer_norm2.b"])
-            h = ops.activation(ops.linear(h, p[lp + ".mlp.fc1.w"], p[lp + ".mlp.fc1.b"]), ops.ACT_QUICK_GELU)
-            x = ops.linear(h, p[lp + ".mlp.fc2.w"], p[lp + ".mlp.fc2.b"], residual=x)
+            x = encoder_layer(p, lp, lp + ".self_attn", x, heads, ops.ACT_QUICK_GELU)
         cls = x[:, 0].contiguous()
-        pooled = ops.layernorm(cls, p[v + ".post_layernorm.g"], p[v + ".post_layernorm.b"]).float()
+        pooled = ops.layernorm(cls, *_norm(p, v + ".post_layernorm")).float()
         return ops.linear(pooled, p["proj.w"])
 
     def similarity(self, pixels):

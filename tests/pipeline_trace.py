@@ -17,7 +17,8 @@ from saspa_aug_amd import imageproc
 from saspa_aug_amd import ops as real_ops
 from saspa_aug_amd import pipeline as P
 
-_DT = {torch.bfloat16: "bf16", torch.float16: "f16", torch.float32: "f32", torch.uint8: "u8", torch.int32: "i32", torch.int64: "i64"}
+_DT = {torch.bfloat16: "bf16", torch.float16: "f16", torch.float32: "f32", torch.uint8: "u8", torch.int32: "i32", torch.int64: "i64",
+       torch.float64: "f64", torch.float8_e4m3fn: "e4m3", torch.bool: "bool"}       # (the last three: tests/models_trace.py)
 _LOG = [None]                       # the Log of the case that is running (what _T.record_stream writes to)
 
 

@@ -230,6 +230,22 @@ typedef struct SaspaAttnParams {
 #define SASPA_ATTN_V_ROWMAJOR 2
 int saspa_flash_attn_bf16(const SaspaAttnParams* p, void* stream);
 
+/* Fused attention for ONE WIDE head per batch entry (the 512-channel mid-block attention of the VAE):
+ *   out[b][i][:] = sum_j softmax_j(scale * q[b][i][:] . k[b][j][:]) * v[b][j][:]
+ * d is a multiple of 64 with 192 <= d <= 512 (narrower heads: saspa_flash_attn_bf16).  q, k, v and out are row-major [batch][n][ld]
+ * in the library's 16-bit type (`dtype` must be saspa_half_type()), each with its own row pitch (ld*) and batch stride (s*b), in
+ * elements -- so q, k and v may be column slices of one fused Q | K | V buffer.  V is read row-major: no transposed copy, no
+ * workspace.  nq, nk >= 1, otherwise arbitrary; keys >= nk of the last key tile are masked inside the kernel.
+ * Arithmetic: logits, running maximum, running sum and the online-softmax rescale in fp32; scale * log2(e) is applied to the fp32
+ * logit; P is rounded once to the 16-bit type for the PV MFMA; O accumulates in fp32 and is rounded once on store -- the rounding
+ * points of saspa_flash_attn_bf16.  No logit is ever stored in 16 bits, so unscaled dot products beyond 65504 are harmless in fp16.
+ * A batch entry's result does not depend on the batch size or its position in the batch.
+ * Host-side validation, before any launch: null pointer, dtype other than the library's 16-bit type, batch / nq / nk < 1,
+ * batch > 65535, d outside the range above, a pitch shorter than d -> SASPA_EINVAL; pointers not 16-byte aligned, pitches or batch
+ * strides not multiples of 8 -> SASPA_EALIGN. */
+int saspa_attn_wide(int dtype, const void* q, int ldq, long long sqb, const void* k, int ldk, long long skb, const void* v, int ldv,
+                    long long svb, void* out, int ldo, long long sob, int batch, int nq, int nk, int d, float scale, void* stream);
+
 /* row softmax in place over a [rows][ld] matrix (unfused attention path: fp32
  * parity mode and the 512-wide single-head VAE attention): x = softmax(scale*x) over
  * the first n columns; causal: row r of each `rows_per_mat` block only sees cols <= r. */

@@ -18,7 +18,8 @@ SASPA_CONTROLNET (canny | hed; empty or "None": no ControlNet -- what ip2p, the 
 SASPA_LPIPS_MIN / SASPA_LPIPS_MAX (the LPIPS filter's bounds; both or neither), SASPA_CLIP_FILTERING=per_class with
 SASPA_CLIP_FILTERING_DISCOUNT (the per-class CLIP filter; it replaces the model-confidence filter, which it cannot be combined with),
 SASPA_PNG_DEVICE=1 (generated and source PNGs are compressed on the device; off by default), SASPA_FP16=1 with SASPA_FP16_VAE=bf16|x3
-(IEEE fp16 compute for the text tower / UNet / ControlNet / scheduler steps of the SD-1.5 pipelines; off by default)."""
+(IEEE fp16 compute for the text tower / UNet / ControlNet / scheduler steps of the SD-1.5 pipelines; off by default),
+SASPA_XL_VAE=x3|exact|bf16|f16 (sd_xl-turbo only: how the VAE decodes; unset: fp32 storage after upcast_vae(), as the reference)."""
 import os
 import sys
 from pathlib import Path
@@ -95,7 +96,8 @@ if __name__ == "__main__":
                    CLIP_FILTERING_TYPE=CLIP_FILTERING_TYPE, CLIP_FILTERING_DISCOUNT=CLIP_FILTERING_DISCOUNT, BATCH_SIZE=BATCH_SIZE,
                    PRECISION=os.environ.get("SASPA_PRECISION", "bf16"), WEIGHTS_DIR=os.environ.get("SASPA_WEIGHTS_DIR"),
                    PROMPTS_FILE=os.environ.get("SASPA_PROMPTS_FILE"), PNG_DEVICE=os.environ.get("SASPA_PNG_DEVICE", "0") == "1",
-                   FP16=os.environ.get("SASPA_FP16", "0") == "1", FP16_VAE=os.environ.get("SASPA_FP16_VAE", "bf16"))
+                   FP16=os.environ.get("SASPA_FP16", "0") == "1", FP16_VAE=os.environ.get("SASPA_FP16_VAE", "bf16"),
+                   XL_VAE=os.environ.get("SASPA_XL_VAE") or None)
     assert s.DATASET in R.dataset_utils.DATASETS_SUPPORTED
     assert s.BASE_MODEL in R.BASE_MODEL_DICT.keys()
     assert s.NUM_PER_IMAGE > 0

@@ -213,6 +213,20 @@ def rowmajor_v_enabled():
     return os.environ.get("SASPA_ATTN_VROW", "1") != "0"
 
 
+def wide_head(d):
+    """Head widths ops.attn_wide (saspa_attn_wide) takes: the single 512-channel head of the VAE mid block and its kin."""
+    return 192 <= d <= 512 and d % 64 == 0
+
+
+def vae_attn_fused(dtype):
+    """Does a VAE of this dtype run its mid-block attention as the fused wide-head launch?  fp16: always.  bf16: with
+    SASPA_VAE_ATTN=fused (A/B knob, default off).  fp32 storage: never."""
+    mode = os.environ.get("SASPA_VAE_ATTN", "unfused")
+    if mode not in ("unfused", "fused"):
+        raise ValueError(f"SASPA_VAE_ATTN must be 'unfused' or 'fused', got {mode!r}")
+    return dtype == torch.float16 or (dtype == torch.bfloat16 and mode == "fused")
+
+
 def attention_core(q, k, vt, heads, nq, nk, causal=False, prescaled=False, v_rowmajor=False):
     """q: [B,nq,C] view, k: [B,nk,C] view, vt: [B,C,ld] (v_rowmajor: V itself, [B,nk,C] view).  bf16 with head dim <= 160: fused
     flash kernel; otherwise (fp32 parity mode, 512-wide VAE head): scores GEMM -> row softmax
@@ -893,7 +907,22 @@ class VAEDecoder:
     def _pack_mid(self, m):
         self.pk.resnet(m + ".resnets.0")
         self.pk.norm(m + ".attentions.0.group_norm")
-        self.pk.attn(m + ".attentions.0", True, has_bias=True)
+        a = m + ".attentions.0"
+        self.pk.attn(a, True, has_bias=True)
+        c = self.p[a + ".o.w"].shape[0]
+        # The mid block's attention is ONE head as wide as the block (512 channels in the SD / SDXL VAEs).  fp16: always the fused
+        # wide-head launch (ops.attn_wide) -- the unfused path stores the UNSCALED q . k in the 16-bit type, which passes 65504 as
+        # soon as 512-channel activations are a little above 10, and is not offered.  bf16: SASPA_VAE_ATTN=fused (A/B knob, read
+        # when the weights are packed; default off: the launches of the unfused path exactly).  fp32 storage never.
+        self.fused_attn = vae_attn_fused(self.dtype)
+        if self.fused_attn and wide_head(c):
+            # one Q | K | V projection whose column slices are the kernel's operands (V row-major; its bias is in the out bias)
+            p = self.p
+            p[a + ".qkv.w"] = torch.cat([p.pop(a + ".qk.w"), p.pop(a + ".v.w")], 0).contiguous()
+            p[a + ".qkv.b"] = torch.cat([p.pop(a + ".qk.b"), torch.zeros(c, device=self.dev, dtype=torch.float32)]).contiguous()
+        elif self.dtype == torch.float16 and c > 160:
+            raise NotImplementedError(f"fp16 VAE: a {c}-channel mid-block head has no fused attention kernel (saspa_flash_attn: "
+                                      f"d <= 160, saspa_attn_wide: 192 <= d <= 512, d % 64 == 0) and the unfused path overflows")
         self.pk.resnet(m + ".resnets.1")
 
     def resnet(self, pfx, x):
@@ -914,6 +943,11 @@ class VAEDecoder:
         b, hh, ww, c = x.shape
         n = hh * ww
         h = ops.groupnorm(x, *_norm(p, a + ".group_norm", self.cfg["groups"], 1e-6)).view(b, n, c)
+        if (a + ".qkv.w") in p:      # fused wide head (_pack_mid): no [B, 1, n, n] score matrix, no logit rounded to 16 bits
+            qkv = ops.linear(h, *_wb(p, a + ".qkv"))
+            o = torch.empty((b, n, c), device=x.device, dtype=x.dtype)
+            ops.attn_wide(qkv[:, :, :c], qkv[:, :, c:2 * c], qkv[:, :, 2 * c:], o, n, n, c ** -0.5)
+            return ops.linear(o, *_wb(p, a + ".o"), residual=x.view(b, n, c)).view(b, hh, ww, c)
         qk = ops.linear(h, *_wb(p, a + ".qk"))
         vt = project_vt(h, p[a + ".v.w"], n)
         o = attention_core(qk[:, :, :c], qk[:, :, c:], vt, 1, n, n)

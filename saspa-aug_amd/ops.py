@@ -832,6 +832,26 @@ def flash_attn(q, k, vt, out, heads, d, nq, nk, scale, causal=False, prescaled=F
     return out
 
 
+def attn_wide(q, k, v, out, nq, nk, scale):
+    """One wide head per batch entry (192 <= d <= 512, d % 64 == 0: the VAE's 512-channel mid-block attention) in one fused launch:
+    q [B, nq, d], k / v [B, nk, d] and out [B, nq, d] views whose last dim is contiguous -- column slices of one fused Q | K | V
+    buffer as they are; V row-major, no score matrix, no workspace.  bf16 tensors go to the default library, fp16 to the fp16 one;
+    anything the library refuses (other dtypes, other widths, empty operands) raises with its SASPA_E* code, nothing is launched."""
+    _check_dev(q, k, v, out)
+    _same_dtype("attn_wide", q, k=k, v=v, out=out)
+    for name, t in (("q", q), ("k", k), ("v", v), ("out", out)):
+        if t.dim() != 3 or t.stride(2) != 1:
+            raise ValueError(f"attn_wide: {name} must be [B, n, d] with a contiguous last dim, got {tuple(t.shape)} / {t.stride()}")
+    b, d = q.shape[0], q.shape[2]
+    lib = _L(q)
+    _launch("attn_wide", 4.0 * b * nq * nk * d,
+            lambda: _lib.check(lib.saspa_attn_wide(_dt(q), _ptr(q), q.stride(1), q.stride(0), _ptr(k), k.stride(1), k.stride(0),
+                                                   _ptr(v), v.stride(1), v.stride(0), _ptr(out), out.stride(1), out.stride(0),
+                                                   b, int(nq), int(nk), d, float(scale), _stream()), "saspa_attn_wide"),
+            (b, 1, nq, nk, d))
+    return out
+
+
 def softmax_rows(x, n, scale, causal=False, rows_per_mat=1):
     """In-place softmax(scale*x) over the first n columns of [rows, ld]; pad columns zeroed."""
     _check_dev(x)

@@ -322,6 +322,19 @@ class _StepGraph:
         return self.x
 
 
+XL_VAE_MODES = (None, "x3", "exact", "bf16", "f16")
+
+
+def xl_vae_mode(value):
+    """A VAE mode of the SDXL pipelines as `set_vae_mode` / SASPA_XL_VAE / run_aug.Settings.XL_VAE spell it -> one of XL_VAE_MODES
+    (None, "" and "default": today's behaviour, `upcast_vae()` decides); anything else is a ValueError."""
+    if value is None or value in ("", "default", "none", "None"):
+        return None
+    if value not in XL_VAE_MODES:
+        raise ValueError(f"VAE mode must be one of {XL_VAE_MODES[1:]} (or None), got {value!r}")
+    return value
+
+
 class StableDiffusionControlNetPipeline:
     HAS_CONTROLNET = True
     CFG_PREFIX = True                 # _sample() evaluates the CFG-shared encoder prefix once per image (cfg_prefix_enabled)
@@ -342,6 +355,7 @@ class StableDiffusionControlNetPipeline:
         self._neg_cache = {}
         self._fp16 = False                # enable_fp16(): fp16 compute for text tower / UNet / ControlNet / scheduler steps
         self._fp16_vae = "bf16"
+        self.last_nonfinite = None        # SDXL VAE mode "f16": device bool [B], the decoder's output of that image was not finite
 
     # ---- construction -------------------------------------------------------------------
     @classmethod
@@ -473,6 +487,19 @@ class StableDiffusionControlNetPipeline:
     def upcast_vae(self, gemm=None):  # SDXL-only hook the reference calls at run_aug/run_aug.py:224
         return self
 
+    def set_vae_mode(self, mode):
+        """The 16-bit VAE modes belong to the SDXL pipelines, whose reference VAE is madebyollin/sdxl-vae-fp16-fix -- re-trained to
+        stay inside fp16.  The VAE of this family is not that one (the SD-1.5 VAE overflows fp16, which is why enable_fp16() keeps it
+        in bf16 or on fp32 storage): refused, whatever the mode."""
+        mode = xl_vae_mode(mode)
+        raise NotImplementedError(f"set_vae_mode({mode!r}): the VAE of {type(self).__name__} is not the fp16-fix one (the SD-1.5 "
+                                  "VAE overflows fp16); the VAE modes exist for StableDiffusionXLControlNetPipeline, and "
+                                  "enable_fp16(vae=...) chooses between bf16 and x3 here")
+
+    def _nonfinite_guard(self, img):
+        """Per-image non-finite flags of the decoder's output where a mode asks for them (SDXL, VAE mode "f16"); None otherwise."""
+        return None
+
     def run_safety_checker(self, images_u8):
         """device u8 [B,H,W,3] -> (images with flagged ones replaced by black, device int32 flags [B] | None)."""
         if self.safety_checker is None:
@@ -544,6 +571,7 @@ class StableDiffusionControlNetPipeline:
         z = ops.scale(x, 1.0 / self.cfgs["vae"]["scaling_factor"])
         # (fp16 compute, SDXL's upcast_vae(): the hand-off to the bf16 / fp32 VAE; a no-op otherwise)
         img = self.vae.decode(z.to(self.vae.dtype))
+        self.last_nonfinite = self._nonfinite_guard(img)
         out, self.last_nsfw = self.run_safety_checker(ops.act_to_u8(img))
         return (out, x, img) if return_latents else out
 
@@ -954,6 +982,43 @@ class StableDiffusionXLControlNetPipeline(StableDiffusionControlNetPipeline):
         self._vae_fp32 = False
         self._vae_gemm = None
         self._vae_sd = None
+        self._vae_mode = None             # set_vae_mode(); when it was never called, `.to()` takes SASPA_XL_VAE
+        self._vae_mode_set = False
+
+    def set_vae_mode(self, mode):
+        """How the VAE decodes, whatever `upcast_vae()` says.  Before or after `.to()` (after: the decoder is re-packed from the
+        retained VAE state dict).  Never called: the environment's SASPA_XL_VAE, read by `.to()`.
+        None     today's behaviour: the pipeline's dtype until `upcast_vae()`, then fp32 storage with SASPA_F32X3 GEMMs (or exact
+                 fp32 with gemm="exact" / SASPA_VAE_EXACT_FP32=1).
+        "x3" / "exact"   fp32 storage with that GEMM form, with or without `upcast_vae()`.
+        "bf16"   a bf16 VAE; `upcast_vae()` is a no-op.
+        "f16"    an IEEE fp16 VAE on the fp16 build of the kernels, whatever the denoiser's dtype -- what the reference loads
+                 (madebyollin/sdxl-vae-fp16-fix in torch.float16, run_aug/run_aug.py:189).  The mid-block attention runs as the fused
+                 wide-head launch (ops.attn_wide).  `upcast_vae()` is a no-op.  fp16 stores do not clamp, so the decoder's output is
+                 checked per image with torch.isfinite before quantisation: `last_nonfinite` (device bool [B]); run_aug fails
+                 such an item.  That the real checkpoint stays finite through this decoder is NOT verified (it is not available
+                 offline; parity of the fp16 VAE is shown on synthetic weights only) -- hence the guard.
+        The latents are cast at the hand-off in `_decode`; the denoiser and the text towers are untouched."""
+        self._vae_mode, self._vae_mode_set = xl_vae_mode(mode), True
+        if self.vae is not None:
+            self._apply_vae_mode()
+        return self
+
+    def _apply_vae_mode(self):
+        m = self._vae_mode
+        if m in ("x3", "exact") or (m is None and self._vae_fp32):
+            dt, gemm = torch.float32, (m or self._vae_gemm or ("exact" if os.environ.get("SASPA_VAE_EXACT_FP32", "0") == "1" else "x3"))
+        elif m is None:
+            dt, gemm = self._vae_dtype, "exact"
+        else:
+            dt, gemm = (torch.float16 if m == "f16" else torch.bfloat16), "exact"
+        if self.vae.dtype != dt or self.vae.f32_gemm != (gemm if dt == torch.float32 else "exact"):
+            self.vae = models.VAEDecoder(self._vae_sd, self.cfgs["vae"], self.device, dt, f32_gemm=gemm)
+
+    def _nonfinite_guard(self, img):
+        if self._vae_mode != "f16":
+            return None
+        return ~torch.isfinite(img[..., :3]).flatten(1).all(1)
 
     @classmethod
     def from_synthetic(cls, cfgs=SDXL_TURBO, seed=0):
@@ -973,8 +1038,12 @@ class StableDiffusionXLControlNetPipeline(StableDiffusionControlNetPipeline):
 
     def to(self, device, dtype=None):
         self._vae_sd = None if self._state_dicts is None else self._state_dicts["vae"]
+        if not self._vae_mode_set:
+            self._vae_mode = xl_vae_mode(os.environ.get("SASPA_XL_VAE"))
         super().to(device, dtype)
-        if self._vae_fp32:
+        if self._vae_mode is not None:
+            self._apply_vae_mode()
+        elif self._vae_fp32:
             self.upcast_vae(self._vae_gemm)
         return self
 
@@ -987,7 +1056,11 @@ class StableDiffusionXLControlNetPipeline(StableDiffusionControlNetPipeline):
         VAE, not for the last mantissa bits: the decoder's GEMMs default to `SASPA_F32X3` (three bf16 MFMAs per product,
         ~1e-5 relative, well inside the 1e-3 per-pixel bar, several times the fp32 MFMA rate); `gemm="exact"` or
         SASPA_VAE_EXACT_FP32=1 selects the exact fp32 MFMA path.  GroupNorm / softmax / residuals are fp32 either way."""
+        if self._vae_mode in ("bf16", "f16"):        # set_vae_mode / SASPA_XL_VAE: the 16-bit VAE stays
+            return self
         self._vae_fp32 = True
+        if gemm is None and self._vae_mode in ("x3", "exact"):
+            gemm = self._vae_mode
         if gemm is None:
             gemm = "exact" if os.environ.get("SASPA_VAE_EXACT_FP32", "0") == "1" else "x3"
         self._vae_gemm = gemm

@@ -184,6 +184,7 @@ class Settings:
     FP16: bool = False                 # IEEE fp16 compute (pipe.enable_fp16) for the SD-1.5 pipelines with PRECISION "bf16"; off: bf16
     FP16_VAE: str = "bf16"             # with FP16: "bf16" keeps the VAE as it is, "x3" runs it on fp32 storage with SASPA_F32X3 GEMMs
     MAX_BATCHES: int = 0               # > 0: stop this rank after that many batches (rehearsals / diagnostics; the rest stays status 0)
+    XL_VAE: str = None                 # sd_xl-turbo: pipe.set_vae_mode -- None (upcast_vae() decides: fp32 storage) | "x3" | "exact" | "bf16" | "f16"
 
 
 @dataclass
@@ -256,7 +257,7 @@ def read_prompts_from_json(json_file, dataset_name=None, per_class=False):
 # pipeline construction / call (run_aug/run_aug.py:128-279)
 # ------------------------------------------------------------------------------------------
 def init_pipeline(base_model, controlnet, SDEdit, use_compile=False, sampler="ddim", weights_dir=None, cfgs=None,
-                  state_dicts=None):
+                  state_dicts=None, xl_vae=None):
     """(base_model, controlnet, SDEdit) -> pipeline object.  Implemented: sd_v1.5 + canny (the
     SaSPA configuration for planes and the BASELINE metric).  `use_compile` is accepted and
     ignored: the reference's torch.compile(reduce-overhead) has no counterpart, the kernels are
@@ -305,6 +306,10 @@ def init_pipeline(base_model, controlnet, SDEdit, use_compile=False, sampler="dd
             logging.info("no WEIGHTS_DIR given: using architecture-exact SYNTHETIC weights (no checkpoint available offline)")
             pipe = StableDiffusionXLControlNetPipeline.from_synthetic(cfgs, seed=0)
         pipe.scheduler = _scheduler_for(pipe)        # DDIM or UniPC, "trailing" spacing inherited from the sdxl-turbo config
+        if xl_vae is not None:
+            # Settings.XL_VAE: the VAE mode wins over the upcast below ("bf16" / "f16" make it a no-op).  Without it the
+            # pipeline itself reads SASPA_XL_VAE when it is placed on the device.
+            pipe.set_vae_mode(xl_vae)
         pipe.upcast_vae()
         return pipe
     if base_model == "sd_v1.5" and controlnet is None and SDEdit:
@@ -745,23 +750,29 @@ def hip_batch_generator(pipe, s: Settings):
         enc = (ops.png_deflate(out), ops.png_deflate(src)) if s.PNG_DEVICE else None
         ev = torch.cuda.Event()
         ev.record()
-        return out, ctrl, ev, src, subs, enc
+        # SDXL, VAE mode "f16": per-image flags of a non-finite decoder output (device bool [B]); None in every other mode
+        return out, ctrl, ev, src, subs, enc, getattr(pipe, "last_nonfinite", None)
 
     def finish(handle):
         """Device -> host copies of a batch enqueued earlier, on a side stream that waits for THAT batch only: the next
         batch's launch sequence may already be queued behind it on the main stream and keeps the GPU busy meanwhile.
-        -> (images, controls, resized sources, resized subjects | None)."""
-        out, ctrl, ev, src, subs, enc = handle
+        -> (images, controls, resized sources, resized subjects | None), plus the batch's non-finite flags (bool [B]) when the
+        pipeline raised any: they ride the same copies and the same single wait as the images."""
+        out, ctrl, ev, src, subs, enc, bad = handle
+        flags = lambda b: () if b is None else (b.numpy(),)      # noqa: E731
         side.wait_event(ev)
         with torch.cuda.stream(side):
             for t in (out, src) + ((ctrl,) if ctrl is not None else ()) + tuple(subs or ()) + tuple(t for e in enc or () for t in e):
                 t.record_stream(side)
+            if bad is not None:
+                bad.record_stream(side)
             if enc is not None:
                 # streams and sizes instead of the pixels of `out` / `src`; the control maps and subjects stay pixels (Pillow writers)
                 if os.environ.get("SASPA_HOST_BLOCKING", "1") == "0":
                     host = [t.cpu() for e in enc for t in e]
                     c = ctrl.cpu() if ctrl is not None else None
                     sb = [t.cpu() for t in subs] if subs is not None else None
+                    bd = bad.cpu() if bad is not None else None
                 else:
                     def d2h(t):
                         h = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
@@ -770,15 +781,17 @@ def hip_batch_generator(pipe, s: Settings):
                     host = [d2h(t) for e in enc for t in e]
                     c = d2h(ctrl) if ctrl is not None else None
                     sb = [d2h(t) for t in subs] if subs is not None else None
+                    bd = d2h(bad) if bad is not None else None
                     done = torch.cuda.Event()
                     done.record()
                     ops.sleep_wait(done, 0.002)
                 return (_EncodedBatch(host[0].numpy(), host[1].numpy(), out.shape[1:]), (c.numpy() if c is not None else None),
-                        _EncodedBatch(host[2].numpy(), host[3].numpy(), src.shape[1:]), ([t.numpy() for t in sb] if sb is not None else None))
+                        _EncodedBatch(host[2].numpy(), host[3].numpy(), src.shape[1:]), ([t.numpy() for t in sb] if sb is not None else None)) + flags(bd)
             if os.environ.get("SASPA_HOST_BLOCKING", "1") == "0":
                 o, sr = out.cpu(), src.cpu()                    # (a synchronous copy spins on the calling thread until the batch is done)
                 c = ctrl.cpu() if ctrl is not None else None
                 sb = [t.cpu() for t in subs] if subs is not None else None
+                bd = bad.cpu() if bad is not None else None
             else:
                 # asynchronous copies into pinned buffers, then ONE sleeping wait (event query + 1 ms naps, ops.sleep_wait): the thread
                 # gives its core back for the rest of the batch instead of spinning in hipMemcpy / hipEventSynchronize (round 6: host
@@ -790,10 +803,11 @@ def hip_batch_generator(pipe, s: Settings):
                 o, sr = d2h(out), d2h(src)
                 c = d2h(ctrl) if ctrl is not None else None
                 sb = [d2h(t) for t in subs] if subs is not None else None
+                bd = d2h(bad) if bad is not None else None
                 done = torch.cuda.Event()
                 done.record()
                 ops.sleep_wait(done, 0.002)
-        return o.numpy(), (c.numpy() if c is not None else None), sr.numpy(), ([t.numpy() for t in sb] if sb is not None else None)
+        return (o.numpy(), (c.numpy() if c is not None else None), sr.numpy(), ([t.numpy() for t in sb] if sb is not None else None)) + flags(bd)
 
     def run(batch, noises, sources, subjects=None, category=None):
         return finish(enqueue(batch, noises, sources, subjects, category))
@@ -922,7 +936,7 @@ def _main(s: Settings, ds_utils=None, batch_generator=None, dist=None, pipe=None
 
     if batch_generator is None:
         if pipe is None:
-            pipe = init_pipeline(s.BASE_MODEL, s.CONTROLNET, s.SDEDIT, weights_dir=s.WEIGHTS_DIR)
+            pipe = init_pipeline(s.BASE_MODEL, s.CONTROLNET, s.SDEDIT, weights_dir=s.WEIGHTS_DIR, xl_vae=s.XL_VAE)
             if s.FP16 and s.PRECISION != "fp32":
                 pipe.enable_fp16(True, vae=s.FP16_VAE)          # (raises on the BLIP-Diffusion / SDXL pipelines)
             pipe = pipe.to(s.DEVICE, torch.float32 if s.PRECISION == "fp32" else torch.float16)
@@ -964,13 +978,14 @@ def _main(s: Settings, ds_utils=None, batch_generator=None, dist=None, pipe=None
     def drain(entry):
         batch, handle, sources, subjects = entry
         try:
-            images, controls, resized, resized_subjects = batch_generator.finish(handle)
+            # (a generator may append per-item non-finite flags: the SDXL pipeline's fp16 VAE mode, Settings.XL_VAE = "f16")
+            images, controls, resized, resized_subjects, *bad = batch_generator.finish(handle)
         except RuntimeError as e:
             failed(batch, e)
             return False
-        emit(batch, images, controls, resized, resized_subjects if subjects is not None else None)
+        ok = emit(batch, images, controls, resized, resized_subjects if subjects is not None else None, bad[0] if bad else None)
         batch_log.append((batch[0].height, batch[0].width, len(batch), _time.time()))
-        return True
+        return ok
 
     def write(arrs, k, path):
         if isinstance(arrs, _EncodedBatch):                  # PNG_DEVICE: already compressed on the device
@@ -978,7 +993,12 @@ def _main(s: Settings, ds_utils=None, batch_generator=None, dist=None, pipe=None
         else:
             png.submit(arrs[k], path)
 
-    def emit(batch, images, controls, sources, subjects):
+    def emit(batch, images, controls, sources, subjects, nonfinite=None):
+        """Hand a finished batch to the PNG writers.  nonfinite[k] (optional, per item): the decoder's output of item k was not
+        finite -- the item fails like an item of a failed batch (status -1, counted toward the abort rule, its PNG not written);
+        the other items of the batch are unaffected.  -> False when an item failed."""
+        nonlocal num_errors
+        ok = True
         for k, it in enumerate(batch):
             stem40 = it.image_stem[:MAX_FILENAME_LENGTH]
             if first_variant[it.index] == it.order:
@@ -987,8 +1007,15 @@ def _main(s: Settings, ds_utils=None, batch_generator=None, dist=None, pipe=None
                     png.submit(controls[k], f"{output_folder}/{stem40}_control.png")
             if subjects is not None and it.subject_path:     # :453-454 "_subject_{i}.png" (excluded from the JSON by name)
                 png.submit(subjects[k], os.path.join(output_folder, f"{stem40}_subject_{it.i}.png"))
+            if nonfinite is not None and bool(nonfinite[k]):
+                logging.error(f"non-finite decoder output for {it.output_path}: not written")
+                num_errors += 1
+                it.status = -1
+                ok = False
+                continue
             write(images, k, it.output_path)
             it.status = 1
+        return ok
 
     import time as _time
     prof = os.environ.get("SASPA_PROFILE_LOOP") == "1"          # per-batch host timings in the log (diagnostics)
@@ -1005,7 +1032,7 @@ def _main(s: Settings, ds_utils=None, batch_generator=None, dist=None, pipe=None
             if pipelined:
                 handle = batch_generator.enqueue(*args)
             else:
-                images, controls = batch_generator(*args)
+                images, controls, *bad = batch_generator(*args)
             if prof:
                 print(f"[loop] batch {bi}: wait for sources {t1 - t0:.3f} s, enqueue {_time.time() - t1:.3f} s", flush=True)
         except KeyboardInterrupt:
@@ -1030,8 +1057,9 @@ def _main(s: Settings, ds_utils=None, batch_generator=None, dist=None, pipe=None
                     inflight = None
                     break
             inflight = (batch, handle, sources, subjects)
-        else:
-            emit(batch, images, controls, sources, subjects)
+        elif not emit(batch, images, controls, sources, subjects, bad[0] if bad else None) and num_errors > 20:
+            logging.info("Too many errors, stopping generation on this rank")
+            break
     if inflight is not None:
         drain(inflight)
     png.close()

@@ -11,6 +11,45 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'
 import saspa_aug_amd  # noqa: F401
 from saspa_aug_amd import ops
 dev = torch.device('cuda:0')
+if "wide" in sys.argv:
+    # The VAE's mid-block attention: ONE 512-channel head per image, n = 4096 (512^2) and 16384 (1024^2) tokens.  wide = the fused
+    # launch (ops.attn_wide, q / k / v as column slices of one Q | K | V buffer); unfused = models.attention_core's path for heads
+    # wider than 160 (scores GEMM stored in the 16-bit type, row softmax, PV GEMM, V^T given).  Both 16-bit types, rounds interleaved,
+    # HIP events, the shader clock sampled over each arm's timed launches.  usage: python tools/attn_bench.py wide [quick]
+    from bench import ClockSampler
+    from saspa_aug_amd import models
+    D = 512
+    for (B, N) in ([(1, 4096)] if "quick" in sys.argv else [(8, 4096), (1, 4096), (2, 16384), (1, 16384)]):
+        for dt in (torch.bfloat16, torch.float16):
+            qkv = (0.5 * torch.randn(B, N, 3 * D, device=dev)).to(dt)
+            q, k, v = qkv[:, :, :D], qkv[:, :, D:2 * D], qkv[:, :, 2 * D:]
+            vt = v.transpose(1, 2).contiguous()
+            out = torch.empty(B, N, D, device=dev, dtype=dt)
+            arms = {"wide": lambda: ops.attn_wide(q, k, v, out, N, N, D ** -0.5), "unfused": lambda: models.attention_core(q, k, vt, 1, N, N)}
+            times, clocks, res = {a: [] for a in arms}, {a: [] for a in arms}, {}
+            rep = 3 if N > 4096 else 10
+            for rnd in range(4):
+                for name, fn in arms.items():
+                    if not rnd:
+                        res[name] = fn().float().clone()
+                        continue
+                    cs = ClockSampler(dev, period=0.005).start()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(rep):
+                        fn()
+                    e1.record(); torch.cuda.synchronize()
+                    c = cs.stop()
+                    times[name].append(e0.elapsed_time(e1) * 1000 / rep)
+                    clocks[name].append(c["sclk_mhz_median"] if c else float("nan"))
+            fl = 4.0 * B * N * N * D
+            med = {a: sorted(t)[len(t) // 2] for a, t in times.items()}
+            line = "  ".join(f"{a} {med[a]:9.1f} us {fl / med[a] / 1e6:6.1f} TF/s (sclk {sorted(clocks[a])[len(clocks[a]) // 2]:.0f} MHz)" for a in arms)
+            print(f"{str(dt).replace('torch.', '')} B={B} n={N} d={D}: {line}  unfused / wide {med['unfused'] / med['wide']:.2f}  "
+                  f"max |wide - unfused| {(res['wide'] - res['unfused']).abs().max().item():.3e}", flush=True)
+            del qkv, vt, out, res
+            torch.cuda.empty_cache()
+    sys.exit(0)
 shapes = [(16, 8, 4096, 4096, 40), (16, 8, 1024, 1024, 80), (16, 8, 256, 256, 160), (16, 8, 4096, 77, 40), (16, 8, 1024, 77, 80),
           (8, 10, 1024, 1024, 64), (8, 20, 256, 256, 64), (8, 10, 4096, 4096, 64), (8, 10, 1024, 77, 64)]
 if "quick" in sys.argv:

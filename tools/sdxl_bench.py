@@ -1,7 +1,10 @@
 """BASELINE.json configs[4] timing (parity-test configuration, not the bench line): SDXL-Turbo + Canny ControlNet at
 full width, synthetic weights, bf16 denoiser + fp32-upcast VAE (run_aug/run_aug.py:224).  Two operating points:
 the reference's own (512x512, 2 DDIM steps, no CFG, run_aug/run_aug.py:564-571) and the BASELINE stretch shape
-(1024x1024, 4 steps).  usage: python tools/sdxl_bench.py [batch] [--bf16-vae | --exact-vae] [--fp8 [--fp8-conv] [--fp8-ff-mx]]
+(1024x1024, 4 steps).  usage: python tools/sdxl_bench.py [batch] [--bf16-vae | --exact-vae | --vae MODE[,MODE...]] [--fp8 [--fp8-conv] [--fp8-ff-mx]]
+--vae MODE: the VAE mode (pipeline.set_vae_mode: x3 | exact | bf16 | f16).  Several modes: ONE pipeline, the modes alternating
+round by round at each operating point (same box, same session, same thermal history), one JSON line per (operating point, mode)
+with the median of the rounds and the shader clock sampled during that mode's timed runs; the fp8 share is not recorded then.
 --fp8-conv: the resnet 3x3 convs on MX-fp8 tiles too (pipeline.enable_fp8(convs=True)).
 --fp8-ff-mx: the calibration-free feed-forward (pipeline.enable_fp8(ff="mx")) instead of the calibrated tensor scale."""
 import json, os, sys, time
@@ -17,6 +20,9 @@ t0 = time.time()
 pipe = StableDiffusionXLControlNetPipeline.from_synthetic(CFG.SDXL_TURBO, 0)
 if "--fp8" in sys.argv:
     pipe.enable_fp8(convs="--fp8-conv" in sys.argv, ff="mx" if "--fp8-ff-mx" in sys.argv else "calibrated")
+vae_modes = sys.argv[sys.argv.index("--vae") + 1].split(",") if "--vae" in sys.argv else None
+if vae_modes:
+    pipe.set_vae_mode(vae_modes[0])
 if "--bf16-vae" not in sys.argv:
     pipe.upcast_vae("exact" if "--exact-vae" in sys.argv else None)      # default: fp32 storage, SASPA_F32X3 GEMMs
 pipe = pipe.to(dev, torch.bfloat16)
@@ -29,6 +35,35 @@ for res, steps in ((512, 2), (1024, 4)):
     def once():
         ctrl = ops.canny(imgs, 120, 200)
         return pipe.generate_batch(ids, None, ctrl, lat, steps, 0.0, 0.75)
+
+    if vae_modes:
+        from bench import ClockSampler
+        rounds, per = 3, 2
+        rec = {m: dict(t=[], tv=[], clk=[], finite=True) for m in vae_modes}
+        z32 = torch.randn((b, res // 8, res // 8, 8), device=dev)
+        for rnd in range(rounds + 1):                        # round 0 warms every mode up (graph capture, allocator)
+            for m in vae_modes:
+                pipe.set_vae_mode(m)
+                out = once(); torch.cuda.synchronize()
+                if not rnd:
+                    continue
+                cs = ClockSampler(dev, period=0.05).start()
+                t1 = time.time()
+                for _ in range(per): out = once()
+                torch.cuda.synchronize(); rec[m]["t"].append((time.time() - t1) / per)
+                c = cs.stop()
+                z = z32.to(pipe.vae.dtype); torch.cuda.synchronize(); t2 = time.time()
+                img = pipe.vae.decode(z); torch.cuda.synchronize(); rec[m]["tv"].append(time.time() - t2)
+                rec[m]["clk"].append(c["sclk_mhz_median"] if c else float("nan"))
+                rec[m]["finite"] &= bool(img.float().isfinite().all()) and (pipe.last_nonfinite is None or not bool(pipe.last_nonfinite.any()))
+        for m, r in rec.items():
+            med = lambda v: sorted(v)[len(v) // 2]   # noqa: E731
+            print(json.dumps({"workload": f"SDXL-Turbo + Canny ControlNet, batch={b} {res}x{res}, {steps} DDIM steps, no CFG, ctrl-scale 0.75",
+                              "vae_mode": m, "s_per_batch": round(med(r["t"]), 4), "images_per_s": round(b / med(r["t"]), 3),
+                              "vae_decode_s_per_batch": round(med(r["tv"]), 4), "rounds_s_per_batch": [round(v, 4) for v in r["t"]],
+                              "rounds_vae_decode_s": [round(v, 4) for v in r["tv"]], "sclk_mhz_median_per_round": r["clk"],
+                              "finite": r["finite"], "modes_alternating": vae_modes, "data": "synthetic"}), flush=True)
+        continue
 
     out = once(); torch.cuda.synchronize()
     n = 3

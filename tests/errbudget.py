@@ -50,6 +50,27 @@ LIMITS = {
     # zero: max 2.0, rms 0.82 .. 0.93 and bias -0.70 .. -0.78 (mean of -binade bottom / |ref| = -ln 2 on log-uniform values): max
     # and rms cannot hold both margins, the bias does (ratio >= 8).  The scale applied twice: every statistic above 6.
     "e4m3": dict(max=2.2, rms=1.2, bias=0.05, slope=0.05),
+    # the ResnetBlock2D path (tests/resnet_ref.py), measured over test_errbudget.SEEDS.
+    # "gnstat": the (sum, sum of squares) a producer's epilogue leaves per (128-row block, unit), in units of 2^-24 of sum |v| /
+    # sum v^2.  The kernels' orders (fdot2 pairs, 8 / 16 / 32 row groups): max 2.6 .. 5.8, rms 0.90 .. 1.65, |bias| <= 1.06, |slope|
+    # <= 2.2; ONE fp32 accumulator walking all 1280 values in order, the coarsest order a right kernel could take: max 64 .. 80, rms
+    # 27.6 .. 37.9, bias 19 .. 26.4, slope 36 .. 52 -- it sets the limits.  Weakest mutant, the sums of the unrounded fp32
+    # accumulators: max 6.6e3 .. 1.1e4, rms 1.9e3 .. 2.4e3 (bias and slope inside their noise: max and rms carry it, ratio >= 23);
+    # a row left out, a unit's columns shifted, sums taken before the residual: every statistic above 1e4.
+    "gnstat": dict(max=180.0, rms=80.0, bias=56.0, slope=110.0),
+    # "gn_chain": conv -> bf16 -> GroupNorm -> SiLU with every rounding point in the reference, the output's included (as
+    # "xattn" / "ff": a right result differs by rare one-ulp flips).  Legit: max <= 0.21 (0.34 .. 0.59 for ONE output flip, worst
+    # placed: it sets max), rms <= 7.8e-4 (1.7e-3 for the one flip), |bias| <= 5e-6, |slope| <= 9e-4.  The intermediate kept in fp32 /
+    # alpha after the rounding: max 0.26 .. 0.62 and bias / slope inside their noise -- the rms carries them, 0.021 .. 0.042 (ratio
+    # >= 3.4); n-1 variance (n = 1280 / 1760): rms 0.015 .. 0.019, slope 0.075 .. 0.115; tail items left out: rms 0.26 .. 4.4; eps x 10
+    # (low variance): rms 4.5; the row vector of image b - 1: rms 3.5 .. 10.
+    "gn_chain": dict(max=1.2, rms=0.006, bias=0.0005, slope=0.02),
+    # "conv_gn": GroupNorm -> SiLU -> bf16 -> 3x3 conv, the output rounding measured.  Legit: max 0.05 .. 0.21, rms 0.006 .. 0.0202,
+    # |bias| <= 1.4e-4, |slope| <= 0.0069 (both inside 4 standard errors).  n-1 variance (n = 512): max 0.33 .. 0.44, rms 0.028 -- the
+    # bias carries it, 1.4e-3 .. 1.6e-3 at a standard error of 5e-5 (ratio >= 2.5), the slope (0.044 .. 0.050) holds 2.0; the
+    # normalised input truncated: max 0.07 .. 0.44, carried by bias 4e-3 .. 1.1e-2 and slope 0.21 .. 0.49; padding before the
+    # normalisation, the previous chunk's affine, un-SiLU'd halo rows, the first group's statistics, eps x 10: max 2.1 .. 11.9.
+    "conv_gn": dict(max=0.45, rms=0.045, bias=0.00015, slope=0.007),
 }
 STATS = ("max", "rms", "bias", "slope")
 Z_NOISE = 8.0           # standard errors of bias / slope granted on top of the systematic limit (8 sigma: never by chance)
@@ -193,6 +214,14 @@ def chain_gemm_scale(a, b, bias=None, *, prev=None, residual=None):
     if residual is not None:
         s = s + _abs64(residual)
     return _floor(s)
+
+
+def chain_norm_scale(xhat, gamma, beta, prev, rstd, mu_rstd=None):
+    """out = act(gamma xhat + beta) with xhat = (y - mean) rstd and y an intermediate of per-element scale `prev` (a conv output
+    rounded to the storage type: conv_scale): norm_scale's own terms + prev pushed through |gamma rstd| (rstd broadcastable to
+    xhat).  A flipped y also moves its group's mean and variance, by 1 / n of that: inside the margin.  SiLU after the affine has a
+    slope of at most 1.1 and is absorbed as gemm_scale documents."""
+    return _floor(norm_scale(xhat, gamma, beta, mu_rstd) + prev.double() * (gamma.double() * rstd.double()).abs())
 
 
 def chain_attn_scale(p, v, o, k, prev_q, *, logit_unit=math.log(2.0)):

@@ -228,6 +228,23 @@ typedef struct SaspaAttnParams {
  * a fused Q | K | V projection as they are; the kernel transposes on the way from LDS to the MFMA (ds_read_b64_tr_b16), so
  * no transposed value projection is launched (BasicTransformerBlock.attn1 at the 32x32 / 16x16 levels). */
 #define SASPA_ATTN_V_ROWMAJOR 2
+/* Which loop saspa_flash_attn_bf16 would run `p` on and in which form: its validation, its knobs (SASPA_ATTN_MODE / _V4 / _RING, read
+ * per call as the launch reads them) and its launch plan (saspa_attn.hip: plan_attn), nothing launched, `stream` not needed.  Returns
+ * SASPA_ATTN_LOOP_* in bits 0-3, ORed with the SASPA_ATTN_PLAN_* bits and (ablation id << SASPA_ATTN_PLAN_ABL_SHIFT; 0 in the shipped
+ * library) -- one value per kernel instantiation -- or the SASPA_E* code saspa_flash_attn_bf16 would return.  Measurement and test aid:
+ * a test that means one loop asserts it before it runs, tests/golden/attn_dispatch.json records the rule decision for decision. */
+#define SASPA_ATTN_LOOP_V1 1          /* running-maximum loop, 4 waves x 32 queries (flash_attn_kernel) */
+#define SASPA_ATTN_LOOP_V2 2          /* prescaled queries, reference level, 4 waves (flash_attn_v2_kernel) */
+#define SASPA_ATTN_LOOP_V3 3          /* v2's arithmetic software-pipelined, 8 waves x 32 queries (flash_attn_v3_kernel) */
+#define SASPA_ATTN_LOOP_V4 4          /* 8 waves x 64 queries, 32-key half steps, d = 40 (flash_attn_v4_kernel) */
+#define SASPA_ATTN_LOOP_MASK 15
+#define SASPA_ATTN_PLAN_KEYS128 16    /* 128-key K / V tiles (64 otherwise) */
+#define SASPA_ATTN_PLAN_DB 32         /* v2: two LDS buffers, one barrier per tile */
+#define SASPA_ATTN_PLAN_RING6 64      /* v3: six ring slots, one barrier per two steps (four otherwise) */
+#define SASPA_ATTN_PLAN_VROW 128      /* the kernel reads V row-major (SASPA_ATTN_V_ROWMAJOR) */
+#define SASPA_ATTN_PLAN_ONES 256      /* the softmax denominator accumulates in the spare ones row of V^T (D < padded head dim) */
+#define SASPA_ATTN_PLAN_ABL_SHIFT 12
+int saspa_flash_attn_which(const SaspaAttnParams* p);
 int saspa_flash_attn_bf16(const SaspaAttnParams* p, void* stream);
 
 /* Fused attention for ONE WIDE head per batch entry (the 512-channel mid-block attention of the VAE):

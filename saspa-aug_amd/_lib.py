@@ -121,6 +121,7 @@ SYMBOLS = {
     "saspa_ff_block": (_I, [C.POINTER(FfBlockParams), _P]),
     "saspa_ff_block_eligible": (_I, [C.POINTER(FfBlockParams)]),
     "saspa_flash_attn_bf16": (_I, [C.POINTER(AttnParams), _P]),
+    "saspa_flash_attn_which": (_I, [C.POINTER(AttnParams)]),
     "saspa_softmax_rows": (_I, [_I, _P, _LL, _I, _I, _F, _I, _I, _P]),
     "saspa_attn_wide": (_I, [_I, _P, _I, _LL, _P, _I, _LL, _P, _I, _LL, _P, _I, _LL, _I, _I, _I, _I, _F, _P]),
     "saspa_groupnorm_stats": (_I, [C.POINTER(GroupNormParams), _P]),
@@ -188,7 +189,7 @@ SYMBOLS = {
 F16_SYMBOL_NAMES = (
     "saspa_gemm", "saspa_gemm_suggest_ksplit", "saspa_gemm_as_eligible", "saspa_gemm_as_auto", "saspa_gemm_which",
     "saspa_ff_block", "saspa_ff_block_eligible", "saspa_xattn_block", "saspa_xattn_block_bcast", "saspa_flash_attn_bf16",
-    "saspa_softmax_rows", "saspa_attn_wide",
+    "saspa_flash_attn_which", "saspa_softmax_rows", "saspa_attn_wide",
     "saspa_groupnorm_stats", "saspa_groupnorm_apply", "saspa_groupnorm_onepass_eligible", "saspa_groupnorm_onepass",
     "saspa_splitk_groupnorm_eligible", "saspa_splitk_groupnorm", "saspa_layernorm", "saspa_geglu", "saspa_activation",
     "saspa_embed_tokens", "saspa_embed_tokens_ctx", "saspa_cfg_plms_step", "saspa_cfg_plms_step_dev", "saspa_cfg_ddim_step",

@@ -1,7 +1,12 @@
 // Fused flash attention (bf16, fp32 accumulate) for gfx950 and the row-softmax used
 // by the unfused (fp32 parity / VAE 512-wide head) path.  See include/saspa_hip.h.
 //
-// Formulation (per wave: 32 queries, per workgroup: 4 waves = 128 queries, KV tile = 64 or 128 keys):
+// Four loops share the formulation below: v1 (flash_attn_kernel: running maximum, the only loop for queries that carry no scale,
+// for fewer than 512 keys and for d > 96), v2 (prescaled queries against a reference level, no per-score multiply / max),
+// v3 (v2's arithmetic software-pipelined inside the wave, 8 waves = 256 queries per workgroup) and v4 (64 queries per wave, d = 40).
+// Which one runs a problem, on which tile and ring, is decided in one place -- plan_attn, near the end of the file -- and can be
+// asked without launching: saspa_flash_attn_which.
+// Formulation (v1; per wave: 32 queries, per workgroup: 4 waves = 128 queries, KV tile = 64 or 128 keys):
 //   S^T = K Q^T     v_mfma_f32_32x32x16_bf16, A = K rows (LDS), B = Q rows (registers).
 //                   The accumulator then has the QUERY on the lane (column) and 16 of the
 //                   32 keys in registers, so the softmax max / sum are in-register plus one
@@ -1377,110 +1382,168 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_attn_v4_kernel(const SaspaAt
   }
 }
 
-template <int KS, int NB>
-int launch_attn(const SaspaAttnParams& p0, hipStream_t s) {
-  SaspaAttnParams p = p0;
-  dim3 grid((p.nq + 127) / 128, p.heads, p.batch);
-  // 128-key tiles for the long self-attention sequences at head dims <= 96 (register budget);
-  // 64-key tiles otherwise (cross-attention has 77 keys, d = 160 needs the registers for O^T)
-  constexpr bool BIG_OK = KS <= 6;
-  const bool big = BIG_OK && p.nk >= 512;
-  // A/B knob (diagnostics; read per launch so that tools/attn_bench.py can flip it inside one process): SASPA_ATTN_MODE
-  //   unset: the dispatch rule below.  0: prescaled queries through the v1 loop (c = 1).  1 / 2: v2 with one LDS buffer /
-  //   with two buffers and one barrier per tile.  3 / 4: the software-pipelined v3 loop (8 waves = 256 queries per workgroup).
-  const char* me = getenv("SASPA_ATTN_MODE");
-  int mode = me ? atoi(me) : -1;
-  const bool rm = (p.flags & SASPA_ATTN_V_ROWMAJOR) != 0;
-  if (p.flags & SASPA_ATTN_QPRESCALED) {
-    // v2 / v3 keep S' and the packed P live together, which fits two waves per SIMD up to d = 96 (v3 at d = 96 only with
-    // the spare ones row); wider heads (SD-1.5's 16x16 / 8x8 levels, d = 160) and short key sequences (cross-attention:
-    // 77 keys = two tiles, the first of which always takes the slow path; 40 vs 44 us at level 0) run the v1 loop.
-    constexpr bool V2_OK = KS <= 6;
-    constexpr bool V3_OK = V2_OK && (KS <= 5 || 32 * NB > 16 * KS);
-    const dim3 grid8((p.nq + 255) / 256, p.heads, p.batch);
-    if (mode < 0) {
-      // measured (tools/attn_bench.py, profiles/r3_attn_bench.txt): the 8-wave v3 loop wins once its 256-query workgroups
-      // still give every CU two of them; below that v2's 128-query workgroups balance better
-      const long long wg8 = (long long)grid8.x * grid8.y * grid8.z;
-      mode = (V3_OK && !p.causal && wg8 >= 512) ? 4 : 2;
-    }
-    if ((mode == 3 || mode == 4) && (!V3_OK || p.causal)) mode = 2;
-    if (rm && mode != 3 && mode != 4) mode = 0;       // row-major V exists on the v1 and v3 loops
-    if (mode == 0 || !V2_OK || !big) {
-      p.scale = 0.6931471805599453f;       // the v1 loop multiplies by log2(e): net factor 1
-    } else if constexpr (V2_OK) {
-      constexpr int KTB = KS <= 3 ? 128 : 64;
-#define SASPA_V2(ONES_, DB_) hipLaunchKernelGGL((flash_attn_v2_kernel<KS, NB, ONES_, KTB, DB_>), grid, dim3(256), 0, s, p)
-      if constexpr (V3_OK) {
-        if (mode >= 3) {
-#ifdef SASPA_GEMM_ABLATION
-          if constexpr (KS == 3 && NB == 2) {
-            const char* ae = getenv("SASPA_ATTN_ABLATE");
-            const int abl = ae ? atoi(ae) : 0;
-#define SASPA_V3A(A_) case A_: hipLaunchKernelGGL((flash_attn_v3_kernel<KS, NB, true, 8, A_>), grid8, dim3(512), 0, s, p); SASPA_CHECK_LAUNCH(); return 0;
-            switch (abl) {
-              SASPA_V3A(1) SASPA_V3A(2) SASPA_V3A(4) SASPA_V3A(8) SASPA_V3A(16) SASPA_V3A(14) SASPA_V3A(13) SASPA_V3A(11) SASPA_V3A(7)
-              default: break;
-            }
-#undef SASPA_V3A
-          }
-#endif
-          // six ring slots / one barrier per two steps: measured (tools/attn_bench.py, ring4 / rm4 columns, profiles/r6_attn_ring.txt)
-          // -0.5 % at (16, 8, 4096, 4096, 40) and -1.5 % at 5 632 keys on the V^T path with the ones row, but +3.7 % at d = 64 without
-          // the ones row and +7.7 % on the row-major-V path (236 against 202 registers) -- the barrier is not what the step waits
-          // for.  Taken where it wins; SASPA_ATTN_RING=4: the four-slot ring everywhere (A/B knob, read per launch)
-          // v4 (64 queries per wave, 32-key half steps, the level in the head dimension's padding): d = 40 with V^T;
-          // SASPA_ATTN_V4=0 keeps v3, =2 takes v4 for every eligible launch (A/B / test knob, read per launch)
-          if constexpr (KS == 3 && NB == 2) {
-            const char* v4e = getenv("SASPA_ATTN_V4");
-            const long long wg16 = (long long)((p.nq + 511) / 512) * p.heads * p.batch;
-            const int v4 = v4e ? atoi(v4e) : 1;          // 0: never, 1: from two workgroups per CU on, 2: whenever the shape allows (tests)
-            if (!rm && p.D == 40 && v4 != 0 && (wg16 >= 512 || v4 == 2)) {
-              hipLaunchKernelGGL((flash_attn_v4_kernel<KS, NB, 8>), dim3((p.nq + 511) / 512, p.heads, p.batch), dim3(512), 0, s, p);
-              SASPA_CHECK_LAUNCH();
-              return 0;
-            }
-          }
-          const char* re = getenv("SASPA_ATTN_RING");
-          if constexpr (KS == 3 && NB == 2) {
-            if (!rm && p.D < 32 * NB && !(re && atoi(re) == 4)) {
-              hipLaunchKernelGGL((flash_attn_v3_kernel<KS, NB, true, 8, 0, false, 6>), grid8, dim3(512), 0, s, p);
-              SASPA_CHECK_LAUNCH();
-              return 0;
-            }
-          }
-          if (rm) {
-            if (p.D < 32 * NB) hipLaunchKernelGGL((flash_attn_v3_kernel<KS, NB, true, 8, 0, true>), grid8, dim3(512), 0, s, p);
-            else hipLaunchKernelGGL((flash_attn_v3_kernel<KS, NB, false, 8, 0, true>), grid8, dim3(512), 0, s, p);
-          } else {
-            if (p.D < 32 * NB) hipLaunchKernelGGL((flash_attn_v3_kernel<KS, NB, true, 8>), grid8, dim3(512), 0, s, p);
-            else hipLaunchKernelGGL((flash_attn_v3_kernel<KS, NB, false, 8>), grid8, dim3(512), 0, s, p);
-          }
-          SASPA_CHECK_LAUNCH();
-          return 0;
-        }
-      }
-      const bool db = mode >= 2;
-      if (p.D < 32 * NB) { if (db) SASPA_V2(true, true); else SASPA_V2(true, false); }
-      else { if (db) SASPA_V2(false, true); else SASPA_V2(false, false); }
-#undef SASPA_V2
-      SASPA_CHECK_LAUNCH();
-      return 0;
-    }
-  }
-  if (rm) {        // (64-key tiles: the row-major tile of 128 keys x 320 bytes would not leave two workgroups per CU at d = 160)
-    if (p.D < 32 * NB) hipLaunchKernelGGL((flash_attn_kernel<KS, NB, true, 64, true>), grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((flash_attn_kernel<KS, NB, false, 64, true>), grid, dim3(256), 0, s, p);
-  } else if (p.D < 32 * NB) {
-    if (big) hipLaunchKernelGGL((flash_attn_kernel<KS, NB, true, BIG_OK ? 128 : 64>), grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((flash_attn_kernel<KS, NB, true, 64>), grid, dim3(256), 0, s, p);
+// ---- the launch plan of saspa_flash_attn_bf16 -------------------------------------------------------------------------------
+// check_attn() validates, attn_pins() reads the knobs, plan_attn() decides loop, tile, ring and grid for a validated problem;
+// saspa_flash_attn_bf16 runs the plan through launch_attn(), saspa_flash_attn_which reports it.  Every rule is written once, in
+// plan_attn; tests/golden/attn_dispatch.json records its decisions.
+
+// Argument validation shared by saspa_flash_attn_bf16 and saspa_flash_attn_which: p = *pp
+int check_attn(const SaspaAttnParams* pp, SaspaAttnParams& p) {
+  if (!pp) return SASPA_EINVAL;
+  p = *pp;
+  if (!p.q || !p.k || !p.vt || !p.o) return SASPA_EINVAL;
+  if (p.batch <= 0 || p.heads <= 0 || p.nq <= 0 || p.nk <= 0 || p.D <= 0) return SASPA_EINVAL;
+  if (p.D % 8 || p.D > 160) return SASPA_ERANGE;
+  if (p.ldq % 8 || p.ldk % 8 || p.ldvt % 8 || p.ldo % 4 || p.sqb % 8 || p.skb % 8 || p.svb % 8 || p.sob % 4) return SASPA_EALIGN;
+  if (!aligned16(p.q) || !aligned16(p.k) || !aligned16(p.vt) || !aligned16(p.o)) return SASPA_EALIGN;
+  if (p.flags & ~(SASPA_ATTN_QPRESCALED | SASPA_ATTN_V_ROWMAJOR)) return SASPA_EINVAL;
+  if (p.flags & SASPA_ATTN_V_ROWMAJOR) {       // vt is V[b][key][heads * D] (row pitch ldvt)
+    if (p.ldvt < p.heads * p.D || (long long)p.nk * p.ldvt * 2 >= (1ll << 31)) return SASPA_ERANGE;
   } else {
-    if (big) hipLaunchKernelGGL((flash_attn_kernel<KS, NB, false, BIG_OK ? 128 : 64>), grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((flash_attn_kernel<KS, NB, false, 64>), grid, dim3(256), 0, s, p);
+    if (p.ldvt < ((p.nk + 7) / 8) * 8 || (long long)p.D * p.ldvt * 2 >= (1ll << 31)) return SASPA_ERANGE;
   }
-  SASPA_CHECK_LAUNCH();
+  if (p.ldq < p.heads * p.D || p.ldk < p.heads * p.D || p.ldo < p.heads * p.D) return SASPA_ERANGE;
+  if ((long long)p.nk * p.ldk * 2 >= (1ll << 31)) return SASPA_ERANGE;
   return 0;
 }
+
+// The four knobs -- A/B and test aids, the only getenv calls of this file -- parsed once PER LAUNCH and never cached: tools/attn_bench.py
+// and the tests flip them inside one process.
+//   SASPA_ATTN_MODE    unset (-1): the rule of plan_attn.  0: prescaled queries through the v1 loop (c = 1).  1 / 2: v2 with one LDS
+//                      buffer / with two buffers and one barrier per tile.  3 / 4: the software-pipelined v3 loop (8 waves = 256
+//                      queries per workgroup).  Only prescaled queries have a choice; a loop closed to the shape gives way (plan_attn).
+//   SASPA_ATTN_V4      1 (default): v4 from two workgroups per CU on.  0: d = 40 stays on v3.  2: v4 for every eligible launch (tests).
+//   SASPA_ATTN_RING    4: v3 on its four-slot ring everywhere (default: six slots where they win).
+//   SASPA_ATTN_ABLATE  `make ABLATION=1` only, 0 in the shipped library: the ABL id of flash_attn_v3_kernel (tools/attn_ablate.py).
+struct AttnPins { int mode, v4, ring, ablate; };
+AttnPins attn_pins() {
+  auto env = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+#ifdef SASPA_GEMM_ABLATION
+  const int ablate = env("SASPA_ATTN_ABLATE", 0);
+#else
+  const int ablate = 0;
+#endif
+  return {env("SASPA_ATTN_MODE", -1), env("SASPA_ATTN_V4", 1), env("SASPA_ATTN_RING", 0), ablate};
+}
+
+// The head-dimension bucket (KS 16-wide steps of the QK^T reduction, NB = ceil(KS / 2) 32-wide blocks of O^T) and what each loop's
+// register budget opens to it; the planner asks at run time, the launcher under `if constexpr`, so that a closed loop is never instantiated.
+constexpr int attn_ks(int d) { return d <= 96 ? (d + 15) / 16 : d <= 128 ? 8 : 10; }
+constexpr int attn_nb(int ks) { return (ks + 1) / 2; }
+// 128-key tiles of the v1 loop at head dims <= 96 (d = 160 needs the registers for O^T)
+constexpr bool attn_big_ok(int ks) { return ks <= 6; }
+// v2 / v3 keep S' and the packed P live together, which fits two waves per SIMD up to d = 96 (v3 at d = 96 only with the spare ones row)
+constexpr bool attn_v2_ok(int ks) { return ks <= 6; }
+constexpr bool attn_v3_ok(int ks, int nb) { return attn_v2_ok(ks) && (ks <= 5 || 32 * nb > 16 * ks); }
+constexpr int attn_v2_keys(int ks) { return ks <= 3 ? 128 : 64; }
+// the d = 40 / 48 bucket alone carries the six-slot ring of v3, v4 and the ablation variants
+constexpr bool attn_d40_bucket(int ks, int nb) { return ks == 3 && nb == 2; }
+constexpr bool attn_ablation_id(int a) { return a == 1 || a == 2 || a == 4 || a == 8 || a == 16 || a == 14 || a == 13 || a == 11 || a == 7; }
+
+struct AttnPlan {
+  int loop, keys;    // SASPA_ATTN_LOOP_V1 .. V4; keys per K / V tile: 64 or 128
+  bool db;           // v2: two LDS buffers, one barrier per tile
+  int ring;          // v3: 4 or 6 ring slots
+  bool rm, ones;     // the kernel reads V row-major; the denominator accumulates in the spare ones row
+  int abl;           // v3 ablation id (0 in the shipped library)
+  int wgq;           // queries per workgroup: 128 (v1, v2), 256 (v3), 512 (v4); the grid is (ceil(nq / wgq), heads, batch)
+  float scale;       // the scale the kernel receives
+};
+// the value saspa_flash_attn_which returns: one per kernel instantiation of a bucket
+constexpr int attn_code(int loop, int keys, bool db, int ring, bool rm, bool ones, int abl) {
+  return loop | (keys == 128 ? SASPA_ATTN_PLAN_KEYS128 : 0) | (db ? SASPA_ATTN_PLAN_DB : 0) | (ring == 6 ? SASPA_ATTN_PLAN_RING6 : 0) |
+         (rm ? SASPA_ATTN_PLAN_VROW : 0) | (ones ? SASPA_ATTN_PLAN_ONES : 0) | (abl << SASPA_ATTN_PLAN_ABL_SHIFT);
+}
+int attn_code(const AttnPlan& g) { return attn_code(g.loop, g.keys, g.db, g.ring, g.rm, g.ones, g.abl); }
+// what the kernels receive: the caller's parameters with the plan's scale
+SaspaAttnParams attn_kernel_args(const SaspaAttnParams& p, const AttnPlan& g) { SaspaAttnParams a = p; a.scale = g.scale; return a; }
+
+constexpr int kAttnLongKeys = 512;         // shorter key sequences always run the v1 loop on 64-key tiles
+constexpr long long kAttnTwoPerCu = 512;   // workgroups that give each of the 256 CUs two
+
+// p: validated by check_attn.  The rules in order; the first that applies decides.
+int plan_attn(const SaspaAttnParams& p, const AttnPins& pins, AttnPlan& g) {
+  const int ks = attn_ks(p.D), nb = attn_nb(ks);
+  const bool rm = (p.flags & SASPA_ATTN_V_ROWMAJOR) != 0, pre = (p.flags & SASPA_ATTN_QPRESCALED) != 0;
+  const bool v3_ok = attn_v3_ok(ks, nb), d40 = attn_d40_bucket(ks, nb);
+  const bool ones = p.D < 32 * nb;      // V^T row D is a spare MFMA row, filled with ones: every loop takes it where it exists
+  // 128-key tiles for the long self-attention sequences at head dims <= 96 (register budget);
+  // 64-key tiles otherwise (cross-attention has 77 keys, d = 160 needs the registers for O^T)
+  const bool big = attn_big_ok(ks) && p.nk >= kAttnLongKeys;
+  auto wgs = [&](int wgq) { return (long long)((p.nq + wgq - 1) / wgq) * p.heads * p.batch; };
+  float scale = p.scale;
+  auto pick = [&](int loop, int wgq, int keys, bool vrow, bool db = false, int ring = 4, int abl = 0) {
+    g = {loop, keys, db, ring, vrow, ones, abl, wgq, scale};
+    return 0;
+  };
+  // the loop of prescaled queries as SASPA_ATTN_MODE numbers them (0: v1, 1 / 2: v2, 3 and up: v3); the others have v1 only
+  int mode = pre ? pins.mode : 0;
+  if (pre) {
+    // measured (tools/attn_bench.py, profiles/r3_attn_bench.txt): the 8-wave v3 loop wins once its 256-query workgroups
+    // still give every CU two of them; below that v2's 128-query workgroups balance better
+    if (mode < 0) mode = (v3_ok && !p.causal && wgs(256) >= kAttnTwoPerCu) ? 4 : 2;
+    if (mode >= 3 && !v3_ok) mode = 2;                           // v3 is closed to the bucket
+    if ((mode == 3 || mode == 4) && p.causal) mode = 2;          // causal launches stay off v3
+    if (rm && mode != 3 && mode != 4) mode = 0;                  // row-major V exists on the v1 and v3 loops
+  }
+  // v1: wider heads (SD-1.5's 16x16 / 8x8 levels, d = 160) and short key sequences (cross-attention: 77 keys = two tiles, the first
+  // of which always takes the slow path; 40 vs 44 us at level 0).  Row-major V on 64-key tiles: the row-major tile of 128 keys x
+  // 320 bytes would not leave two workgroups per CU at d = 160.
+  if (mode == 0 || !attn_v2_ok(ks) || !big) {
+    if (pre) scale = 0.6931471805599453f;                        // the v1 loop multiplies by log2(e): net factor 1
+    return pick(SASPA_ATTN_LOOP_V1, 128, big && !rm ? 128 : 64, rm);
+  }
+  if (mode < 3) return pick(SASPA_ATTN_LOOP_V2, 128, attn_v2_keys(ks), false, mode >= 2);        // (row-major V never gets here)
+  // the ablation variants of v3 exist for V^T with the ones row only; an id takes them without looking at the V layout
+  if (d40 && attn_ablation_id(pins.ablate)) return pick(SASPA_ATTN_LOOP_V3, 256, 64, false, false, 4, pins.ablate);
+  // v4 (64 queries per wave, 32-key half steps, the level in the head dimension's padding): d = 40 with V^T, from two of its
+  // 512-query workgroups per CU on
+  if (d40 && !rm && p.D == 40 && pins.v4 != 0 && (wgs(512) >= kAttnTwoPerCu || pins.v4 == 2)) return pick(SASPA_ATTN_LOOP_V4, 512, 64, false);
+  // six ring slots / one barrier per two steps: measured (tools/attn_bench.py, ring4 / rm4 columns, profiles/r6_attn_ring.txt)
+  // -0.5 % at (16, 8, 4096, 4096, 40) and -1.5 % at 5 632 keys on the V^T path with the ones row, but +3.7 % at d = 64 without
+  // the ones row and +7.7 % on the row-major-V path (236 against 202 registers) -- the barrier is not what the step waits
+  // for.  Taken where it wins.
+  const bool ring6 = d40 && !rm && ones && pins.ring != 4;
+  return pick(SASPA_ATTN_LOOP_V3, 256, 64, rm, false, ring6 ? 6 : 4);
+}
+
+// Runs a plan of bucket (KS, NB): one line per kernel instantiation, keyed by attn_code; no decision is taken here.  A loop closed
+// to the bucket is not instantiated (`if constexpr`) and its codes, which plan_attn never produces for the bucket, end in SASPA_ERANGE.
+#define SASPA_ATTN_LAUNCH(OPEN_, CODE_, NT_, ...) \
+  case (CODE_): if constexpr (OPEN_) { hipLaunchKernelGGL((__VA_ARGS__), grid, dim3(NT_), 0, s, a); SASPA_CHECK_LAUNCH(); return 0; } break;
+template <int KS, int NB>
+int launch_attn(const SaspaAttnParams& p, const AttnPlan& g, hipStream_t s) {
+  static_assert(NB == attn_nb(KS), "the buckets of attn_ks / attn_nb");
+  constexpr bool BIG = attn_big_ok(KS), V2_OK = attn_v2_ok(KS), V3_OK = attn_v3_ok(KS, NB), D40 = attn_d40_bucket(KS, NB);
+  constexpr int K2 = attn_v2_keys(KS);
+  const SaspaAttnParams a = attn_kernel_args(p, g);
+  const dim3 grid((p.nq + g.wgq - 1) / g.wgq, p.heads, p.batch);
+  switch (attn_code(g)) {  //            loop keys  db     ring rm     ones   abl
+    SASPA_ATTN_LAUNCH(true, attn_code(1, 64, false, 4, false, false, 0), 256, flash_attn_kernel<KS, NB, false, 64>)
+    SASPA_ATTN_LAUNCH(true, attn_code(1, 64, false, 4, false, true, 0), 256, flash_attn_kernel<KS, NB, true, 64>)
+    SASPA_ATTN_LAUNCH(true, attn_code(1, 64, false, 4, true, false, 0), 256, flash_attn_kernel<KS, NB, false, 64, true>)
+    SASPA_ATTN_LAUNCH(true, attn_code(1, 64, false, 4, true, true, 0), 256, flash_attn_kernel<KS, NB, true, 64, true>)
+    SASPA_ATTN_LAUNCH(BIG, attn_code(1, 128, false, 4, false, false, 0), 256, flash_attn_kernel<KS, NB, false, 128>)
+    SASPA_ATTN_LAUNCH(BIG, attn_code(1, 128, false, 4, false, true, 0), 256, flash_attn_kernel<KS, NB, true, 128>)
+    SASPA_ATTN_LAUNCH(V2_OK, attn_code(2, K2, false, 4, false, false, 0), 256, flash_attn_v2_kernel<KS, NB, false, K2, false>)
+    SASPA_ATTN_LAUNCH(V2_OK, attn_code(2, K2, false, 4, false, true, 0), 256, flash_attn_v2_kernel<KS, NB, true, K2, false>)
+    SASPA_ATTN_LAUNCH(V2_OK, attn_code(2, K2, true, 4, false, false, 0), 256, flash_attn_v2_kernel<KS, NB, false, K2, true>)
+    SASPA_ATTN_LAUNCH(V2_OK, attn_code(2, K2, true, 4, false, true, 0), 256, flash_attn_v2_kernel<KS, NB, true, K2, true>)
+    SASPA_ATTN_LAUNCH(V3_OK, attn_code(3, 64, false, 4, false, false, 0), 512, flash_attn_v3_kernel<KS, NB, false, 8>)
+    SASPA_ATTN_LAUNCH(V3_OK, attn_code(3, 64, false, 4, false, true, 0), 512, flash_attn_v3_kernel<KS, NB, true, 8>)
+    SASPA_ATTN_LAUNCH(V3_OK, attn_code(3, 64, false, 4, true, false, 0), 512, flash_attn_v3_kernel<KS, NB, false, 8, 0, true>)
+    SASPA_ATTN_LAUNCH(V3_OK, attn_code(3, 64, false, 4, true, true, 0), 512, flash_attn_v3_kernel<KS, NB, true, 8, 0, true>)
+    SASPA_ATTN_LAUNCH(D40, attn_code(3, 64, false, 6, false, true, 0), 512, flash_attn_v3_kernel<KS, NB, true, 8, 0, false, 6>)
+    SASPA_ATTN_LAUNCH(D40, attn_code(4, 64, false, 4, false, true, 0), 512, flash_attn_v4_kernel<KS, NB, 8>)
+#ifdef SASPA_GEMM_ABLATION
+#define SASPA_V3A(A_) SASPA_ATTN_LAUNCH(D40, attn_code(3, 64, false, 4, false, true, A_), 512, flash_attn_v3_kernel<KS, NB, true, 8, A_>)
+    SASPA_V3A(1) SASPA_V3A(2) SASPA_V3A(4) SASPA_V3A(8) SASPA_V3A(16) SASPA_V3A(14) SASPA_V3A(13) SASPA_V3A(11) SASPA_V3A(7)
+#undef SASPA_V3A
+#endif
+  }
+  return SASPA_ERANGE;
+}
+#undef SASPA_ATTN_LAUNCH
 
 // ---- row softmax (unfused path) ----
 template <typename T>
@@ -1511,32 +1574,31 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(T* x, long long rows,
 
 }  // namespace
 
+extern "C" int saspa_flash_attn_which(const SaspaAttnParams* pp) {
+  SaspaAttnParams p;
+  AttnPlan g;
+  int rc = check_attn(pp, p);
+  if (rc == 0) rc = plan_attn(p, attn_pins(), g);
+  return rc ? rc : attn_code(g);
+}
+
 extern "C" int saspa_flash_attn_bf16(const SaspaAttnParams* pp, void* stream) {
-  if (!pp) return SASPA_EINVAL;
-  const SaspaAttnParams& p = *pp;
-  if (!p.q || !p.k || !p.vt || !p.o) return SASPA_EINVAL;
-  if (p.batch <= 0 || p.heads <= 0 || p.nq <= 0 || p.nk <= 0 || p.D <= 0) return SASPA_EINVAL;
-  if (p.D % 8 || p.D > 160) return SASPA_ERANGE;
-  if (p.ldq % 8 || p.ldk % 8 || p.ldvt % 8 || p.ldo % 4 || p.sqb % 8 || p.skb % 8 || p.svb % 8 || p.sob % 4) return SASPA_EALIGN;
-  if (!aligned16(p.q) || !aligned16(p.k) || !aligned16(p.vt) || !aligned16(p.o)) return SASPA_EALIGN;
-  if (p.flags & ~(SASPA_ATTN_QPRESCALED | SASPA_ATTN_V_ROWMAJOR)) return SASPA_EINVAL;
-  if (p.flags & SASPA_ATTN_V_ROWMAJOR) {       // vt is V[b][key][heads * D] (row pitch ldvt)
-    if (p.ldvt < p.heads * p.D || (long long)p.nk * p.ldvt * 2 >= (1ll << 31)) return SASPA_ERANGE;
-  } else {
-    if (p.ldvt < ((p.nk + 7) / 8) * 8 || (long long)p.D * p.ldvt * 2 >= (1ll << 31)) return SASPA_ERANGE;
-  }
-  if (p.ldq < p.heads * p.D || p.ldk < p.heads * p.D || p.ldo < p.heads * p.D) return SASPA_ERANGE;
-  if ((long long)p.nk * p.ldk * 2 >= (1ll << 31)) return SASPA_ERANGE;
+  SaspaAttnParams p;
+  AttnPlan g;
+  int rc = check_attn(pp, p);
+  if (rc == 0) rc = plan_attn(p, attn_pins(), g);
+  if (rc) return rc;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int D = p.D;
-  if (D <= 16) return launch_attn<1, 1>(p, s);
-  if (D <= 32) return launch_attn<2, 1>(p, s);
-  if (D <= 48) return launch_attn<3, 2>(p, s);
-  if (D <= 64) return launch_attn<4, 2>(p, s);
-  if (D <= 80) return launch_attn<5, 3>(p, s);
-  if (D <= 96) return launch_attn<6, 3>(p, s);
-  if (D <= 128) return launch_attn<8, 4>(p, s);
-  return launch_attn<10, 5>(p, s);
+  switch (attn_ks(p.D)) {
+    case 1: return launch_attn<1, 1>(p, g, s);
+    case 2: return launch_attn<2, 1>(p, g, s);
+    case 3: return launch_attn<3, 2>(p, g, s);
+    case 4: return launch_attn<4, 2>(p, g, s);
+    case 5: return launch_attn<5, 3>(p, g, s);
+    case 6: return launch_attn<6, 3>(p, g, s);
+    case 8: return launch_attn<8, 4>(p, g, s);
+    default: return launch_attn<10, 5>(p, g, s);
+  }
 }
 
 extern "C" int saspa_softmax_rows(int dtype, void* x, long long rows, int n, int ld, float scale, int causal,

@@ -808,6 +808,27 @@ def ff_block(x, ln, w1p, b1p, w2f, b2, residual=None, out=None):
     return out
 
 
+def _attn_params(q, k, vt, out, heads, d, nq, nk, scale, causal, prescaled, v_rowmajor):
+    p = _lib.AttnParams()
+    p.q, p.ldq, p.sqb = _ptr(q), q.stride(1), q.stride(0)
+    p.k, p.ldk, p.skb = _ptr(k), k.stride(1), k.stride(0)
+    p.vt, p.ldvt, p.svb = _ptr(vt), vt.stride(1), vt.stride(0)
+    p.o, p.ldo, p.sob = _ptr(out), out.stride(1), out.stride(0)
+    p.batch, p.heads, p.D, p.nq, p.nk = q.shape[0], heads, d, nq, nk
+    p.scale, p.causal, p.flags = float(scale), int(causal), (1 if prescaled else 0) | (2 if v_rowmajor else 0)
+    return p
+
+
+def flash_attn_which(q, k, vt, out, heads, d, nq, nk, causal=False, prescaled=False, v_rowmajor=False):
+    """Which loop `flash_attn` would run these operands on, under the SASPA_ATTN_* knobs as they stand: saspa_flash_attn_which's packed
+    plan (include/saspa_hip.h: loop 1 .. 4 in the low four bits, then the SASPA_ATTN_PLAN_* bits).  Host-side, launches nothing."""
+    p = _attn_params(q, k, vt, out, heads, d, nq, nk, 1.0, causal, prescaled, v_rowmajor)
+    w = int(_L(q).saspa_flash_attn_which(C.byref(p)))
+    if w < 0:
+        _lib.check(w, "saspa_flash_attn_which")
+    return w
+
+
 def flash_attn(q, k, vt, out, heads, d, nq, nk, scale, causal=False, prescaled=False, v_rowmajor=False):
     """q: [B, nq, >=heads*d] view, k: [B, nk, >=heads*d] view, vt: [B, heads*d, ldvt] (keys
     contiguous), out: [B, nq, >=heads*d] view.  bf16 only.  prescaled: q already carries scale * log2(e)
@@ -819,13 +840,7 @@ def flash_attn(q, k, vt, out, heads, d, nq, nk, scale, causal=False, prescaled=F
     lib = _L(q)
     if not is_half(q):
         raise TypeError("flash_attn is the bf16 path; fp32 uses the unfused GEMM+softmax path")
-    p = _lib.AttnParams()
-    p.q, p.ldq, p.sqb = _ptr(q), q.stride(1), q.stride(0)
-    p.k, p.ldk, p.skb = _ptr(k), k.stride(1), k.stride(0)
-    p.vt, p.ldvt, p.svb = _ptr(vt), vt.stride(1), vt.stride(0)
-    p.o, p.ldo, p.sob = _ptr(out), out.stride(1), out.stride(0)
-    p.batch, p.heads, p.D, p.nq, p.nk = q.shape[0], heads, d, nq, nk
-    p.scale, p.causal, p.flags = float(scale), int(causal), (1 if prescaled else 0) | (2 if v_rowmajor else 0)
+    p = _attn_params(q, k, vt, out, heads, d, nq, nk, scale, causal, prescaled, v_rowmajor)
     _launch("flash_attn", 4.0 * q.shape[0] * heads * nq * nk * d,
             lambda: _lib.check(lib.saspa_flash_attn_bf16(C.byref(p), _stream()), "saspa_flash_attn_bf16"),
             (q.shape[0], heads, nq, nk, d))

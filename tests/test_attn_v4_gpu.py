@@ -16,7 +16,8 @@ def dev():
     return torch.device("cuda:0")
 
 
-def _run(dev, qs, kk, vv, heads, d, nq, nk):
+def _run(dev, qs, kk, vv, heads, d, nq, nk, loop):
+    """Runs the prescaled launch after checking that the knobs as they stand put it on `loop` (3: v3, 4: v4)."""
     dtype = torch.bfloat16
     bsz, c = qs.shape[0], heads * d
     ldvt = ops.round8(nk) + 8
@@ -27,12 +28,18 @@ def _run(dev, qs, kk, vv, heads, d, nq, nk):
     qkbuf[:, nk:, c:] = _poison_keys(qs.float(), max(nq, nk) - nk).to(dev, dtype)  # K rows past nk must be masked
     qkbuf[:, :nk, c:] = kk.to(dev, dtype)
     out = torch.zeros(bsz, nq, c, device=dev, dtype=dtype)
+    assert ops.flash_attn_which(qkbuf[:, :nq, :c], qkbuf[:, :nk, c:], vt, out, heads, d, nq, nk, False, prescaled=True) & 15 == loop
     ops.flash_attn(qkbuf[:, :nq, :c], qkbuf[:, :nk, c:], vt, out, heads, d, nq, nk, 123.0, False, prescaled=True)
     return out
 
 
-@pytest.mark.parametrize("bsz,heads,nq,nk", [(2, 2, 1024, 1024), (1, 1, 257, 2048 + 31), (2, 8, 640, 512 + 77), (1, 2, 512, 512),
-                                             (1, 3, 1500, 576), (1, 1, 64, 4096), (2, 1, 700, 1000)])
+V4_CASES = [(2, 2, 1024, 1024), (1, 1, 257, 2048 + 31), (2, 8, 640, 512 + 77), (1, 2, 512, 512), (1, 3, 1500, 576), (1, 1, 64, 4096),
+            (2, 1, 700, 1000)]
+LEVEL_MOVE_SHAPE = (1, 1, 40, 640)       # batch, heads, d, queries = keys
+LEVEL0_SHAPE = (16, 8, 40, 4096)
+
+
+@pytest.mark.parametrize("bsz,heads,nq,nk", V4_CASES)
 def test_v4_vs_reference_and_v3(dev, monkeypatch, bsz, heads, nq, nk):
     d, dtype = 40, torch.bfloat16
     monkeypatch.setenv("SASPA_ATTN_MODE", "4")
@@ -42,11 +49,11 @@ def test_v4_vs_reference_and_v3(dev, monkeypatch, bsz, heads, nq, nk):
     vv = q(_rand(bsz, nk, c, seed=33), dtype)
     ref = _ref_attn(qeff, kk, vv, heads)
     monkeypatch.setenv("SASPA_ATTN_V4", "2")
-    out4 = _run(dev, qs, kk, vv, heads, d, nq, nk)
+    out4 = _run(dev, qs, kk, vv, heads, d, nq, nk, 4)
     assert torch.isfinite(out4).all()
     assert_close(out4.float().cpu(), ref, dtype, what=f"flash v4 nq={nq} nk={nk}")
     monkeypatch.setenv("SASPA_ATTN_V4", "0")
-    out3 = _run(dev, qs, kk, vv, heads, d, nq, nk)
+    out3 = _run(dev, qs, kk, vv, heads, d, nq, nk, 3)
     # same arithmetic up to the level (v4 rounds it to bf16): equal to bf16 rounding of the output
     assert (out4.float() - out3.float()).abs().max().item() <= 2 ** -6 * ref.abs().max().item()
 
@@ -58,7 +65,7 @@ def test_v4_level_moves(dev, monkeypatch, spike, shift):
     monkeypatch.setenv("SASPA_ATTN_MODE", "4")
     monkeypatch.setenv("SASPA_ATTN_V4", "2")
     dtype = torch.bfloat16
-    bsz, heads, d, n = 1, 1, 40, 640
+    bsz, heads, d, n = LEVEL_MOVE_SHAPE
     qq = _rand(bsz, n, d, seed=24)
     kk = _rand(bsz, n, d, seed=25)
     vv = q(_rand(bsz, n, d, seed=26), dtype)
@@ -71,7 +78,7 @@ def test_v4_level_moves(dev, monkeypatch, spike, shift):
     qs, qeff = _prescaled_q(qq, d)
     kk = q(kk, dtype)
     ref = _ref_attn(qeff, kk, vv, heads)
-    out = _run(dev, qs, kk, vv, heads, d, n, n)
+    out = _run(dev, qs, kk, vv, heads, d, n, n, 4)
     assert torch.isfinite(out).all()
     assert_close(out.float().cpu(), ref, dtype, what=f"flash v4 level move spike={spike} shift={shift}")
 
@@ -79,15 +86,15 @@ def test_v4_level_moves(dev, monkeypatch, spike, shift):
 def test_v4_is_the_default_at_the_level0_shape(dev, monkeypatch):
     """(16, 8, 4096, 4096, 40) takes v4 by default and v3 with SASPA_ATTN_V4=0: the two differ in the last bit of some outputs only."""
     monkeypatch.delenv("SASPA_ATTN_MODE", raising=False)
-    d, heads, bsz, n = 40, 8, 16, 4096
+    bsz, heads, d, n = LEVEL0_SHAPE
     g = torch.Generator(device="cpu").manual_seed(5)
     qs = (torch.randn(bsz, n, heads * d, generator=g) * 0.5).to(torch.bfloat16)
     kk = torch.randn(bsz, n, heads * d, generator=g).to(torch.bfloat16)
     vv = torch.randn(bsz, n, heads * d, generator=g).to(torch.bfloat16)
     monkeypatch.delenv("SASPA_ATTN_V4", raising=False)
-    a = _run(dev, qs, kk, vv, heads, d, n, n)
+    a = _run(dev, qs, kk, vv, heads, d, n, n, 4)
     monkeypatch.setenv("SASPA_ATTN_V4", "0")
-    b = _run(dev, qs, kk, vv, heads, d, n, n)
+    b = _run(dev, qs, kk, vv, heads, d, n, n, 3)
     assert torch.isfinite(a).all()
     diff = (a.float() - b.float()).abs().max().item()
     assert 0 < diff <= 2 ** -6 * b.float().abs().max().item() + 1e-3, diff      # (0 would mean the knob selected nothing)

@@ -127,10 +127,10 @@ ATTN_CASES = [(40, 2, 130, 77, False, 1), (64, 3, 77, 77, True, 5), (48, 1, 100,
               (40, 1, 257, 2048 + 31, False, 17), (40, 2, 64, 1, False, 21), (40, 4, 200, 1024, False, 25)]
 
 
-def _flash(dev, qq, kk, vv, heads, d, nq, nk, scale, causal, prescaled, rowmajor):
+def _flash(dev, qq, kk, vv, heads, d, nq, nk, scale, causal, prescaled, rowmajor, loop):
     """Heads-folded [h, n, d] operands -> the kernel's [1, n, h d] layout.  The buffers hold max(nq, nk) + 8 rows: K rows past nk
     are POISONED with a large key along the queries' common direction (an unmasked tail key would dominate its rows) and V rows /
-    V^T columns past nk are NaN."""
+    V^T columns past nk are NaN.  `loop`: the loop (1 .. 4) the knobs as they stand must put the launch on, asserted before it runs."""
     c = heads * d
     nr = max(nq, nk) + 8
     flat = lambda t: t.permute(1, 0, 2).reshape(1, t.shape[1], c).float()  # noqa: E731
@@ -147,6 +147,7 @@ def _flash(dev, qq, kk, vv, heads, d, nq, nk, scale, causal, prescaled, rowmajor
     qkv[:, :nk, 2 * c:] = flat(vv).to(dev, BF)
     out = torch.zeros(1, nq, c, device=dev, dtype=BF)
     v = qkv[:, :nk, 2 * c:] if rowmajor else vt
+    assert ops.flash_attn_which(qkv[:, :nq, :c], qkv[:, :nk, c:2 * c], v, out, heads, d, nq, nk, causal, prescaled, rowmajor) & 15 == loop
     ops.flash_attn(qkv[:, :nq, :c], qkv[:, :nk, c:2 * c], v, out, heads, d, nq, nk, scale, causal, prescaled=prescaled,
                    v_rowmajor=rowmajor)
     return out.cpu().reshape(nq, heads, d).permute(1, 0, 2)
@@ -158,17 +159,39 @@ LOOPS = [("0", "0", False, False), ("1", "0", True, False), ("2", "0", True, Fal
          ("0", "0", False, True), ("4", "0", True, True)]
 
 
+def attn_skip(case, loop):
+    """Why test_flash_attn_budget does not run this (case, loop), or None."""
+    d, nk = case[0], case[3]
+    mode, v4, _, rowmajor = loop
+    if rowmajor and d not in (40, 64, 80):
+        return "row-major V is pinned at the production head dimensions"
+    if v4 == "2" and d != 40:
+        return "v4 serves d = 40 only"
+    if mode in ("1", "2") and nk < 512:
+        return "short sequences take the v1 loop whatever the mode (covered by mode 4)"
+    return None
+
+
+def attn_loop(case, loop):
+    """The loop (1 .. 4) a LOOPS entry puts an ATTN_CASES launch on (d <= 80, no causal mask from 512 keys on): v1 for plain
+    queries and below 512 keys whatever the mode; modes 1 / 2 v2; mode 4 v3, or v4 where SASPA_ATTN_V4=2 and d = 40 with V^T."""
+    d, nk = case[0], case[3]
+    mode, v4, prescaled, rowmajor = loop
+    if not prescaled or nk < 512:
+        return 1
+    if mode in ("1", "2"):
+        return 2
+    return 4 if v4 == "2" and d == 40 and not rowmajor else 3
+
+
 @pytest.mark.parametrize("loop", LOOPS, ids=lambda t: f"mode{t[0]}-v4_{t[1]}-{'pre' if t[2] else 'plain'}-{'vrow' if t[3] else 'vt'}")
 @pytest.mark.parametrize("case", ATTN_CASES, ids=lambda t: f"d{t[0]}h{t[1]}q{t[2]}k{t[3]}{'c' if t[4] else ''}")
 def test_flash_attn_budget(dev, monkeypatch, case, loop):
     d, heads, nq, nk, causal, seed = case
     mode, v4, prescaled, rowmajor = loop
-    if rowmajor and d not in (40, 64, 80):
-        pytest.skip("row-major V is pinned at the production head dimensions")
-    if v4 == "2" and d != 40:
-        pytest.skip("v4 serves d = 40 only")
-    if mode in ("1", "2") and nk < 512:
-        pytest.skip("short sequences take the v1 loop whatever the mode (covered by mode 4)")
+    if attn_skip(case, loop):
+        pytest.skip(attn_skip(case, loop))
+    want = attn_loop(case, loop)
     monkeypatch.setenv("SASPA_ATTN_MODE", mode)
     monkeypatch.setenv("SASPA_ATTN_V4", v4)
     qq, kk, vv = attn_operands(heads, nq, nk, d, seed)
@@ -181,14 +204,14 @@ def test_flash_attn_budget(dev, monkeypatch, case, loop):
     ref, p = _attn_ref(qeff, kk, vv, sc, causal)
     s = attn_scale(p, vv)
     tag = f"flash d={d} h={heads} nq={nq} nk={nk}{' causal' if causal else ''} loop {loop}"
-    got = _flash(dev, qs, kk, vv, heads, d, nq, nk, kscale, causal, prescaled, rowmajor)
+    got = _flash(dev, qs, kk, vv, heads, d, nq, nk, kscale, causal, prescaled, rowmajor, want)
     _check(got, ref, s, "attn", tag)
     if nk > 1 and loop in (LOOPS[0], LOOPS[3]):
         # negative controls: the same launch with nk - 1 keys, and (plain queries) with the scale x (1 + 2^-5)
-        _control(_flash(dev, qs, kk[:, :-1], vv[:, :-1], heads, d, nq, nk - 1, kscale, causal, prescaled, rowmajor), ref, s, "attn",
+        _control(_flash(dev, qs, kk[:, :-1], vv[:, :-1], heads, d, nq, nk - 1, kscale, causal, prescaled, rowmajor, want), ref, s, "attn",
                  f"{tag} with nk - 1")
         if not prescaled:
-            _control(_flash(dev, qs, kk, vv, heads, d, nq, nk, kscale * (1 + 2 ** -5), causal, prescaled, rowmajor), ref, s, "attn",
+            _control(_flash(dev, qs, kk, vv, heads, d, nq, nk, kscale * (1 + 2 ** -5), causal, prescaled, rowmajor, want), ref, s, "attn",
                      f"{tag} with scale x (1 + 2^-5)")
 
 

@@ -274,12 +274,22 @@ def _prescaled_q(qq, d):
     return qs, qs / (d ** -0.5 * 1.4426950408889634)
 
 
-@pytest.mark.parametrize("d,heads,nq,nk,causal", [
+PRESCALED_CASES = [
     (40, 8, 200, 200, False), (80, 4, 300, 300, False), (160, 2, 256, 256, False), (64, 3, 77, 77, True),
     (40, 8, 130, 77, False), (8, 4, 64, 64, False), (16, 2, 33, 200, False), (32, 4, 128, 64, False),
     (40, 2, 1024, 1024, False), (64, 2, 640, 1024, False), (48, 1, 100, 513, False), (80, 2, 300, 1090, False),
-    (40, 1, 257, 2048 + 31, False)])
-@pytest.mark.parametrize("mode", ["1", "2", "4"])
+    (40, 1, 257, 2048 + 31, False)]
+PRESCALED_MODES = ["1", "2", "4"]
+
+
+def prescaled_loop(mode, nk):
+    """The loop (1 .. 4) SASPA_ATTN_MODE `mode` puts a small prescaled launch of these tests on (V^T, d <= 80 from 512 keys on, no
+    causal mask there, too few workgroups for v4): below 512 keys v1 whatever the mode, modes 1 / 2 v2, modes 3 / 4 v3."""
+    return 1 if nk < 512 else 3 if mode in ("3", "4") else 2
+
+
+@pytest.mark.parametrize("d,heads,nq,nk,causal", PRESCALED_CASES)
+@pytest.mark.parametrize("mode", PRESCALED_MODES)
 def test_flash_attn_prescaled(dev, monkeypatch, mode, d, heads, nq, nk, causal):
     """SASPA_ATTN_QPRESCALED (v2 / v3 loops: reference level on the MFMA C operand, OR-bit overflow check; mode 3 = the
     software-pipelined v3 loop).  Sequences below 512 keys take the v1 loop whatever the mode: run those once."""
@@ -299,21 +309,36 @@ def test_flash_attn_prescaled(dev, monkeypatch, mode, d, heads, nq, nk, causal):
     qkbuf[:, :nq, :c] = qs.to(dev, dtype)
     qkbuf[:, :nk, c:] = kk.to(dev, dtype)
     out = torch.zeros(bsz, nq, c, device=dev, dtype=dtype)
+    assert ops.flash_attn_which(qkbuf[:, :nq, :c], qkbuf[:, :nk, c:], vt, out, heads, d, nq, nk, causal, prescaled=True) & 15 \
+        == prescaled_loop(mode, nk)
     ops.flash_attn(qkbuf[:, :nq, :c], qkbuf[:, :nk, c:], vt, out, heads, d, nq, nk, 123.0, causal, prescaled=True)   # scale ignored
     assert_close(out.float().cpu(), ref, dtype, what=f"flash prescaled d={d} nq={nq} nk={nk}")
 
 
-@pytest.mark.parametrize("d,heads,nq,nk,causal", [
+VROW_CASES = [
     (40, 8, 200, 200, False), (80, 4, 300, 300, False), (160, 2, 256, 256, False), (64, 3, 77, 77, True),
     (40, 8, 130, 77, False), (8, 4, 64, 64, False), (16, 2, 33, 200, False), (32, 4, 128, 64, False), (128, 2, 96, 130, False),
-    (40, 8, 1024, 1024, False), (80, 8, 1024, 1024, False), (64, 4, 640, 1090, False), (96, 2, 512, 2048 + 31, False)])
+    (40, 8, 1024, 1024, False), (80, 8, 1024, 1024, False), (64, 4, 640, 1090, False), (96, 2, 512, 2048 + 31, False)]
+VROW_BATCH = 8
+
+
+def vrow_loops(prescaled, nk, d):
+    """(loop of the V^T form, loop of the row-major form) under the mode test_flash_attn_v_rowmajor pins: v1 below 512 keys or
+    without prescaled queries; the 8-wave v3 loop for long prescaled sequences up to d = 80; at d = 96, which v3 does not take, the
+    V^T form falls to v2 and the row-major form, which v2 does not read, to v1."""
+    if not prescaled or nk < 512:
+        return 1, 1
+    return (3, 3) if d <= 80 else (2, 1)
+
+
+@pytest.mark.parametrize("d,heads,nq,nk,causal", VROW_CASES)
 @pytest.mark.parametrize("prescaled", [False, True])
 def test_flash_attn_v_rowmajor(dev, monkeypatch, d, heads, nq, nk, causal, prescaled):
     """SASPA_ATTN_V_ROWMAJOR (ABI 14): V handed over as the V columns of a fused Q | K | V projection, transposed between LDS and the
     MFMA by ds_read_b64_tr_b16 -- the same MFMA operands as the V^T form, so BIT-EQUAL with it on the loop that serves both (v1
     below 512 keys or without prescaled queries; the 8-wave v3 loop for long prescaled sequences, pinned here with mode 4)."""
     dtype = torch.bfloat16
-    bsz, c = 8, heads * d
+    bsz, c = VROW_BATCH, heads * d
     monkeypatch.setenv("SASPA_ATTN_MODE", "4" if prescaled else "0")
     qs, qeff = _prescaled_q(_rand(bsz, nq, c, seed=21), d) if prescaled else (q(_rand(bsz, nq, c, seed=21), dtype),) * 2
     kk = q(_rand(bsz, nk, c, seed=22), dtype)
@@ -329,6 +354,10 @@ def test_flash_attn_v_rowmajor(dev, monkeypatch, d, heads, nq, nk, causal, presc
     vt[:, :, :nk] = vv.transpose(1, 2).to(dev, dtype)
     out_t, out_r = (torch.zeros(bsz, nq, c, device=dev, dtype=dtype) for _ in range(2))
     args = (heads, d, nq, nk, d ** -0.5, causal)
+    which = (ops.flash_attn_which(qkv[:, :nq, :c], qkv[:, :nk, c:2 * c], vt, out_t, heads, d, nq, nk, causal, prescaled) & 15,
+             ops.flash_attn_which(qkv[:, :nq, :c], qkv[:, :nk, c:2 * c], qkv[:, :nk, 2 * c:3 * c], out_r, heads, d, nq, nk, causal, prescaled,
+                                  v_rowmajor=True) & 15)
+    assert which == vrow_loops(prescaled, nk, d)
     ops.flash_attn(qkv[:, :nq, :c], qkv[:, :nk, c:2 * c], vt, out_t, *args, prescaled=prescaled)
     ops.flash_attn(qkv[:, :nq, :c], qkv[:, :nk, c:2 * c], qkv[:, :nk, 2 * c:3 * c], out_r, *args, prescaled=prescaled, v_rowmajor=True)
     assert_close(out_r.float().cpu(), ref, dtype, what=f"flash row-major V d={d} nq={nq} nk={nk}")
@@ -344,7 +373,11 @@ def test_flash_attn_v_rowmajor(dev, monkeypatch, d, heads, nq, nk, causal, presc
                 assert same, (out_r.float() - out_t.float()).abs().max().item()
 
 
-@pytest.mark.parametrize("mode", ["2", "4"])
+LEVEL_MOVE_MODES = ["2", "4"]            # (1, 1, 512, 512, 40): prescaled_loop's v2 and v3
+LEVEL_MOVE_SHAPE = (1, 1, 40, 512)       # batch, heads, d, queries = keys
+
+
+@pytest.mark.parametrize("mode", LEVEL_MOVE_MODES)
 @pytest.mark.parametrize("spike,shift", [(6.0, 0.0), (60.0, 0.0), (1.0, -40.0), (6.0, 25.0)])
 def test_flash_attn_prescaled_level_moves(dev, monkeypatch, mode, spike, shift):
     """The v2 loop only moves its reference level when some p reaches 2.0: force that at a late KV tile (spiked key), with
@@ -352,7 +385,7 @@ def test_flash_attn_prescaled_level_moves(dev, monkeypatch, mode, spike, shift):
     large enough that exp2 of the stale level overflows to inf (60 x)."""
     monkeypatch.setenv("SASPA_ATTN_MODE", mode)
     dtype = torch.bfloat16
-    bsz, heads, d, n = 1, 1, 40, 512
+    bsz, heads, d, n = LEVEL_MOVE_SHAPE
     qq = _rand(bsz, n, d, seed=24)
     kk = _rand(bsz, n, d, seed=25)
     vv = q(_rand(bsz, n, d, seed=26), dtype)
@@ -366,7 +399,9 @@ def test_flash_attn_prescaled_level_moves(dev, monkeypatch, mode, spike, shift):
     ref = _ref_attn(qeff, kk, vv, heads)
     vt = vv.transpose(1, 2).contiguous().to(dev, dtype)
     out = torch.zeros(bsz, n, d, device=dev, dtype=dtype)
-    ops.flash_attn(qs.to(dev, dtype), kk.to(dev, dtype), vt, out, heads, d, n, n, 1.0, prescaled=True)
+    qd, kd = qs.to(dev, dtype), kk.to(dev, dtype)
+    assert ops.flash_attn_which(qd, kd, vt, out, heads, d, n, n, prescaled=True) & 15 == prescaled_loop(mode, n)
+    ops.flash_attn(qd, kd, vt, out, heads, d, n, n, 1.0, prescaled=True)
     assert torch.isfinite(out).all()
     assert_close(out.float().cpu(), ref, dtype, what=f"flash prescaled level move spike={spike} shift={shift}")
 

@@ -283,6 +283,151 @@ def test_gemm_dispatch_table():
     assert not bad, f"{len(bad)} of {len(want)} dispatch decisions changed:\n{msg}"
 
 
+# ---- the flash-attention dispatch table -------------------------------------------------------------------------------------
+# A deterministic corpus of SaspaAttnParams under the SASPA_ATTN_* knobs and, per row, saspa_flash_attn_which (loop | plan bits, or
+# the error code), compared with tests/golden/attn_dispatch.json.  The golden was recorded from the dispatch as it stood BEFORE
+# plan_attn existed (its launch sites made to return the code of the instantiation they launch): plan_attn reproduces it row for row.
+# A deliberate change of a rule rewrites it:  PYTHONPATH=. python tests/test_lib_abi.py --write-attn-dispatch-golden
+ATTN_GOLDEN = os.path.join(ROOT, "tests", "golden", "attn_dispatch.json")
+_PRE, _VROW = 1, 2                                             # SASPA_ATTN_QPRESCALED, SASPA_ATTN_V_ROWMAJOR
+_ATTN_KNOBS = ("SASPA_ATTN_MODE", "SASPA_ATTN_V4", "SASPA_ATTN_RING")
+_ALL_D = list(range(8, 161, 8))
+_CORE_D = [40, 64, 80, 96, 128, 160]
+_PRODUCTION = [(16, 8, 4096, 4096, 40), (16, 8, 1024, 1024, 80), (16, 8, 256, 256, 160),                 # (batch, heads, nq, nk, d)
+               (16, 8, 4096, 77, 40), (16, 8, 1024, 77, 80), (16, 8, 256, 77, 160), (16, 8, 64, 77, 160)]
+# every (loop, plan bits) the dispatch can reach in the shipped libraries: (loop, keys per tile, v2 double buffer, v3 ring slots,
+# row-major V, ones row)
+ATTN_REACHABLE = (
+    [(1, 64, False, 4, rm, ones) for rm in (False, True) for ones in (False, True)]
+    + [(1, 128, False, 4, False, ones) for ones in (False, True)]
+    + [(2, keys, db, 4, False, ones) for keys in (64, 128) for db in (False, True) for ones in (False, True)]
+    + [(3, 64, False, 4, rm, ones) for rm in (False, True) for ones in (False, True)]
+    + [(3, 64, False, 6, False, True), (4, 64, False, 4, False, True)])
+
+
+def _attn_code(loop, keys, db, ring, rm, ones):
+    return loop | (16 if keys == 128 else 0) | (32 if db else 0) | (64 if ring == 6 else 0) | (128 if rm else 0) | (256 if ones else 0)
+
+
+def _attn(b, heads, nq, nk, d, flags=0, causal=0, over=None):
+    """A valid launch over operands that are never dereferenced; `over` then overwrites fields (the invalid rows)."""
+    p = _lib.AttnParams()
+    c = heads * d
+    p.q, p.ldq, p.sqb = _A0, c, nq * c
+    p.k, p.ldk, p.skb = _A1, c, nk * c
+    p.vt, p.ldvt = _W, (c if flags & _VROW else (nk + 7) // 8 * 8)
+    p.svb = (nk if flags & _VROW else c) * p.ldvt
+    p.o, p.ldo, p.sob = _OUT, c, nq * c
+    p.batch, p.heads, p.D, p.nq, p.nk, p.scale, p.causal, p.flags = b, heads, d, nq, nk, d ** -0.5, causal, flags
+    for name, v in (over or {}).items():
+        setattr(p, name, v)
+    return p
+
+
+def _attn_invalid_rows():
+    rows = [("null", None), ("all zero", _lib.AttnParams())]
+
+    def add(what, *shape, **over):
+        rows.append(((what,) + shape, _attn(*shape, flags=over.get("flags", 0), over=over)))
+    base = (2, 8, 1024, 1024, 40)
+    for field in ("q", "k", "vt", "o"):
+        add(f"{field} null", *base, **{field: None})
+        add(f"{field} misaligned", *base, **{field: _A0 + 8})
+    for field in ("batch", "heads", "nq", "nk", "D"):
+        add(f"{field} = 0", *base, **{field: 0})
+    for d in (4, 12, 44, 164, 168, 320):                                       # D % 8, D > 160
+        add("head dim", 2, 8, 1024, 1024, 40, D=d)
+    for field, v in (("ldq", 324), ("ldk", 324), ("ldvt", 1028), ("ldo", 322), ("sqb", 4), ("skb", 4), ("svb", 4), ("sob", 2)):
+        add(f"{field} misaligned", *base, **{field: v})
+    for flags in (4, 8, 7, -1):
+        add("unknown flag bits", *base, flags=flags)
+    for field in ("ldq", "ldk", "ldo"):
+        add(f"{field} short", *base, **{field: 312})
+    add("ldvt short (V^T)", *base, ldvt=1016)
+    add("ldvt short (row-major V)", *base, flags=_VROW, ldvt=312)
+    # the 2 GiB limits of the kernels' 32-bit byte offsets, each alone and from both sides:
+    for ldvt in (6710880, 6710888):                                            # D x ldvt x 2 (V^T rows)
+        add("2 GiB: V^T", 1, 1, 128, 1024, 160, ldvt=ldvt)
+    for nk in (3355440, 3355448):                                              # nk x ldvt x 2 (row-major V)
+        add("2 GiB: row-major V", 1, 2, 128, nk, 80, flags=_VROW, ldvt=320)
+    for nk in (6710880, 6710888):                                              # nk x ldk x 2
+        add("2 GiB: K", 1, 2, 128, nk, 80)
+    return rows
+
+
+def attn_dispatch_corpus():
+    """[(knobs, [(description, SaspaAttnParams)])] in a fixed order: the invalid rows; every head dimension x key count x flags x
+    causal on a small and a large grid; both sides of the workgroup thresholds and the production shapes; the knobs on a core of head
+    dimensions; the pinned modes at every head dimension."""
+    def shapes(ds, nks, grids):
+        return [((b, h, nq, nk, d, fl, ca), _attn(b, h, nq, nk, d, fl, ca)) for d in ds for nk in nks for (b, h, nq) in grids
+                for fl in (0, _PRE, _VROW, _PRE | _VROW) for ca in (0, 1)]
+    small, large = (1, 2, 1024), (16, 8, 1024)                                 # 8 and 512 workgroups of 256 queries
+    groups = [({}, _attn_invalid_rows()), ({}, shapes(_ALL_D, (77, 511, 512, 4096), (small, large)))]
+    # ceil(nq / 256) x heads x batch and ceil(nq / 512) x heads x batch at 511 and 512, by nq and by heads x batch
+    edge = [(1, 1, 256 * 511), (1, 1, 256 * 511 + 1), (1, 1, 512 * 511), (1, 1, 512 * 511 + 1), (7, 73, 256), (8, 64, 256), (8, 64, 257),
+            (7, 73, 512), (8, 64, 512), (16, 8, 768), (16, 8, 769), (16, 8, 1536), (16, 8, 1537), (16, 8, 2048)]
+    groups.append(({}, shapes(_CORE_D + [48], (4096,), edge)))
+    groups.append(({}, [((b, h, nq, nk, d, fl, ca), _attn(b, h, nq, nk, d, fl, ca)) for (b, h, nq, nk, d) in _PRODUCTION
+                        for fl in (0, _PRE, _VROW, _PRE | _VROW) for ca in (0, 1)]))
+    pins = [{"SASPA_ATTN_MODE": m} for m in "01234"]
+    pins += [{"SASPA_ATTN_V4": v, **mode} for v in "02" for mode in ({}, {"SASPA_ATTN_MODE": "4"})]
+    pins += [{"SASPA_ATTN_RING": "4", **mode, **v4} for mode in ({}, {"SASPA_ATTN_MODE": "4"}) for v4 in ({}, {"SASPA_ATTN_V4": "0"})]
+    for knobs in pins:
+        groups.append((knobs, shapes(_CORE_D, (77, 512, 4096), (small, large, (1, 1, 512 * 511 + 1)))))
+    for mode in "14":
+        groups.append(({"SASPA_ATTN_MODE": mode}, shapes(_ALL_D, (4096,), (large,))))
+    return groups
+
+
+def attn_dispatch_table(lib, setenv, delenv):
+    table = []
+    for knobs, rows in attn_dispatch_corpus():
+        for name in _ATTN_KNOBS:
+            if name in knobs:
+                setenv(name, knobs[name])
+            else:
+                delenv(name)
+        table += [lib.saspa_flash_attn_which(None if p is None else C.byref(p)) for _, p in rows]
+    for name in _ATTN_KNOBS:
+        delenv(name)
+    return table
+
+
+def _decode_attn(w):
+    if w < 0:
+        return _lib.ERRORS.get(w, str(w)).split()[0]
+    bits = [name for bit, name in ((16, "128-key tiles"), (32, "double buffer"), (64, "six-slot ring"), (128, "row-major V"), (256, "ones row"))
+            if w & bit]
+    return f"v{w & 15} " + ", ".join(bits + ([f"ablation {w >> 12}"] if w >> 12 else []))
+
+
+def test_attn_dispatch_table(monkeypatch):
+    """The dispatch of saspa_flash_attn_bf16, decision for decision, against the table recorded from the dispatch that preceded
+    plan_attn (no GPU: the dry plan), in the default library and, where it is built, the fp16 one.  On the invalid rows the launch
+    entry itself returns the same code (it returns before it touches a stream)."""
+    with open(ATTN_GOLDEN) as f:
+        want = json.load(f)
+    assert os.path.getsize(ATTN_GOLDEN) < 73848
+    groups = attn_dispatch_corpus()
+    keys = [(knobs, k) for knobs, rows in groups for k, _ in rows]
+    params = [p for _, rows in groups for _, p in rows]
+    assert len(want) == len(keys), (len(want), len(keys))
+    # the golden itself reaches every (loop, plan bits) the dispatch can reach, and nothing else
+    assert {w for w in want if w >= 0} == {_attn_code(*t) for t in ATTN_REACHABLE}, sorted({_decode_attn(w) for w in want if w >= 0})
+    assert {w for w in want if w < 0} == {_lib.SASPA_EINVAL, _lib.SASPA_EALIGN, _lib.SASPA_ERANGE}
+    libs = [("default", _lib.load())] + ([("fp16", _lib.load_f16())] if os.path.exists(_lib.F16_LIB_PATH) else [])
+    for which, lib in libs:
+        got = attn_dispatch_table(lib, monkeypatch.setenv, lambda name: monkeypatch.delenv(name, raising=False))
+        bad = [i for i in range(len(want)) if got[i] != want[i]]
+        msg = "\n".join(f"row {i} knobs {keys[i][0]} (b, heads, nq, nk, d, flags, causal) = {keys[i][1]}:\n  got  {_decode_attn(got[i])}\n"
+                        f"  want {_decode_attn(want[i])}" for i in bad[:8])
+        assert not bad, f"{which} library: {len(bad)} of {len(want)} attention dispatch decisions changed:\n{msg}"
+        for i, p in enumerate(params):
+            if want[i] < 0:
+                assert lib.saspa_flash_attn_bf16(None if p is None else C.byref(p), None) == want[i], keys[i]
+
+
 if __name__ == "__main__":
     import sys
     if sys.argv[1:] == ["--write-dispatch-golden"]:
@@ -290,6 +435,11 @@ if __name__ == "__main__":
         with open(DISPATCH_GOLDEN, "w") as f:
             f.write("[\n" + ",\n".join(json.dumps(r, separators=(",", ":")) for r in rows) + "\n]\n")
         print(f"{DISPATCH_GOLDEN}: {len(rows)} rows")
+    if sys.argv[1:] == ["--write-attn-dispatch-golden"]:
+        rows = attn_dispatch_table(_lib.load(), os.environ.__setitem__, lambda name: os.environ.pop(name, None))
+        with open(ATTN_GOLDEN, "w") as f:
+            f.write("[\n" + ",\n".join(",".join(str(w) for w in rows[i:i + 32]) for i in range(0, len(rows), 32)) + "\n]\n")
+        print(f"{ATTN_GOLDEN}: {len(rows)} rows")
 
 
 def test_ff_block_host_side_validation():

@@ -263,6 +263,23 @@ int saspa_flash_attn_bf16(const SaspaAttnParams* p, void* stream);
 int saspa_attn_wide(int dtype, const void* q, int ldq, long long sqb, const void* k, int ldk, long long skb, const void* v, int ldv,
                     long long svb, void* out, int ldo, long long sob, int batch, int nq, int nk, int d, float scale, void* stream);
 
+/* Flash attention on fp32 STORAGE with x3 products (the fused form of the fp32 parity path; default library only):
+ *   o[b][i][h*D+d] = sum_j softmax_j(scale * q[b][i][h,:] . k[b][j][h,:]) * v[b][j][h,d]
+ * Takes SaspaAttnParams as saspa_flash_attn_bf16 does, with q, k, vt and o pointing to float; pitches and batch strides in elements.
+ * V arrives TRANSPOSED, vt[b][h*D+d][ldvt >= nk].  D is a multiple of 8, at most 160; nq, nk >= 1, otherwise arbitrary: keys >= nk are
+ * masked inside the kernel, causal = 1 masks j > i, `scale` is honoured.  No score matrix, no workspace, no allocation, no host
+ * synchronisation; capturable.
+ * Arithmetic: every fp32 operand is split as hi = bf16(x), lo = bf16(x - hi) (round to nearest) and every product sum -- the logits
+ * Q K^T and the weighted values P V alike -- is lo hi + hi lo + hi hi accumulated in fp32 on bf16 MFMAs (SASPA_F32X3's split and order:
+ * at most 2^-17 of |a b| per product).  scale * log2(e) is applied to the fp32 logit; running maximum, exp2, row sum and the online
+ * rescale are fp32; P is split from its fp32 value and NEVER rounded to one bf16 (what separates this kernel from the 16-bit loops); O
+ * accumulates in fp32 and is divided by the fp32 row sum.  Every reduction has a fixed order, nothing is atomic: a batch entry's result
+ * depends neither on the batch size nor on its position in the batch.
+ * Host-side validation, before any launch: null pointer, batch / heads / nq / nk < 1, D outside the range above, ldq / ldk / ldo <
+ * heads * D, ldvt < nk, any SASPA_ATTN_* flag set (prescaled queries and row-major V belong to the 16-bit loops) -> SASPA_EINVAL;
+ * pointers not 16-byte aligned, pitches or batch strides not multiples of 4 -> SASPA_EALIGN. */
+int saspa_flash_attn_f32x3(const SaspaAttnParams* p, void* stream);
+
 /* row softmax in place over a [rows][ld] matrix (unfused attention path: fp32
  * parity mode and the 512-wide single-head VAE attention): x = softmax(scale*x) over
  * the first n columns; causal: row r of each `rows_per_mat` block only sees cols <= r. */

@@ -122,6 +122,7 @@ SYMBOLS = {
     "saspa_ff_block_eligible": (_I, [C.POINTER(FfBlockParams)]),
     "saspa_flash_attn_bf16": (_I, [C.POINTER(AttnParams), _P]),
     "saspa_flash_attn_which": (_I, [C.POINTER(AttnParams)]),
+    "saspa_flash_attn_f32x3": (_I, [C.POINTER(AttnParams), _P]),
     "saspa_softmax_rows": (_I, [_I, _P, _LL, _I, _I, _F, _I, _I, _P]),
     "saspa_attn_wide": (_I, [_I, _P, _I, _LL, _P, _I, _LL, _P, _I, _LL, _P, _I, _LL, _I, _I, _I, _I, _F, _P]),
     "saspa_groupnorm_stats": (_I, [C.POINTER(GroupNormParams), _P]),

@@ -230,7 +230,8 @@ def vae_attn_fused(dtype):
 def attention_core(q, k, vt, heads, nq, nk, causal=False, prescaled=False, v_rowmajor=False):
     """q: [B,nq,C] view, k: [B,nk,C] view, vt: [B,C,ld] (v_rowmajor: V itself, [B,nk,C] view).  bf16 with head dim <= 160: fused
     flash kernel; otherwise (fp32 parity mode, 512-wide VAE head): scores GEMM -> row softmax
-    -> PV GEMM, all batched over (batch, head).
+    -> PV GEMM, all batched over (batch, head).  fp32 with head dim <= 160 inside ops.f32_attn_mode("fused"): one launch with x3
+    products and no score matrix (ops.flash_attn_f32x3).
     prescaled: q was projected with head_dim^-0.5 * log2(e) folded into its weights (_Packed.attn(qscale=...));
     only the flash path takes such queries."""
     b = q.shape[0]
@@ -241,6 +242,10 @@ def attention_core(q, k, vt, heads, nq, nk, causal=False, prescaled=False, v_row
     if ops.is_half(q) and d <= 160:
         return ops.flash_attn(q, k, vt, out, heads, d, nq, nk, scale, causal, prescaled=prescaled, v_rowmajor=v_rowmajor)
     assert not prescaled and not v_rowmajor, "prescaled queries / row-major V exist for the flash path only"
+    # fp32 with ops.f32_attn_mode("fused") (the mode is read as data, not asked through a call: with it off -- the default -- the
+    # calls this function makes are the ones it always made)
+    if q.dtype == torch.float32 and d <= 160 and ops._F32_ATTN_MODE[0] == "fused":
+        return ops.flash_attn_f32x3(q, k, vt, out, heads, d, nq, nk, scale, causal)
     lds = ops.round8(nk)
     assert vt.stride(1) >= lds
     scores = torch.empty((b, heads, nq, lds), device=q.device, dtype=q.dtype)

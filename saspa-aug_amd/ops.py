@@ -164,6 +164,31 @@ def _gemm_dt(t):
     return _lib.SASPA_F32X3 if (d == _lib.SASPA_F32 and _F32_GEMM_MODE[0] == "x3") else d
 
 
+_F32_ATTN_MODE = ["unfused"]
+
+
+class f32_attn_mode:
+    """Context: how fp32 attention with heads of at most 160 channels issued inside runs (models.attention_core) -- "unfused" (scores
+    GEMM -> row softmax -> PV GEMM through a score matrix, the default) or "fused" (flash_attn_f32x3: one launch, x3 products, no
+    score matrix).  16-bit attention and wider heads do not look at it."""
+
+    def __init__(self, mode):
+        if mode not in ("unfused", "fused"):
+            raise ValueError(mode)
+        self.mode = mode
+
+    def __enter__(self):
+        self.prev = _F32_ATTN_MODE[0]
+        _F32_ATTN_MODE[0] = self.mode
+
+    def __exit__(self, *a):
+        _F32_ATTN_MODE[0] = self.prev
+
+
+def f32_attn_fused():
+    return _F32_ATTN_MODE[0] == "fused"
+
+
 def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -843,6 +868,23 @@ def flash_attn(q, k, vt, out, heads, d, nq, nk, scale, causal=False, prescaled=F
     p = _attn_params(q, k, vt, out, heads, d, nq, nk, scale, causal, prescaled, v_rowmajor)
     _launch("flash_attn", 4.0 * q.shape[0] * heads * nq * nk * d,
             lambda: _lib.check(lib.saspa_flash_attn_bf16(C.byref(p), _stream()), "saspa_flash_attn_bf16"),
+            (q.shape[0], heads, nq, nk, d))
+    return out
+
+
+def flash_attn_f32x3(q, k, vt, out, heads, d, nq, nk, scale, causal=False):
+    """flash_attn's operands in fp32: q [B, nq, >=heads*d] view, k [B, nk, >=heads*d] view, vt [B, heads*d, ldvt >= nk] (keys
+    contiguous), out [B, nq, >=heads*d] view.  One fused launch with x3 products (three bf16 MFMAs per product, counted as one
+    product in the recorder's FLOPs), no score matrix; d a multiple of 8, at most 160.  Anything the library refuses raises with its
+    SASPA_E* code, nothing is launched."""
+    _check_dev(q, k, vt, out)
+    _same_dtype("flash_attn_f32x3", q, k=k, v=vt, out=out)
+    if q.dtype != torch.float32:
+        raise TypeError("flash_attn_f32x3 is the fp32 path; 16-bit tensors use flash_attn")
+    lib = _L(q)
+    p = _attn_params(q, k, vt, out, heads, d, nq, nk, scale, causal, False, False)
+    _launch("flash_attn_f32x3", 4.0 * q.shape[0] * heads * nq * nk * d,
+            lambda: _lib.check(lib.saspa_flash_attn_f32x3(C.byref(p), _stream()), "saspa_flash_attn_f32x3"),
             (q.shape[0], heads, nq, nk, d))
     return out
 

@@ -335,6 +335,15 @@ def xl_vae_mode(value):
     return value
 
 
+def f32_mode(gemm, attn):
+    """The fp32 modes as `set_f32_mode` / SASPA_F32_GEMM / SASPA_F32_ATTN spell them -> (gemm, attn); anything else is a ValueError."""
+    if gemm not in ("exact", "x3"):
+        raise ValueError(f"fp32 GEMM mode must be 'exact' or 'x3', got {gemm!r}")
+    if attn not in ("unfused", "fused"):
+        raise ValueError(f"fp32 attention mode must be 'unfused' or 'fused', got {attn!r}")
+    return gemm, attn
+
+
 class StableDiffusionControlNetPipeline:
     HAS_CONTROLNET = True
     CFG_PREFIX = True                 # _sample() evaluates the CFG-shared encoder prefix once per image (cfg_prefix_enabled)
@@ -355,6 +364,8 @@ class StableDiffusionControlNetPipeline:
         self._neg_cache = {}
         self._fp16 = False                # enable_fp16(): fp16 compute for text tower / UNet / ControlNet / scheduler steps
         self._fp16_vae = "bf16"
+        self._f32_mode = None             # set_f32_mode(): (gemm, attn) of the fp32 compute dtype; None = SASPA_F32_GEMM / SASPA_F32_ATTN
+        self.f32_gemm, self.f32_attn = "exact", "unfused"    # what .to() resolved: the modes the fp32 networks run in
         self.last_nonfinite = None        # SDXL VAE mode "f16": device bool [B], the decoder's output of that image was not finite
 
     # ---- construction -------------------------------------------------------------------
@@ -401,6 +412,9 @@ class StableDiffusionControlNetPipeline:
                 cdt = torch.float16
         elif dtype == torch.float32:
             cdt, ndt = torch.float32, torch.float32
+            # opt-in (set_f32_mode / SASPA_F32_GEMM, SASPA_F32_ATTN): x3 GEMMs and fused x3 attention for the fp32 networks
+            self.f32_gemm, self.f32_attn = self._f32_mode or f32_mode(os.environ.get("SASPA_F32_GEMM") or "exact",
+                                                                      os.environ.get("SASPA_F32_ATTN") or "unfused")
         else:
             raise TypeError(f"unsupported pipeline dtype {dtype}")
         # fp16 compute keeps the VAE (its activations overflow fp16) and the safety checker out of fp16: the VAE stays bf16, or runs
@@ -460,6 +474,27 @@ class StableDiffusionControlNetPipeline:
         self._fp16, self._fp16_vae = bool(on), vae
         return self
 
+    def set_f32_mode(self, gemm="exact", attn="unfused"):
+        """Call BEFORE `.to()`: how `.to(dev, torch.float32)` -- the parity dtype -- runs the text tower(s), UNet, ControlNet and the
+        BLIP front-end.  gemm="x3": their GEMMs / convs as three bf16 MFMAs per product (ops.f32_gemm_mode, at most 2^-17 per product);
+        attn="fused": their attention with heads of at most 160 channels in one launch with x3 products and no score matrix
+        (ops.f32_attn_mode, saspa_flash_attn_f32x3).  SASPA_F32_GEMM=x3 / SASPA_F32_ATTN=fused do the same.  The VAE keeps its own
+        rule.  Off by default ("exact", "unfused": every launch as it was); with a 16-bit dtype the call changes nothing."""
+        mode = f32_mode(gemm, attn)
+        if self.unet is not None:
+            raise RuntimeError("set_f32_mode() must be called before .to(): the modes are fixed when the pipeline is placed")
+        self._f32_mode = mode
+        return self
+
+    def _f32_scope(self):
+        """The context the fp32 networks run in: nothing unless .to(dev, torch.float32) resolved a mode other than the default."""
+        if self.dtype != torch.float32 or (self.f32_gemm, self.f32_attn) == ("exact", "unfused"):
+            return contextlib.nullcontext()
+        stack = contextlib.ExitStack()
+        stack.enter_context(ops.f32_gemm_mode(self.f32_gemm))
+        stack.enter_context(ops.f32_attn_mode(self.f32_attn))
+        return stack
+
     def enable_fp8(self, on=True, convs=False, ff="calibrated"):
         """Call BEFORE `.to()`: the LayerNorm-fed projections of the UNet / ControlNet transformer blocks (cross-attention
         query, GEGLU feed-forward) run as e4m3 W8A8 GEMMs (BASELINE.json configs[4] "fp8 MFMA"; SASPA_FP8=1 does the same).
@@ -518,7 +553,8 @@ class StableDiffusionControlNetPipeline:
         self._need_device()
         if not torch.is_tensor(ids):
             ids = torch.as_tensor(np.asarray(ids))
-        return self.text_encoder.forward(ops.h2d(ids, self.device))
+        with self._f32_scope():
+            return self.text_encoder.forward(ops.h2d(ids, self.device))
 
     def _negative_context(self, neg_ids):
         key = np.asarray(neg_ids).tobytes()
@@ -575,8 +611,13 @@ class StableDiffusionControlNetPipeline:
         out, self.last_nsfw = self.run_safety_checker(ops.act_to_u8(img))
         return (out, x, img) if return_latents else out
 
-    def _sample(self, x2, b, hw, ctx, cemb2, steps, guidance_scale, cscale, t_start=0, branches=2, image_guidance=1.0, cfg=True,
-                added=None):
+    def _sample(self, *a, **kw):
+        """_sample_steps inside the pipeline's fp32 modes (set_f32_mode; nothing is entered by default or in a 16-bit dtype)."""
+        with self._f32_scope():
+            return self._sample_steps(*a, **kw)
+
+    def _sample_steps(self, x2, b, hw, ctx, cemb2, steps, guidance_scale, cscale, t_start=0, branches=2, image_guidance=1.0, cfg=True,
+                      added=None):
         """The denoising loop on the CFG-doubled latents x2 [2B,h,w,8] of b images (in place): the captured step replayed, or with
         SASPA_GRAPH=0 / under a launch recorder the same evaluation and update launched from Python.  t_start > 0 (img2img /
         SDEdit): only the timesteps from index t_start of the `steps`-step schedule run (DDIM only).  branches = 3
@@ -632,7 +673,8 @@ class StableDiffusionControlNetPipeline:
         self._check_latents(latents, self.cfgs["unet"]["in_channels"], ctrl, "control", latents_on_device)
         pos = self._positive_context(prompt_ids, query_embeds)
         ctx = self._guidance_context(self._negative_context(negative_ids), pos)
-        cemb = self.controlnet.cond_embedding(ops.u8_to_act(ctrl, self.dtype))
+        with self._f32_scope():
+            cemb = self.controlnet.cond_embedding(ops.u8_to_act(ctrl, self.dtype))
         cemb2 = torch.cat([cemb, cemb], 0)
         x = latents if latents_on_device else self.latents_to_device(latents)
         x2 = torch.cat([x, x], 0).contiguous()
@@ -719,7 +761,8 @@ class StableDiffusionControlNetImg2ImgPipeline(StableDiffusionControlNetPipeline
         pos = self._positive_context(prompt_ids)
         ctx = self._guidance_context(self._negative_context(negative_ids), pos)
         if self.controlnet is not None:
-            cemb = self.controlnet.cond_embedding(ops.u8_to_act(ctrl, dt))
+            with self._f32_scope():
+                cemb = self.controlnet.cond_embedding(ops.u8_to_act(ctrl, dt))
             cemb2 = torch.cat([cemb, cemb], 0)
         else:
             cemb2 = torch.zeros((1,), device=dev, dtype=dt)           # placeholder: nothing reads it
@@ -924,10 +967,11 @@ class BlipDiffusionControlNetPipeline(StableDiffusionControlNetPipeline):
             return preprocess_reference(im, qc, BLIP_IMAGE_MEAN, BLIP_IMAGE_STD).to(self.device)
         px = torch.stack([one(im) for im in reference_images])
         ids = [self.qformer_tokenizer(c) for c in source_subject_categories]
-        if len({i.shape[1] for i in ids}) == 1:
-            return self.qformer.forward(px, np.concatenate(ids))
-        # categories of different token counts: no padding mask in the kernels -> one item at a time
-        return torch.cat([self.qformer.forward(px[i:i + 1], ids[i]) for i in range(len(ids))], 0)
+        with self._f32_scope():
+            if len({i.shape[1] for i in ids}) == 1:
+                return self.qformer.forward(px, np.concatenate(ids))
+            # categories of different token counts: no padding mask in the kernels -> one item at a time
+            return torch.cat([self.qformer.forward(px[i:i + 1], ids[i]) for i in range(len(ids))], 0)
 
     def _positive_context(self, prompt_ids, query_embeds=None):
         if query_embeds is None:
@@ -935,7 +979,8 @@ class BlipDiffusionControlNetPipeline(StableDiffusionControlNetPipeline):
         ids = torch.as_tensor(np.asarray(prompt_ids)) if not torch.is_tensor(prompt_ids) else prompt_ids
         if ids.shape[1] != self.prompt_token_count():
             raise ValueError(f"prompt must be tokenised to {self.prompt_token_count()} tokens (77 - subject tokens)")
-        return self.text_encoder.forward(ops.h2d(ids, self.device), query_embeds, self.cfgs["ctx_begin_pos"])
+        with self._f32_scope():
+            return self.text_encoder.forward(ops.h2d(ids, self.device), query_embeds, self.cfgs["ctx_begin_pos"])
 
     # ---- the reference's call form (keyword names as diffusers spells them, typo included) ----
     def __call__(self, prompt=None, reference_image=None, condtioning_image=None, source_subject_category=None,
@@ -1082,8 +1127,9 @@ class StableDiffusionXLControlNetPipeline(StableDiffusionControlNetPipeline):
         """-> (context [B,77,ctx1+ctx2], pooled [B, proj] fp32)."""
         self._need_device()
         t = lambda a: ops.h2d(a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a)), self.device)   # noqa: E731
-        h1, _ = self.text_encoder.forward(t(ids1), penultimate=True)
-        h2, pooled = self.text_encoder_2.forward(t(ids2), penultimate=True)
+        with self._f32_scope():
+            h1, _ = self.text_encoder.forward(t(ids1), penultimate=True)
+            h2, pooled = self.text_encoder_2.forward(t(ids2), penultimate=True)
         return torch.cat([h1, h2], -1).contiguous(), pooled.float()
 
     @torch.no_grad()
@@ -1115,7 +1161,8 @@ class StableDiffusionXLControlNetPipeline(StableDiffusionControlNetPipeline):
             ctx = self._guidance_context(nctx, ctx)
             pooled = torch.cat([npooled.expand(b, -1), pooled], 0).contiguous()
         time_ids = [[hh, ww, 0, 0, hh, ww]] * ctx.shape[0]       # original_size + crops_coords_top_left + target_size
-        cemb = self.controlnet.cond_embedding(ops.u8_to_act(ctrl, self.dtype))
+        with self._f32_scope():
+            cemb = self.controlnet.cond_embedding(ops.u8_to_act(ctrl, self.dtype))
         x = latents if latents_on_device else self.latents_to_device(latents)
         if cfg:
             x = torch.cat([x, x], 0).contiguous()

@@ -64,7 +64,9 @@ __global__ __launch_bounds__(256) void pool2d_kernel(const T* x, int ldx, T* y, 
 }
 
 // one workgroup per row: y = sign(x) sqrt(|x| + eps) kept in registers / re-derived, sum of squares in fp32 per lane then
-// fp64 across the workgroup (65 536 elements per row for ResNet-101 x 32 attention maps), out = scale * y / max(|y|, 1e-12)
+// fp64 across the workgroup (65 536 elements per row for ResNet-101 x 32 attention maps), out = scale * y / max(|y|, 1e-12).
+// sign(0) = 0: an exact zero (ordinary under ReLU features and ReLU attention maps) has y = 0 and adds NOTHING to the norm -- not
+// its eps (with 60 % zeros, eps per zero scaled a row by 2.2e-5, 370 units of 2^-24)
 __global__ __launch_bounds__(256) void signsqrt_l2norm_kernel(const float* x, long long ldx, float* y, long long ldy, long long C,
                                                               float eps, float scale) {
   __shared__ double part[4];
@@ -73,7 +75,7 @@ __global__ __launch_bounds__(256) void signsqrt_l2norm_kernel(const float* x, lo
   float ss = 0.0f;
   for (long long i = threadIdx.x; i < C; i += 256) {
     const float v = xr[i];
-    ss += fabsf(v) + eps;                                 // y^2 = |x| + eps exactly (before rounding of the sqrt)
+    if (v != 0.0f) ss += fabsf(v) + eps;                  // y^2 = |x| + eps exactly (before rounding of the sqrt)
   }
   double d = (double)wave_sum(ss);
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = d;

@@ -27,6 +27,9 @@ UNIT_BF16 = 2.0 ** -8
 # SASPA_F32X3: a = hi + lo with hi = bf16(a), lo = bf16(a - hi), products hi*hi + hi*lo + lo*hi in fp32.  |a - hi - lo| <=
 # 2^-9 |a - hi| <= 2^-18 |a| and the dropped lo*lo <= 2^-18 |a b|: 2^-17 |a b| per product at most, fp32 accumulation below that.
 UNIT_F32X3 = 2.0 ** -17
+# the exact-fp32 kernels (SASPA_F32: fp32 operands on the fp32 MFMA, fp32 epilogue and storage): half an fp32 ulp at the bottom of a
+# binade.  A right kernel rounds every product and every partial sum to that, in whatever order it adds (tests/f32_ref.py).
+UNIT_F32 = 2.0 ** -24
 
 # Per family: max / rms / |bias| / |slope| in units.  Each value is checked against both margins in tests/test_errbudget.py.
 LIMITS = {
@@ -71,6 +74,61 @@ LIMITS = {
     # normalised input truncated: max 0.07 .. 0.44, carried by bias 4e-3 .. 1.1e-2 and slope 0.21 .. 0.49; padding before the
     # normalisation, the previous chunk's affine, un-SiLU'd halo rows, the first group's statistics, eps x 10: max 2.1 .. 11.9.
     "conv_gn": dict(max=0.45, rms=0.045, bias=0.00015, slope=0.007),
+    # the exact-fp32 kernels (tests/f32_ref.py), in units of 2^-24 (UNIT_F32), measured over test_errbudget.SEEDS.  Where the weakest
+    # mutant is far away the limits sit 2.2 .. 2.6x above the legit envelope, not 2.0x: torch's own sums are among the emulations, and
+    # their order is the host's.
+    # "f32_gemm": linear / conv / split-K with every epilogue form, N(0, 1) and post-ReLU operands against zero-mean weights, K = 40
+    # .. 4608.  Legit (torch's matmul, K reversed, one fma chain, one exactly-summed 4-product step per rounding, K in 2 / 5 / 8
+    # slices): max 0.41 .. 4.14 (SiLU epilogue at K = 64), rms 0.070 .. 0.432 (bias only, K = 64), |bias| <= 0.027 and |slope| <=
+    # 0.36, both inside 3 of their standard errors.  Weakest mutant, the bf16x3 split operands (SASPA_F32X3 where exact was asked),
+    # K <= 576 only: max 16.5 .. 110, rms 2.92 (K = 576) .. 19 (K = 40), bias and slope inside their noise -- the rms carries it (ratio >= 2.9), max
+    # does not hold 2x at K = 576; beyond K = 576 it sinks into the accumulation error and is not asserted.  Operands truncated to
+    # tf32: rms 194 .. 2.6e3; bias / residual / output through bf16: rms 294 .. 9e3; K columns dropped, bias missing on 4 columns,
+    # alpha before the bias, a copied tail row, ReLU on the wrong side of the residual, column 0's bias in the scalar tail: rms >=
+    # 9.4e3.
+    "f32_gemm": dict(max=10.0, rms=1.0, bias=0.01, slope=0.05),
+    # "f32_gemm_pos": non-negative against non-negative operands (the bilinear attention pooling product, K = 52 / 196 + 4 zero
+    # columns, alpha = 1 / HW): nothing cancels, every partial sum is as large as the result and one accumulator errs by ~0.13
+    # sqrt(K) units.  Legit: max 3.0 .. 7.99, rms 0.91 .. 2.07, |bias| <= 0.105, |slope| <= 0.099 (inside 3 standard errors).
+    # bf16x3 split operands: max 51.9 .. 131, rms 14.5 .. 28.8 (ratio >= 2.6 on max, 2.9 on rms); tf32 operands, output through bf16, a K
+    # tile dropped, a copied tail row: rms >= 1e4.
+    "f32_gemm_pos": dict(max=20.0, rms=5.0, bias=0.05, slope=0.05),
+    # "f32_pool": average pooling, fp32 storage, 4 .. 361 taps added in tap order.  Legit: max 0.74 .. 6.97, rms 0.28 .. 2.78 (196
+    # non-negative taps), |bias| <= 0.58, |slope| <= 3.1, inside 2.1 standard errors (48 .. 2376 outputs).  Weakest mutant, 1 / (k*k
+    # - 1) at 361 taps: max 5.5e3, rms 2.5e3; the last tap row left out: rms >= 1.8e5.
+    "f32_pool": dict(max=18.0, rms=7.0, bias=1.5, slope=1.0),
+    # "f32_pool_bf16": the same with bf16 storage, in units of 2^-8: the output rounding dominates.  Legit: max 0.064 .. 0.996, rms
+    # 0.022 .. 0.422, |bias| <= 0.05, |slope| <= 0.19 (inside 1.1 standard errors).  1 / (k*k - 1) where it is named (f32_ref.pool_
+    # cases): rms 5.3 .. 83, and at 196 non-negative taps (48 outputs) max 1.93, rms 1.26 -- there the bias carries it, 1.21 .. 1.44
+    # at a standard error of 0.056 (ratio >= 2.4).  The last tap row left out: rms 2.78 .. 155.  A bf16 accumulator at 196
+    # non-negative taps: max 5.7 .. 7.4, rms 2.3 .. 2.8 (ratio >= 2.5); at 49 taps (rms 1.3 against a limit that has to grant 0.84)
+    # and on zero-mean inputs (rms 0.3 .. 0.5) it CANNOT hold the 2x margin under any statistic and is not asserted there.
+    "f32_pool_bf16": dict(max=2.1, rms=0.9, bias=0.05, slope=0.1),
+    # "f32_tail": signsqrt_l2norm on rows of 1000 / 4096 post-ReLU features (and N(0, 1) rows of both signs), s = |ref|.  Legit (the
+    # kernel's per-lane sums with the fp64 combine, the reference's own expression in fp32, one wave's 64 lanes combined in fp32):
+    # max 1.96 .. 4.62, rms 0.39 .. 1.62, |bias| <= 1.07, |slope| <= 1.17 (the rounding of a row's 1 / norm is common to the row:
+    # systematic over 4 or 5 rows).  Weakest mutant, eps counted for exact zeros on the rows with 1 / 32 zeros: max 8.2 .. 10.3, rms
+    # 6.2 .. 6.8 -- the bias carries it, 6.0 .. 6.7 (ratio >= 2.2); with 60 % zeros every
+    # statistic is above 110.  eps = 1e-12, the norm taken before the sign-sqrt: rms >= 210.
+    "f32_tail": dict(max=10.5, rms=3.6, bias=2.5, slope=2.7),
+    # the fp32 forms of kernels with bf16 budgets (operands and cases of the bf16 families, nothing rounded on the way out).
+    # "f32_norm": layernorm and groupnorm (statistics + apply), s = norm_scale(..., cancel=1.0).  Legit (two-pass LayerNorm with
+    # torch's sums and with the kernel's lanes; GroupNorm from the kernels' own statistics, scale / shift form and (x - mean) rstd
+    # gamma + beta): max 0.09 .. 4.61, rms 0.011 .. 0.784, |bias| <= 0.037, |slope| <= 0.77 (mean-offset groups: the rounding of
+    # a group's mean x scale is common to its elements, so the slope's standard error, ~0.13, understates it).
+    # Weakest mutant, ONE-pass fp32 statistics for the LayerNorm of mean-offset rows (mu / sigma = 64): max 339 .. 415, rms 36 ..
+    # 39; output or gamma through bf16: rms >= 428; n-1 variance, eps 1e-3, eps swapped / x 10: rms >= 1.4e3.
+    "f32_norm": dict(max=11.0, rms=1.8, bias=0.1, slope=1.0),
+    # "f32_softmax": softmax_rows, s = p (1 + |l| + |l - m|) (f32_ref.softmax_ref).  Legit (the kernel's lane order, torch's own
+    # fp32 softmax): max 1.48 .. 1.84, rms 0.28 .. 0.40, |bias| <= 0.021, |slope| <= 0.068 (inside 2.5 standard errors).  Weakest
+    # mutant, the scale x (1 + 2^-12): max 2.1e3, rms 767; logits or output through bf16: rms >= 4.9e3; the causal mask shifted by
+    # one: rms 5e9 (an output where the reference has an exact zero).
+    "f32_softmax": dict(max=4.5, rms=0.9, bias=0.05, slope=0.1),
+    # "f32_elem": geglu (erf), SiLU, quick-GELU; s carries the cancelling terms of 0.5 g (1 + erf) and the rounding of 1.702 x
+    # (f32_ref.elem_refs).  Legit: the kernel's expressions max 2.1 .. 2.5, rms 0.52 .. 0.67; torch's own fp32 GELU max 7.9 .. 8.9,
+    # rms 1.38 .. 1.41, slope 0.24 .. 0.29 -- it sets the limits.  Weakest mutant, tanh-GELU: max 3.4e3, rms 2.0e3; output through
+    # bf16: rms >= 2e4; SiLU and quick-GELU swapped: rms >= 7e6.
+    "f32_elem": dict(max=21.0, rms=3.3, bias=0.05, slope=0.5),
 }
 STATS = ("max", "rms", "bias", "slope")
 Z_NOISE = 8.0           # standard errors of bias / slope granted on top of the systematic limit (8 sigma: never by chance)
@@ -187,14 +245,15 @@ def attn_scale(p, v):
     return _floor(p.double() @ _abs64(v))
 
 
-def norm_scale(xhat, gamma, beta, mu_rstd=None):
+def norm_scale(xhat, gamma, beta, mu_rstd=None, cancel=2.0 ** -15):
     """|gamma * xhat| + |beta| for a normalised xhat [..., C] (channels last) and per-channel gamma, beta.  mu_rstd (mean * rstd,
     broadcastable): the kernels apply y = x sc + (beta - mean sc) with sc = gamma rstd in fp32 (saspa_norm.hip, gn_apply_kernel and
     the one-pass / fused forms that restate it), two fp32 terms of magnitude |mean sc| that cancel: 2^-24 of each, i.e. 2^-15 |mean sc|
-    in bf16 units, joins the budget (it dominates for a constant group, where rstd = eps^-1/2)."""
+    in bf16 units, joins the budget (it dominates for a constant group, where rstd = eps^-1/2).  cancel: that 2^-24 in the caller's
+    unit (the default: bf16 units; 1.0 for the fp32 families, whose unit it is)."""
     s = (xhat.double() * gamma.double()).abs() + beta.double().abs()
     if mu_rstd is not None:
-        s = s + 2.0 ** -15 * (mu_rstd.double() * gamma.double()).abs()
+        s = s + cancel * (mu_rstd.double() * gamma.double()).abs()
     return _floor(s)
 
 

@@ -6,7 +6,10 @@ a limit that breaks either margin turns this file red.
 
 The fused transformer-block kernels (saspa_xattn_block, saspa_ff_block, the A-stationary GEMM's fused forms) have their float64
 references here as well (xattn_ref / ff_ref / as_ref: the chain with RNE-to-bf16 at exactly the hand-offs the kernels pack at, each
-citing its source line), their magnitudes composed stage by stage (errbudget.chain_*_scale), and families of their own."""
+citing its source line), their magnitudes composed stage by stage (errbudget.chain_*_scale), and families of their own.
+
+The exact-fp32 kernels (fp32 MFMA GEMM / conv / split-K, pooling, the sign-sqrt L2 tail and the fp32 forms of the softmax / norm /
+elementwise kernels) have theirs in tests/f32_ref.py: families f32_*, in units of 2^-24."""
 import functools
 import math
 
@@ -14,8 +17,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from tests import fp8_ref, resnet_ref, sampler_ref
-from tests.errbudget import (LIMITS, UNIT_BF16, UNIT_F32X3, attn_scale, budget_stats, check_budget, conv_scale, elem_scale,
+from tests import f32_ref, fp8_ref, resnet_ref, sampler_ref
+from tests.errbudget import (LIMITS, UNIT_BF16, UNIT_F32, UNIT_F32X3, attn_scale, budget_stats, check_budget, conv_scale, elem_scale,
                              fmt, gemm_scale, geglu_gemm_scale, norm_scale, ratio, rejects)
 
 BF = torch.bfloat16
@@ -956,6 +959,46 @@ def _conv_gn_cases():
     return _bf16_only(lambda: resnet_ref.conv_gn_cases(_rand))
 
 
+def _f32_gemm_cases():
+    """The exact-fp32 GEMM / conv / split-K path (SASPA_F32 on the fp32 MFMA) with every epilogue form, in units of 2^-24
+    (tests/f32_ref.py; fp32 families do not follow the fp16 re-run)."""
+    return f32_ref.gemm_cases(_rand)
+
+
+def _f32_gemm_pos_cases():
+    """... on non-negative operands (the bilinear attention pooling product): no cancellation, a budget of its own."""
+    return f32_ref.gemm_cases(_rand, f32_ref.GEMM_POS_CASES)
+
+
+def _f32_pool_cases():
+    """saspa_pool2d's average form, fp32 storage."""
+    return f32_ref.pool_cases(_rand, torch.float32)
+
+
+def _f32_pool_bf16_cases():
+    """saspa_pool2d's average form, bf16 storage (units of 2^-8)."""
+    return f32_ref.pool_cases(_rand, torch.bfloat16)
+
+
+def _f32_tail_cases():
+    """saspa_signsqrt_l2norm."""
+    return f32_ref.tail_cases(_rand)
+
+
+def _f32_norm_cases():
+    """layernorm / groupnorm on fp32 storage (the bf16 cases with the output rounding removed)."""
+    return f32_ref.norm_cases(_rand)
+
+
+def _f32_softmax_cases():
+    return f32_ref.softmax_cases(_rand)
+
+
+def _f32_elem_cases():
+    """geglu / SiLU / quick-GELU on fp32 storage."""
+    return f32_ref.elem_cases(_rand)
+
+
 def _chain_res_cases():
     """The chains with the residual kept (x itself): the output rounding of branch + residual dominates the error."""
     return _xattn_cases(zero_res=False) + _ff_cases(zero_res=False)
@@ -965,7 +1008,11 @@ FAMILIES = {"gemm": (_gemm_family_cases, UNIT_BF16), "attn": (_attn_cases, UNIT_
             "elem": (_elem_family_cases, UNIT_BF16), "e4m3": (_e4m3_cases, fp8_ref.UNIT_E4M3), "f32x3": (_f32x3_cases, UNIT_F32X3), "xattn": (_xattn_cases, UNIT_BF16),
             "ff": (_ff_cases, UNIT_BF16), "as": (_as_cases, UNIT_BF16), "chain_res": (_chain_res_cases, UNIT_BF16),
             "gnstat": (_gnstat_cases, resnet_ref.UNIT_GNSTAT), "gn_chain": (_gn_chain_cases, UNIT_BF16),
-            "conv_gn": (_conv_gn_cases, UNIT_BF16)}
+            "conv_gn": (_conv_gn_cases, UNIT_BF16),
+            "f32_gemm": (_f32_gemm_cases, UNIT_F32), "f32_gemm_pos": (_f32_gemm_pos_cases, UNIT_F32),
+            "f32_pool": (_f32_pool_cases, UNIT_F32), "f32_pool_bf16": (_f32_pool_bf16_cases, UNIT_BF16),
+            "f32_tail": (_f32_tail_cases, UNIT_F32), "f32_norm": (_f32_norm_cases, UNIT_F32),
+            "f32_softmax": (_f32_softmax_cases, UNIT_F32), "f32_elem": (_f32_elem_cases, UNIT_F32)}
 
 
 @functools.lru_cache(maxsize=None)
@@ -1085,7 +1132,23 @@ def test_catalogue_is_complete():
                  "tail items beyond a multiple of 256 left out of the statistics",
                  "zero padding applied before the normalisation", "normalised input truncated to bf16", "eps x 10 conv_gn",
                  "n-1 variance conv_gn", "scale / shift of the previous 32-channel chunk for a chunk's first tap",
-                 "SiLU skipped on the halo rows", "a chunk that straddles groups takes the first group's statistics"]:
+                 "SiLU skipped on the halo rows", "a chunk that straddles groups takes the first group's statistics",
+                 # the exact-fp32 kernels (tests/f32_ref.py)
+                 "bf16x3 split operands f32", "operands truncated to tf32", "bias rounded to bf16 f32",
+                 "residual rounded to bf16 f32", "output through bf16 f32", "last 4 of K dropped f32", "last 32 of K dropped f32",
+                 "bias missing on the last 4 columns f32", "alpha applied before the bias f32",
+                 "ragged tail row copies its neighbour f32", "ReLU before the residual where ADD_RELU was asked",
+                 "ReLU after the residual where RELU was asked", "scalar-tail columns take column 0's bias",
+                 "bf16x3 split operands f32 bap", "1 / (k*k - 1) avgpool", "last tap row left out avgpool",
+                 "accumulation in bf16 avgpool", "eps counted for exact zeros signsqrt_l2norm", "eps = 1e-12 signsqrt_l2norm",
+                 "norm taken before the sign-sqrt signsqrt_l2norm",
+                 "output through bf16 f32 layernorm", "gamma rounded to bf16 f32 layernorm", "eps 1e-3 f32 layernorm",
+                 "n-1 variance f32 layernorm", "eps swapped f32 layernorm", "one-pass fp32 statistics f32 layernorm",
+                 "output through bf16 f32 groupnorm", "n-1 variance f32 groupnorm", "eps x 10 f32 groupnorm",
+                 "output through bf16 f32 softmax_rows", "logits through bf16 f32 softmax_rows",
+                 "scale x (1 + 2^-12) f32 softmax_rows", "causal mask shifted by one f32 softmax_rows",
+                 "f32 geglu tanh-gelu", "f32 silu swapped for quick-gelu", "f32 quick-gelu swapped for silu",
+                 "f32 geglu output through bf16"]:
         assert want in names, want
 
 

@@ -18,6 +18,8 @@ from saspa_aug_amd import filters, ops, utils
 from saspa_aug_amd import weights as W
 from saspa_aug_amd.synthetic import synthetic_image
 from saspa_aug_amd.tokenizer import HashTokenizer
+from tests import f32_ref
+from tests.errbudget import LIMITS, UNIT_F32, check_budget, fmt
 from tests.util import from_nhwc, to_nhwc
 
 pytestmark = pytest.mark.gpu
@@ -41,11 +43,16 @@ def test_pool2d(dev, dtype):
 
 
 def test_signsqrt_l2norm(dev):
+    """Rows of both signs with a few exact zeros, under the f32_tail rounding-error budget (units of 2^-24 of |ref|, against float64
+    of the reference's formula; tests/test_f32_errbudget_gpu.py has the zero-heavy rows)."""
     x = torch.randn(5, 4096, generator=torch.Generator().manual_seed(1))
     x[0, :7] = 0.0
     got = ops.signsqrt_l2norm(x.to(dev), 1e-6, 100.0).cpu()
-    ref = F.normalize(torch.sign(x) * torch.sqrt(x.abs() + 1e-6), dim=-1) * 100.0
-    assert (got - ref).abs().max() < 1e-4
+    ref, s = f32_ref.tail_ref(x.double(), 1e-6, 100.0)
+    assert (got[x == 0] == 0).all()
+    st = check_budget(got, ref, s, UNIT_F32, limits=LIMITS["f32_tail"], what="signsqrt_l2norm 5x4096, N(0, 1) rows")
+    print(f"\n[budget] f32_tail signsqrt_l2norm 5x4096, N(0, 1) rows: {fmt(st)}")
+    assert (got - F.normalize(torch.sign(x) * torch.sqrt(x.abs() + 1e-6), dim=-1) * 100.0).abs().max() < 1e-4
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])

@@ -760,6 +760,47 @@ long long saspa_png_workspace(int n, int H, int W, int C);
 int saspa_png_deflate(const uint8_t* px, int n, int H, int W, int C, uint8_t* streams, long long capacity, int* sizes,
                       void* workspace, long long workspace_bytes, void* stream);
 
+/* ---- caption decoder (csrc/saspa_decode.hip; default library only) ----
+ * One new token per row against a key/value cache: out[r] = softmax(scale * q[r] K^T) V per head, one query row each.
+ *   q / out: [rows, heads * d] (pitches ldq / ldo).  k / v: caches [entries, nk_max, heads * d], row-major (V is NOT transposed),
+ *   key pitch ldk / ldv, entry stride ske / sve (elements).  Row r reads entry r / group: group = 1 is self-attention (an entry per
+ *   beam row), group = beams is cross-attention (the beams of an image share its K / V, loaded once per workgroup).
+ *   len: int32 per row on the device, keys < len[r] are live (clamped to [0, nk]; 0 gives a zero row); NULL = all nk keys.  Keys at or
+ *   beyond a row's length are never read for it.
+ * Arithmetic: products and sums in fp32 in a fixed order (a logit over d ascending; the maximum and the sum over a fixed lane / stride
+ * pattern; P V over key slices, then the slices ascending), scale multiplies the fp32 logit, expf, one division by the sum, ONE
+ * rounding to the storage type.  No atomics; a row's result does not depend on the other rows of the launch.
+ * dtype SASPA_BF16 or SASPA_F32.  Before any launch: null q / k / v / out, rows / heads / nk / entries < 1, entries * group < rows, a
+ * pitch shorter than heads * d -> SASPA_EINVAL; d % 8 != 0, d > 128, nk > 1024, group outside 1 .. 8 -> SASPA_ERANGE; pointers not
+ * 16-byte aligned, pitches / entry strides not multiples of 16 bytes, len not 4-byte aligned -> SASPA_EALIGN. */
+#define SASPA_DECODE_MAX_D 128
+#define SASPA_DECODE_MAX_NK 1024
+#define SASPA_DECODE_MAX_GROUP 8
+typedef struct {
+  int dtype;
+  const void* q; int ldq;
+  const void* k; int ldk; long long ske;
+  const void* v; int ldv; long long sve;
+  const int* len;
+  void* out; int ldo;
+  int rows, entries, heads, d, nk, group;
+  float scale;
+} SaspaDecodeAttnParams;
+int saspa_decode_attn(const SaspaDecodeAttnParams* p, void* stream);
+
+/* One beam-search step's selection, one workgroup per image.  logits: fp32 [images * group, ld], columns < vocab are live (columns
+ * vocab .. ld - 1 are padding: loaded with their 16-byte chunk, never part of a maximum, a sum or a candidate).  Per row
+ *   lp[t] = (x[t] - max) - log(sum_t exp(x[t] - max))      fp32, fixed order;
+ * the candidate (row g of the image, token t) scores (ban_on && t == ban_token ? -inf : lp[t]) + scores[row], fp32.  Per image the
+ * k = 2 * group best of the group * vocab candidates go to out_score[image][k] (descending) and out_idx[image][k][2] = (row in group,
+ * token); ties go to the lowest flat index row * vocab + token.  -inf candidates (a row whose score is -inf, a banned token) are taken
+ * last and never make a NaN; with fewer than k candidates the tail is (-inf, -1, -1).  No atomics; an image's result does not depend on
+ * the rest of the batch.
+ * Before any launch: null pointers, images / vocab < 1, ld < vocab -> SASPA_EINVAL; group outside 1 .. 8, group * vocab >= 2^31 ->
+ * SASPA_ERANGE; logits not 16-byte aligned, ld % 4 != 0, scores / out_score / out_idx not 4-byte aligned -> SASPA_EALIGN. */
+int saspa_logprob_topk(const float* logits, int ld, int vocab, int images, int group, const float* scores, int ban_token, int ban_on,
+                       float* out_score, int* out_idx, void* stream);
+
 int saspa_abi_version(void);
 /* the dtype code of the library's 16-bit element type: SASPA_BF16 (libsaspa_hip.so) or SASPA_F16 (libsaspa_hip_f16.so) */
 int saspa_half_type(void);

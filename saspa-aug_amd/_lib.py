@@ -11,6 +11,7 @@ F16_LIB_PATH = os.path.join(_HERE, "libsaspa_hip_f16.so")
 SASPA_BF16, SASPA_F32, SASPA_F32X3 = 0, 1, 2
 SASPA_F16 = 3                                              # libsaspa_hip_f16.so only
 SASPA_EINVAL, SASPA_EALIGN, SASPA_ERANGE = -1, -2, -3      # include/saspa_hip.h
+DECODE_MAX_D, DECODE_MAX_NK, DECODE_MAX_GROUP = 128, 1024, 8  # SASPA_DECODE_MAX_*
 LPIPS_MAX_C, LPIPS_MAX_BLOCKS = 512, 64                    # SASPA_LPIPS_MAX_C / SASPA_LPIPS_MAX_BLOCKS
 CLASS_HEAD_MAX_D, CLASS_HEAD_MAX_C = 2048, 4096            # SASPA_CLASS_HEAD_MAX_D / SASPA_CLASS_HEAD_MAX_C
 ERRORS = {-1: "SASPA_EINVAL (null pointer / bad size)", -2: "SASPA_EALIGN (16-byte alignment / channel multiple)",
@@ -101,6 +102,15 @@ class FfBlockParams(C.Structure):
     ]
 
 
+class DecodeAttnParams(C.Structure):
+    _fields_ = [
+        ("dtype", C.c_int), ("q", C.c_void_p), ("ldq", C.c_int), ("k", C.c_void_p), ("ldk", C.c_int), ("ske", C.c_longlong),
+        ("v", C.c_void_p), ("ldv", C.c_int), ("sve", C.c_longlong), ("len", C.c_void_p), ("out", C.c_void_p), ("ldo", C.c_int),
+        ("rows", C.c_int), ("entries", C.c_int), ("heads", C.c_int), ("d", C.c_int), ("nk", C.c_int), ("group", C.c_int),
+        ("scale", C.c_float),
+    ]
+
+
 class HedFuseParams(C.Structure):
     _fields_ = [
         ("nmaps", C.c_int), ("n", C.c_int), ("H", C.c_int), ("W", C.c_int),
@@ -179,6 +189,8 @@ SYMBOLS = {
     "saspa_png_capacity": (_LL, [_I, _I, _I]),
     "saspa_png_workspace": (_LL, [_I, _I, _I, _I]),
     "saspa_png_deflate": (_I, [_P, _I, _I, _I, _I, _P, _LL, _P, _P, _LL, _P]),
+    "saspa_decode_attn": (_I, [C.POINTER(DecodeAttnParams), _P]),
+    "saspa_logprob_topk": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _P, _P]),
     "saspa_abi_version": (_I, []),
     "saspa_half_type": (_I, []),
     "saspa_build_arch": (C.c_char_p, []),

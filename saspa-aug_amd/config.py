@@ -59,6 +59,25 @@ BLIP_IMAGE_MEAN = (0.48145466, 0.4578275, 0.40821073)
 BLIP_IMAGE_STD = (0.26862954, 0.26130258, 0.27577711)
 BLIP_DIFFUSION = dict({k: v for k, v in SD15.items() if k != "safety"}, qformer=BLIP2_QFORMER, ctx_begin_pos=2)
 
+# BLIP captioner, LAVIS `blip_caption` / `base_coco` (prompts_engineering/blip_utils.py:28-58 of the reference): ViT-B/16 at 384^2 (577
+# tokens, fused qkv with bias, pre-LN, erf-GELU, a final LayerNorm over all tokens) + a BERT-base text decoder (12 post-LN layers of
+# causal self-attention, cross-attention to the image tokens, feed-forward) + the BERT LM head.  Vocabulary = bert-base-uncased + [DEC]
+# (30522, the BOS) + [ENC].  Values RECALLED from LAVIS (configs/models/blip_caption_base_coco.yaml, med_config.json, BlipCaption.generate
+# defaults), not verified: no checkpoint could be read here.  vis_eps: LAVIS builds its ViT with LayerNorm(eps=1e-6); the transformers
+# port of the same model defaults to 1e-5 -- a config field, tests pass their oracle's value.
+BLIP_CAPTION = dict(
+    image_size=384, patch=16, vis_width=768, vis_layers=12, vis_heads=12, vis_mlp=3072, vis_eps=1e-6,
+    width=768, layers=12, heads=12, mlp=3072, vocab=30524, max_pos=512, eps=1e-12,
+    bos=30522, eos=102, pad=0, prompt="a picture of ", num_beams=3, max_length=30, min_length=10,
+)
+
+
+def tiny_blip_caption(**kw):
+    """`BLIP_CAPTION` at reduced width with the same topology (tests): 9 image tokens of width 64, 2 + 2 layers, 4 heads of 16."""
+    return dict(dict(image_size=48, patch=16, vis_width=64, vis_layers=2, vis_heads=4, vis_mlp=128, vis_eps=1e-5,
+                     width=64, layers=2, heads=4, mlp=128, vocab=96, max_pos=40, eps=1e-12,
+                     bos=94, eos=2, pad=0, prompt="a picture of ", num_beams=3, max_length=12, min_length=6), **kw)
+
 
 # ---- filter stage (SURVEY 8f f1; all_utils/utils.py:252-255, :306-323, :357-375) ----
 # OpenAI CLIP "RN50" (clip.load('RN50')): ModifiedResNet (3, 4, 6, 3) width 64 -> 2048 channels at 7x7, attention pool with

@@ -909,6 +909,71 @@ def attn_wide(q, k, v, out, nq, nk, scale):
     return out
 
 
+def _decode_attn_params(q, k, v, out, lens, heads, d, nk, group, scale):
+    p = _lib.DecodeAttnParams()
+    p.dtype = _dt(q)
+    p.q, p.ldq = _ptr(q), q.stride(0)
+    p.k, p.ldk, p.ske = _ptr(k), k.stride(1), k.stride(0)
+    p.v, p.ldv, p.sve = _ptr(v), v.stride(1), v.stride(0)
+    p.len = _ptr(lens)
+    p.out, p.ldo = _ptr(out), out.stride(0)
+    p.rows, p.entries, p.heads, p.d, p.nk, p.group = q.shape[0], k.shape[0], int(heads), int(d), int(nk), int(group)
+    p.scale = float(scale)
+    return p
+
+
+def decode_attn(q, k, v, heads, nk, scale, *, group=1, lens=None, out=None):
+    """One query per row against a key/value cache (saspa_decode_attn): q [rows, >= heads*d] view, k / v caches
+    [entries, nk_max, >= heads*d] views (row-major, V not transposed), row r reads entry r // group and its keys < lens[r] (int32 on the
+    device; None = all nk).  bf16 or fp32 storage, fp32 arithmetic, one rounding; -> out [rows, heads*d].  Anything the library refuses
+    (d % 8, d > 128, nk > 1024, group > 8, alignment) raises with its SASPA_E* code, nothing is launched."""
+    _check_dev(q, k, v, lens, out)
+    _same_dtype("decode_attn", q, k=k, v=v, out=out)
+    if q.dim() != 2 or k.dim() != 3 or v.dim() != 3 or q.stride(1) != 1 or k.stride(2) != 1 or v.stride(2) != 1:
+        raise ValueError("decode_attn: q must be [rows, C] and k / v [entries, nk_max, C] with a contiguous last dim")
+    if k.shape[1] < nk or v.shape[1] < nk or v.shape[0] != k.shape[0]:
+        raise ValueError(f"decode_attn: caches {tuple(k.shape)} / {tuple(v.shape)} do not hold {nk} keys per entry")
+    if lens is not None and (lens.dtype != torch.int32 or lens.numel() < q.shape[0] or not lens.is_contiguous()):
+        raise ValueError("decode_attn: lens must be a contiguous int32 tensor with one entry per row")
+    c = k.shape[2]
+    if c % heads or q.shape[1] < c:
+        raise ValueError(f"decode_attn: {c} cache channels do not split into {heads} heads of the query's width {q.shape[1]}")
+    d = c // heads
+    if out is None:
+        out = torch.empty((q.shape[0], c), device=q.device, dtype=q.dtype)
+    p = _decode_attn_params(q, k, v, out, lens, heads, d, nk, group, scale)
+    lib = _L(q)
+    _launch("decode_attn", 4.0 * q.shape[0] * heads * nk * d,
+            lambda: _lib.check(lib.saspa_decode_attn(C.byref(p), _stream()), "saspa_decode_attn"), (q.shape[0], heads, 1, nk, d))
+    return out
+
+
+def logprob_topk(logits, vocab, group, scores, ban_token=-1, ban_on=False):
+    """One beam-search step's selection (saspa_logprob_topk): fp32 logits [images * group, ld >= vocab] (pad columns ignored), fp32
+    running scores [images * group]; per image the 2 * group best of its group * vocab candidates log_softmax(row)[token] +
+    scores[row] (ban_token at -inf while ban_on), descending, ties to the lowest row * vocab + token.
+    -> (scores fp32 [images, 2*group], (row in group, token) int32 [images, 2*group, 2], buf): the first two are views of `buf`
+    (int32 [3, images, 2*group]), so that the host fetches a step's selection with a single copy."""
+    _check_dev(logits, scores)
+    if logits.dtype != torch.float32 or scores.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise TypeError("logprob_topk takes fp32 logits [rows, ld] and fp32 scores")
+    rows = logits.shape[0]
+    if rows % group or scores.numel() != rows or not scores.is_contiguous():
+        raise ValueError(f"logprob_topk: {rows} rows / {scores.numel()} scores are not whole images of {group} rows")
+    if rows > group and logits.stride(0) != logits.shape[1]:
+        raise ValueError("logprob_topk: the rows of the logits must be densely packed")
+    images, k = rows // group, 2 * group
+    buf = torch.empty((3, images, k), device=logits.device, dtype=torch.int32)
+    out_score = buf[0].view(torch.float32)
+    out_idx = buf[1:].view(images, k, 2)
+    lib = _L()
+    _launch("logprob_topk", 0.0,
+            lambda: _lib.check(lib.saspa_logprob_topk(_ptr(logits), logits.stride(0) if rows > 1 else logits.shape[1], int(vocab), images,
+                                                      int(group), _ptr(scores), int(ban_token), int(bool(ban_on)), _ptr(out_score),
+                                                      _ptr(out_idx), _stream()), "saspa_logprob_topk"))
+    return out_score, out_idx, buf
+
+
 def softmax_rows(x, n, scale, causal=False, rows_per_mat=1):
     """In-place softmax(scale*x) over the first n columns of [rows, ld]; pad columns zeroed."""
     _check_dev(x)

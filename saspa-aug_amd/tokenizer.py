@@ -121,6 +121,16 @@ class BertHashTokenizer:
         lo = 1000 if self.vocab > 2000 else 3
         return np.asarray([self.cls] + [lo + zlib.crc32(w.encode()) % (self.vocab - lo) for w in words] + [self.sep], np.int64)[None]
 
+    def decode(self, ids, skip_special_tokens=True):
+        """Placeholder: a hash has no inverse and a synthetic-weight run has no vocabulary -- "t<id>" per token, so that captions of
+        such a run are at least distinct and reproducible.  Special: everything below the first word id, and the two ids above
+        the word range that the BLIP captioner appends ([DEC], [ENC])."""
+        lo = 1000 if self.vocab > 2000 else 3
+        ids = [int(i) for i in ids]
+        if skip_special_tokens:
+            ids = [i for i in ids if lo <= i < self.vocab]
+        return " ".join(f"t{i}" for i in ids)
+
 
 class BertWordPieceTokenizer:
     """bert-base-uncased WordPiece from the checkpoint's vocab.txt (lower-case, punctuation split, greedy
@@ -152,6 +162,29 @@ class BertWordPieceTokenizer:
         for w in re.findall(r"[a-z0-9]+|[^\sa-z0-9]", (text or "").lower()):
             ids += self._pieces(w)
         return np.asarray(ids + [self.sep], np.int64)[None]
+
+    # transformers' clean_up_tokenization (tokenization_utils_base), in its order
+    _CLEAN_UP = ((" .", "."), (" ?", "?"), (" !", "!"), (" ,", ","), (" ' ", "'"), (" n't", "n't"), (" 'm", "'m"), (" 's", "'s"),
+                 (" 've", "'ve"), (" 're", "'re"))
+    SPECIAL = ("[PAD]", "[UNK]", "[CLS]", "[SEP]", "[MASK]", "[DEC]", "[ENC]")
+
+    def decode(self, ids, skip_special_tokens=True, clean_up_tokenization_spaces=True):
+        """ids -> text as transformers.BertTokenizer.decode does it: the pieces joined with spaces, " ##" removed, then the clean-up
+        rules.  Special tokens ([PAD] [UNK] [CLS] [SEP] [MASK], BLIP's [DEC] / [ENC], and ids beyond the vocabulary file, which
+        is where a checkpoint puts [DEC] / [ENC] when vocab.txt lacks them) are skipped."""
+        if not hasattr(self, "_inv"):
+            self._inv = {i: t for t, i in self.vocab.items()}
+        toks = []
+        for i in ids:
+            t = self._inv.get(int(i))
+            if skip_special_tokens and (t is None or t in self.SPECIAL):
+                continue
+            toks.append("[UNK]" if t is None else t)
+        text = " ".join(toks).replace(" ##", "").strip()
+        if clean_up_tokenization_spaces:
+            for a, b in self._CLEAN_UP:
+                text = text.replace(a, b)
+        return text
 
 
 def make_bert_tokenizer(vocab_dir=None, vocab=30523):

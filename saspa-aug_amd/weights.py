@@ -267,7 +267,91 @@ def safety_checker_spec(cfg):
     return spec
 
 
-SPECS = dict(safety=safety_checker_spec, unet=unet_spec, controlnet=controlnet_spec, vae=vae_decoder_spec, text=clip_text_spec, text2=clip_text_spec,
+def blip_caption_spec(cfg):
+    """The BLIP captioner (config.BLIP_CAPTION) under the key names of transformers' BlipForConditionalGeneration: vision_model.*,
+    text_decoder.bert.*, text_decoder.cls.predictions.* -- the one layout a test pins.  (The LM-head decoder weight is tied to the
+    word embeddings in the trained model; a synthetic state dict draws its own.)"""
+    vw, w = cfg["vis_width"], cfg["width"]
+    npos = (cfg["image_size"] // cfg["patch"]) ** 2 + 1
+    v = "vision_model"
+    spec = [(v + ".embeddings.class_embedding", (1, 1, vw), "embed"),
+            (v + ".embeddings.position_embedding", (1, npos, vw), "embed"),
+            (v + ".embeddings.patch_embedding.weight", (vw, 3, cfg["patch"], cfg["patch"]), "w"),
+            (v + ".embeddings.patch_embedding.bias", (vw,), "bias")]
+    for i in range(cfg["vis_layers"]):
+        lp = f"{v}.encoder.layers.{i}"
+        spec += [(lp + ".self_attn.qkv.weight", (3 * vw, vw), "w"), (lp + ".self_attn.qkv.bias", (3 * vw,), "bias"),
+                 (lp + ".self_attn.projection.weight", (vw, vw), "w"), (lp + ".self_attn.projection.bias", (vw,), "bias"),
+                 (lp + ".layer_norm1.weight", (vw,), "gain"), (lp + ".layer_norm1.bias", (vw,), "bias"),
+                 (lp + ".mlp.fc1.weight", (cfg["vis_mlp"], vw), "w"), (lp + ".mlp.fc1.bias", (cfg["vis_mlp"],), "bias"),
+                 (lp + ".mlp.fc2.weight", (vw, cfg["vis_mlp"]), "w"), (lp + ".mlp.fc2.bias", (vw,), "bias"),
+                 (lp + ".layer_norm2.weight", (vw,), "gain"), (lp + ".layer_norm2.bias", (vw,), "bias")]
+    spec += [(v + ".post_layernorm.weight", (vw,), "gain"), (v + ".post_layernorm.bias", (vw,), "bias")]
+    b = "text_decoder.bert"
+    spec += [(b + ".embeddings.word_embeddings.weight", (cfg["vocab"], w), "embed"),
+             (b + ".embeddings.position_embeddings.weight", (cfg["max_pos"], w), "embed"),
+             (b + ".embeddings.LayerNorm.weight", (w,), "gain"), (b + ".embeddings.LayerNorm.bias", (w,), "bias")]
+
+    def dense_ln(pfx, cin, cout):
+        return [(pfx + ".dense.weight", (cout, cin), "w"), (pfx + ".dense.bias", (cout,), "bias"),
+                (pfx + ".LayerNorm.weight", (cout,), "gain"), (pfx + ".LayerNorm.bias", (cout,), "bias")]
+
+    for i in range(cfg["layers"]):
+        lp = f"{b}.encoder.layer.{i}"
+        for a, kin in (("attention", w), ("crossattention", vw)):
+            spec += [(f"{lp}.{a}.self.query.weight", (w, w), "w"), (f"{lp}.{a}.self.query.bias", (w,), "bias")]
+            for n in ("key", "value"):
+                spec += [(f"{lp}.{a}.self.{n}.weight", (w, kin), "w"), (f"{lp}.{a}.self.{n}.bias", (w,), "bias")]
+            spec += dense_ln(f"{lp}.{a}.output", w, w)
+        spec += [(f"{lp}.intermediate.dense.weight", (cfg["mlp"], w), "w"), (f"{lp}.intermediate.dense.bias", (cfg["mlp"],), "bias")]
+        spec += dense_ln(f"{lp}.output", cfg["mlp"], w)
+    c = "text_decoder.cls.predictions"
+    spec += dense_ln(c + ".transform", w, w)
+    spec += [(c + ".decoder.weight", (cfg["vocab"], w), "w"), (c + ".decoder.bias", (cfg["vocab"],), "bias")]
+    return spec
+
+
+def blip_caption_from_transformers(sd):
+    """A BlipForConditionalGeneration state dict -> the names of blip_caption_spec, fp32: buffers (position_ids) dropped, the tied
+    copies resolved (cls.predictions.bias is decoder.bias; a file saved without the tied decoder weight takes the word embeddings)."""
+    c = "text_decoder.cls.predictions"
+    out = {k: v.detach().float() for k, v in sd.items() if not k.endswith("position_ids") and k != c + ".bias"}
+    if c + ".decoder.bias" not in out and c + ".bias" in sd:
+        out[c + ".decoder.bias"] = sd[c + ".bias"].detach().float()
+    if c + ".decoder.weight" not in out:
+        out[c + ".decoder.weight"] = out["text_decoder.bert.embeddings.word_embeddings.weight"]
+    return out
+
+
+# LAVIS BlipCaption checkpoint (model_base_caption_capfilt_large.pth, under its "model" entry): the timm-style ViT names of
+# lavis/models/vit.py.  RECALLED, UNVERIFIED: no LAVIS checkpoint could be read here; a wrong name fails loudly (KeyError at pack time).
+_LAVIS_VIT = (("visual_encoder.cls_token", "vision_model.embeddings.class_embedding"),
+              ("visual_encoder.pos_embed", "vision_model.embeddings.position_embedding"),
+              ("visual_encoder.patch_embed.proj.", "vision_model.embeddings.patch_embedding."),
+              ("visual_encoder.norm.", "vision_model.post_layernorm."))
+_LAVIS_BLOCK = ((".norm1.", ".layer_norm1."), (".norm2.", ".layer_norm2."), (".attn.qkv.", ".self_attn.qkv."),
+                (".attn.proj.", ".self_attn.projection."))
+
+
+def blip_caption_from_lavis(sd):
+    """A LAVIS BlipCaption state dict (visual_encoder.*, text_decoder.*) -> the names of blip_caption_spec.  Key names recalled, unverified."""
+    sd = sd.get("model", sd)
+    out = {}
+    for k, v in sd.items():
+        if k.startswith("visual_encoder.blocks."):
+            k = k.replace("visual_encoder.blocks.", "vision_model.encoder.layers.", 1)
+            for a, b in _LAVIS_BLOCK:
+                k = k.replace(a, b, 1)
+        else:
+            for a, b in _LAVIS_VIT:
+                if k.startswith(a):
+                    k = b + k[len(a):]
+                    break
+        out[k] = v
+    return blip_caption_from_transformers(out)
+
+
+SPECS = dict(blip_caption=blip_caption_spec, safety=safety_checker_spec, unet=unet_spec, controlnet=controlnet_spec, vae=vae_decoder_spec, text=clip_text_spec, text2=clip_text_spec,
              qformer=blip2_qformer_spec)
 
 

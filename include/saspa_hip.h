@@ -801,6 +801,72 @@ int saspa_decode_attn(const SaspaDecodeAttnParams* p, void* stream);
 int saspa_logprob_topk(const float* logits, int ld, int vocab, int images, int group, const float* scores, int ban_token, int ban_on,
                        float* out_score, int* out_idx, void* stream);
 
+/* ---- T5 key-to-text (csrc/saspa_t5.hip; default library only) ----
+ * RMS norm (T5LayerNorm): out[r][c] = (x[r][c] * rs[r]) * gamma[c], rs[r] = 1 / sqrt(sum_c x[r][c]^2 / C + eps): no mean is
+ * subtracted and there is no bias.  x / out: [rows, C] with pitches ldx / ldo (elements), gamma fp32 [C].
+ * Arithmetic: fp32; a wave per row, lane l adds the squares of the 16-byte chunks l, l + 64, ... element by element in one fma chain,
+ * then the 64-lane butterfly; IEEE division and square root; the two products in the order written; ONE rounding to the storage
+ * type.  No atomics; a row's result does not depend on the other rows of the launch.
+ * dtype SASPA_BF16 or SASPA_F32.  Before any launch: null x / out / gamma, another dtype, rows / C < 1, a pitch shorter than C, eps < 0
+ * or NaN -> SASPA_EINVAL; C > 8192 -> SASPA_ERANGE; C % 8 != 0, x / out not 16-byte aligned, pitches not multiples of 16 bytes, gamma
+ * not 4-byte aligned -> SASPA_EALIGN. */
+#define SASPA_RMSNORM_MAX_C 8192
+int saspa_rmsnorm(int dtype, const void* x, int ldx, void* out, int ldo, int rows, int C, const float* gamma, float eps, void* stream);
+
+/* Attention of one query per row against a key/value cache with an additive relative-position bias: saspa_decode_attn's contract
+ * (same cache layout [entries, nk_max, heads * d], row-major V, per-row len clamped to [0, nk] with 0 giving a zero row, keys at or
+ * beyond a row's length never read for it) with three additions:
+ *   rows_per_entry replaces group: row r reads entry r / rows_per_entry, 1 .. 1024 (the tokens of an encoder sequence are the rows of
+ *     its entry; 1 is the cached decoder self-attention);
+ *   pos: int32 per row on the device, the query's position;
+ *   bias: fp32 [heads, ncol] with pitch ldb, and center.  The logit of key j for row r, head h is
+ *       (q . k_j) * scale + bias[h][clamp(pos[r] - j + center, 0, ncol - 1)]
+ *     the bias added in fp32 AFTER the scale; the column is formed in 64 bits and saturates at both ends (T5's buckets saturate beyond
+ *     max_distance, so a table of 2 * max_distance + 1 columns (bidirectional, center = max_distance) or max_distance + 1 (causal,
+ *     center = 0) is exact at any length).  The host builds the table; the kernel never evaluates the bucket function.
+ * Arithmetic: as saspa_decode_attn (a logit over d ascending in one fma chain; the maximum and the sum over a fixed lane / stride
+ * pattern; expf; P V over key slices, then the slices ascending; one division by the sum; ONE rounding to the storage type).  Rows of
+ * an entry share a workgroup in blocks of 8, but each row's order of operations depends on its own len only.  No atomics; a row's
+ * result does not depend on the other rows of the launch.
+ * dtype SASPA_BF16 or SASPA_F32.  Before any launch: null q / k / v / out / pos / bias, rows / heads / d / nk / entries /
+ * rows_per_entry / ncol < 1, entries * rows_per_entry < rows, a pitch shorter than heads * d, ldb < ncol -> SASPA_EINVAL; d % 8 != 0,
+ * d > 128, nk > 1024, rows_per_entry > 1024 -> SASPA_ERANGE; pointers not 16-byte aligned, pitches / entry strides not multiples of
+ * 16 bytes, len / pos / bias not 4-byte aligned -> SASPA_EALIGN. */
+#define SASPA_RELBIAS_MAX_D 128
+#define SASPA_RELBIAS_MAX_NK 1024
+#define SASPA_RELBIAS_MAX_ROWS 1024
+typedef struct {
+  int dtype;
+  const void* q; int ldq;
+  const void* k; int ldk; long long ske;
+  const void* v; int ldv; long long sve;
+  const int* len;
+  const int* pos;
+  const float* bias; int ldb, ncol, center;
+  void* out; int ldo;
+  int rows, entries, heads, d, nk, rows_per_entry;
+  float scale;
+} SaspaAttnRelbiasParams;
+int saspa_attn_relbias(const SaspaAttnRelbiasParams* p, void* stream);
+
+/* One sampling step, one workgroup per row of fp32 logits [rows, ld] (columns vocab .. ld - 1 are padding: loaded with their 16-byte
+ * chunk, never a candidate).  In the order of transformers' warpers (temperature, top-k, top-p), all fp32:
+ *   y[t] = x[t] / temperature (IEEE division);
+ *   the min(top_k, vocab) largest y are kept, ordered by y descending, ties to the lowest token id;
+ *   e[i] = expf(y[i] - y[0]) in that order, z = their sum ascending;
+ *   top_p < 1: the shortest prefix whose running sum of e[i] / z reaches top_p (>=) is kept, at least one token;
+ *   s = the sum of the kept e[i] ascending; the result is the first kept token whose running sum of e[i] / s exceeds u[r] (>), the
+ *   last kept token if rounding leaves none; out_logp[r] = logf(e[i] / s), its log-probability under the kept distribution.
+ * u: one fp32 uniform in [0, 1) per row, on the device.  This does NOT reproduce torch.multinomial's random stream: what it
+ * reproduces is the kept set, the kept probabilities and an inverse-CDF draw on the supplied uniform.  top_k = 1 is the argmax
+ * (greedy) whatever u is.  No atomics; a row's result does not depend on the other rows of the launch.
+ * Before any launch: null pointers, rows / vocab < 1, ld < vocab, temperature not in (0, inf), top_p not in (0, 1] -> SASPA_EINVAL;
+ * top_k outside 1 .. 64 -> SASPA_ERANGE; logits not 16-byte aligned, ld % 4 != 0, u / out_tok / out_logp not 4-byte aligned ->
+ * SASPA_EALIGN. */
+#define SASPA_SAMPLE_MAX_TOPK 64
+int saspa_sample_topk(const float* logits, int ld, int vocab, int rows, float temperature, int top_k, float top_p, const float* u,
+                      int* out_tok, float* out_logp, void* stream);
+
 int saspa_abi_version(void);
 /* the dtype code of the library's 16-bit element type: SASPA_BF16 (libsaspa_hip.so) or SASPA_F16 (libsaspa_hip_f16.so) */
 int saspa_half_type(void);

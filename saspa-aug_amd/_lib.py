@@ -12,6 +12,7 @@ SASPA_BF16, SASPA_F32, SASPA_F32X3 = 0, 1, 2
 SASPA_F16 = 3                                              # libsaspa_hip_f16.so only
 SASPA_EINVAL, SASPA_EALIGN, SASPA_ERANGE = -1, -2, -3      # include/saspa_hip.h
 DECODE_MAX_D, DECODE_MAX_NK, DECODE_MAX_GROUP = 128, 1024, 8  # SASPA_DECODE_MAX_*
+RMSNORM_MAX_C, RELBIAS_MAX_ROWS, SAMPLE_MAX_TOPK = 8192, 1024, 64   # SASPA_RMSNORM_MAX_C / SASPA_RELBIAS_MAX_ROWS / SASPA_SAMPLE_MAX_TOPK
 LPIPS_MAX_C, LPIPS_MAX_BLOCKS = 512, 64                    # SASPA_LPIPS_MAX_C / SASPA_LPIPS_MAX_BLOCKS
 CLASS_HEAD_MAX_D, CLASS_HEAD_MAX_C = 2048, 4096            # SASPA_CLASS_HEAD_MAX_D / SASPA_CLASS_HEAD_MAX_C
 ERRORS = {-1: "SASPA_EINVAL (null pointer / bad size)", -2: "SASPA_EALIGN (16-byte alignment / channel multiple)",
@@ -111,6 +112,16 @@ class DecodeAttnParams(C.Structure):
     ]
 
 
+class AttnRelbiasParams(C.Structure):
+    _fields_ = [
+        ("dtype", C.c_int), ("q", C.c_void_p), ("ldq", C.c_int), ("k", C.c_void_p), ("ldk", C.c_int), ("ske", C.c_longlong),
+        ("v", C.c_void_p), ("ldv", C.c_int), ("sve", C.c_longlong), ("len", C.c_void_p), ("pos", C.c_void_p),
+        ("bias", C.c_void_p), ("ldb", C.c_int), ("ncol", C.c_int), ("center", C.c_int), ("out", C.c_void_p), ("ldo", C.c_int),
+        ("rows", C.c_int), ("entries", C.c_int), ("heads", C.c_int), ("d", C.c_int), ("nk", C.c_int), ("rows_per_entry", C.c_int),
+        ("scale", C.c_float),
+    ]
+
+
 class HedFuseParams(C.Structure):
     _fields_ = [
         ("nmaps", C.c_int), ("n", C.c_int), ("H", C.c_int), ("W", C.c_int),
@@ -191,6 +202,9 @@ SYMBOLS = {
     "saspa_png_deflate": (_I, [_P, _I, _I, _I, _I, _P, _LL, _P, _P, _LL, _P]),
     "saspa_decode_attn": (_I, [C.POINTER(DecodeAttnParams), _P]),
     "saspa_logprob_topk": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _P, _P]),
+    "saspa_rmsnorm": (_I, [_I, _P, _I, _P, _I, _I, _I, _P, C.c_float, _P]),
+    "saspa_attn_relbias": (_I, [C.POINTER(AttnRelbiasParams), _P]),
+    "saspa_sample_topk": (_I, [_P, _I, _I, _I, C.c_float, _I, C.c_float, _P, _P, _P, _P]),
     "saspa_abi_version": (_I, []),
     "saspa_half_type": (_I, []),
     "saspa_build_arch": (C.c_char_p, []),

@@ -79,6 +79,28 @@ def tiny_blip_caption(**kw):
                      bos=94, eos=2, pad=0, prompt="a picture of ", num_beams=3, max_length=12, min_length=6), **kw)
 
 
+# T5 key-to-text generator behind PROMPT_TYPE = "txt2sentence" (prompts_engineering/txt2sentance_prompts.py of the reference: keytotext's
+# pipeline("mrm8488/t5-base-finetuned-common_gen")).  The architecture values are those of the public t5-base config (T5 v1.0: ReLU
+# feed-forward, no biases, RMS norms, relative-position buckets in block 0 of each stack, tied embeddings with the d_model ** -0.5
+# logit scale); tests pin the arithmetic against transformers' T5ForConditionalGeneration.
+# RECALLED, not verified (keytotext is not installed anywhere this was written): `join` / `strip` -- the wrapper joins the keywords
+# into one string and strips list punctuation before tokenising; `top_k` / `top_p` / `temperature` / `max_length` -- passing any
+# generate kwarg (the reference passes do_sample=True) bypasses the wrapper's beam-search defaults, so sampling runs on transformers'
+# defaults; `max_input` -- the encoder cap of this port (T5 itself has no position limit).
+T5_COMMON_GEN = dict(
+    d_model=768, enc_layers=12, dec_layers=12, heads=12, d_kv=64, d_ff=3072, vocab=32128, buckets=32, max_distance=128, eps=1e-6,
+    tie_embeddings=True, pad=0, decoder_start=0, eos=1, max_input=64,
+    join=" ", strip="[]'\",", top_k=50, top_p=1.0, temperature=1.0, max_length=20,          # RECALLED
+)
+
+
+def tiny_t5(**kw):
+    """`T5_COMMON_GEN` at reduced width with the same topology (tests): 2 + 2 layers, d_model 64, 4 heads of 16, 8 buckets with max
+    distance 16 -- sequences of 20 tokens already reach the clamped bucket."""
+    return dict(dict(T5_COMMON_GEN, d_model=64, enc_layers=2, dec_layers=2, heads=4, d_kv=16, d_ff=128, vocab=128, buckets=8,
+                     max_distance=16), **kw)
+
+
 # ---- filter stage (SURVEY 8f f1; all_utils/utils.py:252-255, :306-323, :357-375) ----
 # OpenAI CLIP "RN50" (clip.load('RN50')): ModifiedResNet (3, 4, 6, 3) width 64 -> 2048 channels at 7x7, attention pool with
 # 32 heads -> 1024-d embedding; text tower 12 layers x 512 wide x 8 heads, context 77.  Recalled from the public model.py.

@@ -974,6 +974,106 @@ def logprob_topk(logits, vocab, group, scores, ban_token=-1, ban_on=False):
     return out_score, out_idx, buf
 
 
+def _rmsnorm_args(x2, o2, gamma, eps):
+    rows, c = x2.shape
+    return (_dt(x2), _ptr(x2), x2.stride(0) if rows > 1 else max(c, x2.stride(0)), _ptr(o2),
+            o2.stride(0) if rows > 1 else max(c, o2.stride(0)), rows, c, _ptr(gamma), float(eps), _stream())
+
+
+def rmsnorm(x, gamma, eps=1e-6, out=None):
+    """T5's RMS norm over the last dim (saspa_rmsnorm): x * rsqrt(mean(x^2) + eps) * gamma, no mean subtraction, no bias.  x [..., C]
+    with a contiguous last dim and a uniform row pitch, bf16 or fp32; gamma fp32 [C].  C % 8 == 0, C <= 8192."""
+    _check_dev(x, gamma, out)
+    _same_dtype("rmsnorm", x, out=out)
+    if gamma.dtype != torch.float32 or gamma.numel() < x.shape[-1] or not gamma.is_contiguous():
+        raise ValueError("rmsnorm: gamma must be a contiguous fp32 vector of C elements")
+    if x.stride(-1) != 1:
+        raise ValueError("rmsnorm: the last dim must be contiguous")
+    c = x.shape[-1]
+    x2 = x.reshape(-1, c) if x.dim() != 2 else x
+    if out is None:
+        out = torch.empty(x.shape, device=x.device, dtype=x.dtype)
+    o2 = out.view(-1, c) if out.dim() != 2 else out
+    lib = _L(_dt(x))
+    _launch("rmsnorm", 0.0, lambda: _lib.check(lib.saspa_rmsnorm(*_rmsnorm_args(x2, o2, gamma, eps)), "saspa_rmsnorm"),
+            (x2.shape[0], c))
+    return out
+
+
+def _attn_relbias_params(q, k, v, out, lens, pos, bias, center, heads, d, nk, rows_per_entry, scale):
+    p = _lib.AttnRelbiasParams()
+    p.dtype = _dt(q)
+    p.q, p.ldq = _ptr(q), q.stride(0)
+    p.k, p.ldk, p.ske = _ptr(k), k.stride(1), k.stride(0)
+    p.v, p.ldv, p.sve = _ptr(v), v.stride(1), v.stride(0)
+    p.len, p.pos = _ptr(lens), _ptr(pos)
+    p.bias, p.ldb, p.ncol, p.center = _ptr(bias), bias.stride(0), bias.shape[1], int(center)
+    p.out, p.ldo = _ptr(out), out.stride(0)
+    p.rows, p.entries, p.heads, p.d, p.nk, p.rows_per_entry = q.shape[0], k.shape[0], int(heads), int(d), int(nk), int(rows_per_entry)
+    p.scale = float(scale)
+    return p
+
+
+def attn_relbias(q, k, v, heads, nk, scale, pos, bias, center, *, rows_per_entry=1, lens=None, out=None):
+    """Attention with an additive relative-position bias (saspa_attn_relbias): decode_attn's operands (q [rows, >= heads*d] view, k / v
+    caches [entries, nk_max, >= heads*d] views, lens int32 per row or None) with row r reading entry r // rows_per_entry, pos int32
+    [rows] on the device (the queries' positions) and bias fp32 [heads, ncol]: the logit of key j is
+    scale * q.k_j + bias[head][clamp(pos[r] - j + center, 0, ncol - 1)].  -> out [rows, heads*d].  Anything the library refuses
+    (d % 8, d > 128, nk > 1024, rows_per_entry > 1024, alignment) raises with its SASPA_E* code, nothing is launched."""
+    _check_dev(q, k, v, lens, pos, bias, out)
+    _same_dtype("attn_relbias", q, k=k, v=v, out=out)
+    if q.dim() != 2 or k.dim() != 3 or v.dim() != 3 or q.stride(1) != 1 or k.stride(2) != 1 or v.stride(2) != 1:
+        raise ValueError("attn_relbias: q must be [rows, C] and k / v [entries, nk_max, C] with a contiguous last dim")
+    if k.shape[1] < nk or v.shape[1] < nk or v.shape[0] != k.shape[0]:
+        raise ValueError(f"attn_relbias: caches {tuple(k.shape)} / {tuple(v.shape)} do not hold {nk} keys per entry")
+    for name, t in (("lens", lens), ("pos", pos)):
+        if t is not None and (t.dtype != torch.int32 or t.numel() < q.shape[0] or not t.is_contiguous()):
+            raise ValueError(f"attn_relbias: {name} must be a contiguous int32 tensor with one entry per row")
+    if pos is None:
+        raise ValueError("attn_relbias: pos (the queries' positions) is required")
+    if bias.dtype != torch.float32 or bias.dim() != 2 or bias.shape[0] != heads or bias.stride(1) != 1:
+        raise ValueError(f"attn_relbias: bias must be fp32 [heads = {heads}, ncol] with a contiguous last dim")
+    c = k.shape[2]
+    if c % heads or q.shape[1] < c:
+        raise ValueError(f"attn_relbias: {c} cache channels do not split into {heads} heads of the query's width {q.shape[1]}")
+    d = c // heads
+    if out is None:
+        out = torch.empty((q.shape[0], c), device=q.device, dtype=q.dtype)
+    p = _attn_relbias_params(q, k, v, out, lens, pos, bias, center, heads, d, nk, rows_per_entry, scale)
+    lib = _L(p.dtype)
+    _launch("attn_relbias", 4.0 * q.shape[0] * heads * nk * d,
+            lambda: _lib.check(lib.saspa_attn_relbias(C.byref(p), _stream()), "saspa_attn_relbias"), (q.shape[0], heads, 1, nk, d))
+    return out
+
+
+def _sample_topk_args(logits, vocab, temperature, top_k, top_p, u, tok, logp):
+    rows = logits.shape[0]
+    return (_ptr(logits), logits.stride(0) if rows > 1 else logits.shape[1], int(vocab), rows, float(temperature), int(top_k),
+            float(top_p), _ptr(u), _ptr(tok), _ptr(logp), _stream())
+
+
+def sample_topk(logits, vocab, u, *, temperature=1.0, top_k=50, top_p=1.0):
+    """One sampling step (saspa_sample_topk): fp32 logits [rows, ld >= vocab] (pad columns ignored), u fp32 [rows] uniforms in [0, 1)
+    on the device; temperature -> top-k (<= 64, clamped to vocab; ties to the lowest id) -> top-p -> inverse-CDF draw on u.
+    -> (token int32 [rows], log-probability under the kept distribution fp32 [rows], buf): the first two are views of `buf` (int32
+    [2, rows]), so that the host fetches a step's result with a single copy.  top_k = 1 is greedy."""
+    _check_dev(logits, u)
+    if logits.dtype != torch.float32 or u.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise TypeError("sample_topk takes fp32 logits [rows, ld] and fp32 uniforms")
+    rows = logits.shape[0]
+    if u.numel() != rows or not u.is_contiguous():
+        raise ValueError(f"sample_topk: {u.numel()} uniforms for {rows} rows")
+    if logits.shape[1] < vocab:
+        raise ValueError(f"sample_topk: rows of {logits.shape[1]} columns do not hold a vocabulary of {vocab}")
+    buf = torch.empty((2, rows), device=logits.device, dtype=torch.int32)
+    tok, logp = buf[0], buf[1].view(torch.float32)
+    lib = _L()
+    _launch("sample_topk", 0.0,
+            lambda: _lib.check(lib.saspa_sample_topk(*_sample_topk_args(logits, vocab, temperature, top_k, top_p, u, tok, logp)),
+                               "saspa_sample_topk"), (rows, int(vocab), int(top_k)))
+    return tok, logp, buf
+
+
 def softmax_rows(x, n, scale, causal=False, rows_per_mat=1):
     """In-place softmax(scale*x) over the first n columns of [rows, ld]; pad columns zeroed."""
     _check_dev(x)

@@ -191,3 +191,104 @@ def make_bert_tokenizer(vocab_dir=None, vocab=30523):
     if vocab_dir and os.path.exists(os.path.join(vocab_dir, "vocab.txt")):
         return BertWordPieceTokenizer(os.path.join(vocab_dir, "vocab.txt"))
     return BertHashTokenizer(vocab)
+
+
+# ---- T5 Unigram tokenizer of the key-to-text generator (txt2sentence.py) --------------------------------------------------------
+class UnigramTokenizer:
+    """SentencePiece Unigram as T5 uses it, from the checkpoint's `tokenizer.json` (plain JSON: model.vocab = [[piece, score], ...],
+    model.unk_id): NFKC normalisation, whitespace collapsed, every word prefixed with U+2581, then per word the segmentation of
+    highest total score (Viterbi over the piece scores; the first best path wins a tie; a character no piece covers costs the lowest
+    score - 10 and runs of such characters fuse into one <unk>, as `tokenizers`' Unigram does), and `</s>` appended.  decode() joins the
+    pieces and turns U+2581 back into spaces.
+
+    APPROXIMATED: SentencePiece normalises with a precompiled character map (nmt_nfkc); here that is `unicodedata.normalize("NFKC")`.
+    The two agree on ASCII and Latin-1 text (tests/test_t5_host.py compares ids with `tokenizers` on such input) and may differ on
+    rarer code points (some control and zero-width characters).
+
+    Without a tokenizer.json (a synthetic-weight run has no vocabulary) it is a hash stand-in like the other towers': every
+    lower-cased word maps to a stable id above the special ids, decode() writes "t<id>" per token.  NOT a T5 vocabulary."""
+
+    SPACE = "▁"
+
+    def __init__(self, path=None, vocab_size=32128, eos=1, pad=0):
+        self.eos, self.pad = eos, pad
+        self.pieces = None
+        self.vocab_size = vocab_size
+        if path is None:
+            return
+        with open(path, encoding="utf-8") as f:
+            tj = json.load(f)
+        model = tj["model"]
+        if model.get("type", "Unigram") != "Unigram":
+            raise ValueError(f"{path}: a {model.get('type')} tokenizer, not Unigram")
+        self.vocab = [(p, float(s)) for p, s in model["vocab"]]
+        self.vocab_size = len(self.vocab)
+        self.unk = model.get("unk_id")
+        self.pieces = {}
+        for i, (p, s) in enumerate(self.vocab):
+            self.pieces.setdefault(p, (i, s))
+        self.max_piece = max(len(p) for p, _ in self.vocab)
+        self.unk_score = min(s for _, s in self.vocab) - 10.0
+        self.special = {p for p in ("<pad>", "</s>", "<unk>")} | {t["content"] for t in tj.get("added_tokens", []) if t.get("special")}
+        if "</s>" in self.pieces:
+            self.eos = self.pieces["</s>"][0]
+
+    @classmethod
+    def normalize(cls, text):
+        return " ".join(unicodedata.normalize("NFKC", text or "").split())
+
+    def _word(self, w):
+        """Viterbi over one word (already prefixed): -> ids."""
+        n = len(w)
+        best = [(-1e300, -1, -1)] * (n + 1)          # (score, start, id) of the best path ending at i
+        best[0] = (0.0, -1, -1)
+        for b in range(n):
+            sb = best[b][0]
+            if sb <= -1e300:
+                continue
+            single = False
+            for e in range(b + 1, min(n, b + self.max_piece) + 1):
+                hit = self.pieces.get(w[b:e])
+                if hit is None:
+                    continue
+                single = single or e == b + 1
+                if sb + hit[1] > best[e][0]:
+                    best[e] = (sb + hit[1], b, hit[0])
+            if not single and sb + self.unk_score > best[b + 1][0]:
+                best[b + 1] = (sb + self.unk_score, b, self.unk)
+        ids, i = [], n
+        while i > 0:
+            _, b, t = best[i]
+            ids.append(t)
+            i = b
+        ids.reverse()
+        fused = []
+        for t in ids:                                 # runs of <unk> fuse
+            if not (t == self.unk and fused and fused[-1] == self.unk):
+                fused.append(t)
+        return fused
+
+    def encode(self, text, add_eos=True):
+        """text -> list of ids, `</s>` appended."""
+        words = self.normalize(text).split(" ") if self.normalize(text) else []
+        if self.pieces is None:
+            lo = 3
+            ids = [lo + zlib.crc32(w.lower().encode()) % (self.vocab_size - lo) for w in words]
+        else:
+            ids = [t for w in words for t in self._word(self.SPACE + w)]
+        return ids + ([self.eos] if add_eos else [])
+
+    def __call__(self, text):
+        return np.asarray(self.encode(text), np.int64)[None]
+
+    def decode(self, ids, skip_special_tokens=True):
+        ids = [int(i) for i in ids]
+        if self.pieces is None:
+            return " ".join(f"t{i}" for i in ids if not (skip_special_tokens and i < 3))
+        out = []
+        for i in ids:
+            p = self.vocab[i][0] if 0 <= i < len(self.vocab) else "<unk>"
+            if skip_special_tokens and p in self.special:
+                continue
+            out.append(p)
+        return "".join(out).replace(self.SPACE, " ").strip()

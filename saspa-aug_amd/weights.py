@@ -351,6 +351,72 @@ def blip_caption_from_lavis(sd):
     return blip_caption_from_transformers(out)
 
 
+def t5_keys(cfg):
+    """[(name, shape, kind)] of a T5 v1.0 encoder-decoder in the public transformers layout (T5ForConditionalGeneration.state_dict()
+    without the tied copies encoder.embed_tokens / decoder.embed_tokens): no biases anywhere, the relative-position table in block 0
+    of each stack only.  kind: "emb" | "q" | "w" (other projections; fan-in = shape[1]) | "rel" | "gain" | "gain_out"."""
+    d, inner, ff = cfg["d_model"], cfg["heads"] * cfg["d_kv"], cfg["d_ff"]
+    spec = [("shared.weight", (cfg["vocab"], d), "emb")]
+
+    def attn(pfx, rel):
+        out = [(f"{pfx}.q.weight", (inner, d), "q"), (f"{pfx}.k.weight", (inner, d), "w"), (f"{pfx}.v.weight", (inner, d), "w"),
+               (f"{pfx}.o.weight", (d, inner), "w")]
+        return out + ([(f"{pfx}.relative_attention_bias.weight", (cfg["buckets"], cfg["heads"]), "rel")] if rel else [])
+
+    for stack, layers in (("encoder", cfg["enc_layers"]), ("decoder", cfg["dec_layers"])):
+        for i in range(layers):
+            b = f"{stack}.block.{i}.layer"
+            spec += attn(f"{b}.0.SelfAttention", i == 0) + [(f"{b}.0.layer_norm.weight", (d,), "gain")]
+            j = 1
+            if stack == "decoder":
+                spec += attn(f"{b}.1.EncDecAttention", False) + [(f"{b}.1.layer_norm.weight", (d,), "gain")]
+                j = 2
+            spec += [(f"{b}.{j}.DenseReluDense.wi.weight", (ff, d), "w"), (f"{b}.{j}.DenseReluDense.wo.weight", (d, ff), "w"),
+                     (f"{b}.{j}.layer_norm.weight", (d,), "gain")]
+        spec.append((f"{stack}.final_layer_norm.weight", (d,), "gain_out" if stack == "decoder" else "gain"))
+    if not cfg["tie_embeddings"]:
+        spec.append(("lm_head.weight", (cfg["vocab"], d), "emb"))
+    return spec
+
+
+def t5_synth_state_dict(cfg, seed=0):
+    """Seeded synthetic T5 weights in the public key layout.  NOT transformers' default init: with it (embeddings of std 1, projections
+    scaled down by a further d_kv ** -0.5) the residual stream of a shallow model is its start token's embedding, the tied LM head
+    reads that embedding back, and the tiny model emits id 0 for ever.  Chosen instead: every projection at unit gain (std =
+    fan_in ** -0.5, q included: T5 has no 1 / sqrt(d_kv) in its logits, so attention is sharp), embeddings of std 0.05 (the sub-layers'
+    outputs, not the token's own embedding, dominate the stream: at 0.25 the tied head still reads the last token back and greedy
+    sequences repeat it), relative-position tables of std 1, norm gains 1 +- 0.1, and the decoder's final gain around 40 so that
+    the logits spread over a few units -- greedy and sampled sequences then vary with the input and from step to step."""
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    for name, shape, kind in t5_keys(cfg):
+        r = torch.randn(shape, generator=g)
+        if kind == "emb":
+            sd[name] = 0.05 * r
+        elif kind in ("q", "w"):
+            sd[name] = r * shape[1] ** -0.5
+        elif kind == "rel":
+            sd[name] = r
+        else:
+            sd[name] = (40.0 if kind == "gain_out" else 1.0) * (1.0 + 0.1 * r)
+    return sd
+
+
+def t5_from_hf(sd, cfg):
+    """A T5ForConditionalGeneration state dict (public layout) -> fp32 tensors under the names of t5_keys: the tied copies
+    (encoder.embed_tokens / decoder.embed_tokens, and lm_head under tied embeddings) dropped, every expected name and shape checked --
+    a missing or misshapen tensor raises here, not at pack time."""
+    out = {}
+    for name, shape, _ in t5_keys(cfg):
+        if name not in sd:
+            raise KeyError(f"T5 checkpoint lacks {name}")
+        t = sd[name].detach().float()
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"T5 checkpoint: {name} is {tuple(t.shape)}, the config says {tuple(shape)}")
+        out[name] = t.contiguous()
+    return out
+
+
 SPECS = dict(blip_caption=blip_caption_spec, safety=safety_checker_spec, unet=unet_spec, controlnet=controlnet_spec, vae=vae_decoder_spec, text=clip_text_spec, text2=clip_text_spec,
              qformer=blip2_qformer_spec)
 

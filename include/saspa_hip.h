@@ -537,6 +537,27 @@ int saspa_lpips_layer(int dtype, const void* a, int lda, const void* r, int ldr,
 #define SASPA_CLASS_HEAD_MAX_C 4096
 int saspa_class_head(const float* feat, int ldf, const float* cls, int ldc, const int* labels, float scale, int normalize,
                      float* stats, int* idx, float* logits, int ldl, int rows, int D, int C, void* stream);
+/* The in-line filter stage (Settings.FILTER_INLINE): one threshold-free score record per augmented image, written while the batch is
+ * still on the device; `filters.decide` makes every decision of the post-hoc stage from the records, on the host, for any top_k /
+ * too_high / discount / semantic setting.  One launch per batch, one wave per image.  Row slot[b] of table [n_rows][8] fp32 becomes
+ *   0 valid          bit 0 semantic, bit 1 confidence, bit 2 per-class: which of the fields below were recorded (an exact float)
+ *   1 sem_argmax     numpy's argmax of sem[b][0..P): equal logits give the lowest index, a NaN counts as the maximum, the first one wins
+ *   2 sem_margin     sem[b][0] - max(sem[b][1..P)) as one fp32 subtraction; +inf when P == 1; every NaN result is the canonical quiet NaN
+ *   3 conf_n_greater (float)conf_idx[2 b + 1]   4 conf_p_label  conf_stats[4 b + 1]     (saspa_class_head in logits mode)
+ *   5 pc_p_label     pc_stats[4 b + 1]           6 pc_n_greater  (float)pc_idx[2 b + 1]  (saspa_class_head in embedding mode)
+ *   7 reserved, 0
+ * sem (fp32 [rows][ld], P <= SASPA_FILTER_RECORD_MAX_P prompts, one lane each), the (conf_stats, conf_idx) pair and the (pc_stats,
+ * pc_idx) pair are each optional: NULL = that filter is off, its fields are NaN and its valid bit is clear.  bad (optional, rows
+ * bytes): a non-zero bad[b] gives valid = 0 and NaN fields.  slot: rows DEVICE int32, distinct, each in [0, n_rows) -- the CALLER
+ * checks them (ops.filter_record does, on the host, before anything is uploaded); a slot outside the table is dropped, not written.
+ * The (value, index) reduction is an xor butterfly over a total order, so the record does not depend on the batch size or on the
+ * image's place in the batch.  Plain stores, no atomics, no row but slot[b] is touched, the host is not read.
+ * Host-side validation: null slot / table, rows < 1, n_rows < 1 or half a (stats, idx) pair -> SASPA_EINVAL; P < 1, P >
+ * SASPA_FILTER_RECORD_MAX_P, ld < P or rows > n_rows -> SASPA_ERANGE; table not 16-byte, another pointer not 4-byte aligned ->
+ * SASPA_EALIGN. */
+#define SASPA_FILTER_RECORD_MAX_P 64
+int saspa_filter_record(const float* sem, int ld, int P, const float* conf_stats, const int* conf_idx, const float* pc_stats,
+                        const int* pc_idx, const unsigned char* bad, const int* slot, float* table, int n_rows, int rows, void* stream);
 
 /* ---- cv2.resize, 8-bit RGB [n][h][w][3] -> [n][dh][dw][3] (all_utils/utils.py:58-79 `resize_image`) -------
  * saspa_resize_taps_u8: OpenCV's separable fixed-point filters; xofs / yofs = first tap index per destination sample,

@@ -97,7 +97,7 @@ if __name__ == "__main__":
                    PRECISION=os.environ.get("SASPA_PRECISION", "bf16"), WEIGHTS_DIR=os.environ.get("SASPA_WEIGHTS_DIR"),
                    PROMPTS_FILE=os.environ.get("SASPA_PROMPTS_FILE"), PNG_DEVICE=os.environ.get("SASPA_PNG_DEVICE", "0") == "1",
                    FP16=os.environ.get("SASPA_FP16", "0") == "1", FP16_VAE=os.environ.get("SASPA_FP16_VAE", "bf16"),
-                   XL_VAE=os.environ.get("SASPA_XL_VAE") or None)
+                   XL_VAE=os.environ.get("SASPA_XL_VAE") or None, FILTER_INLINE=os.environ.get("SASPA_FILTER_INLINE", "0") == "1")
     assert s.DATASET in R.dataset_utils.DATASETS_SUPPORTED
     assert s.BASE_MODEL in R.BASE_MODEL_DICT.keys()
     assert s.NUM_PER_IMAGE > 0

@@ -50,7 +50,8 @@ def real_guidance_settings(env=None):
         FOLDER_STEPS_GS_SUFFIX=True, BATCH_SIZE=8, PRECISION=env.get("SASPA_PRECISION", "bf16"),
         WEIGHTS_DIR=env.get("SASPA_WEIGHTS_DIR"), PROMPTS_FILE=env.get("SASPA_PROMPTS_FILE"),
         PNG_DEVICE=env.get("SASPA_PNG_DEVICE", "0") == "1",
-        FP16=env.get("SASPA_FP16", "0") == "1", FP16_VAE=env.get("SASPA_FP16_VAE", "bf16"))
+        FP16=env.get("SASPA_FP16", "0") == "1", FP16_VAE=env.get("SASPA_FP16_VAE", "bf16"),
+        FILTER_INLINE=env.get("SASPA_FILTER_INLINE", "0") == "1")
 
 
 if __name__ == "__main__":

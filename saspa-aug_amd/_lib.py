@@ -15,6 +15,7 @@ DECODE_MAX_D, DECODE_MAX_NK, DECODE_MAX_GROUP = 128, 1024, 8  # SASPA_DECODE_MAX
 RMSNORM_MAX_C, RELBIAS_MAX_ROWS, SAMPLE_MAX_TOPK = 8192, 1024, 64   # SASPA_RMSNORM_MAX_C / SASPA_RELBIAS_MAX_ROWS / SASPA_SAMPLE_MAX_TOPK
 LPIPS_MAX_C, LPIPS_MAX_BLOCKS = 512, 64                    # SASPA_LPIPS_MAX_C / SASPA_LPIPS_MAX_BLOCKS
 CLASS_HEAD_MAX_D, CLASS_HEAD_MAX_C = 2048, 4096            # SASPA_CLASS_HEAD_MAX_D / SASPA_CLASS_HEAD_MAX_C
+FILTER_RECORD_MAX_P, FILTER_RECORD_FIELDS = 64, 8          # SASPA_FILTER_RECORD_MAX_P; fp32 per record
 ERRORS = {-1: "SASPA_EINVAL (null pointer / bad size)", -2: "SASPA_EALIGN (16-byte alignment / channel multiple)",
           -3: "SASPA_ERANGE (unsupported shape)"}
 
@@ -175,6 +176,7 @@ SYMBOLS = {
     "saspa_signsqrt_l2norm": (_I, [_P, _LL, _P, _LL, _I, _LL, _F, _F, _P]),
     "saspa_lpips_layer": (_I, [_I, _P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "saspa_class_head": (_I, [_P, _I, _P, _I, _P, _F, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "saspa_filter_record": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "saspa_resize_taps_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P]),
     "saspa_hed_fuse": (_I, [C.POINTER(HedFuseParams), _P]),
     "saspa_gemm_fp8": (_I, [C.POINTER(GemmF8Params), _P]),

@@ -777,3 +777,217 @@ def apply_filters(mapping, original_images_paths, ds_utils, dev, semantic=None, 
                 keep[ap] = bool(c_ok and not h_bad and l_ok and p_ok and s_ok)
     out = {name: [ap for ap in aps if keep[ap]] for name, aps in mapping.items()}
     return out, counters
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the in-line form of the stage (Settings.FILTER_INLINE): threshold-free scores recorded while generating, decisions on the host
+# ---------------------------------------------------------------------------------------------------------------------
+RECORD_FIELDS = ("valid", "sem_argmax", "sem_margin", "conf_n_greater", "conf_p_label", "pc_p_label", "pc_n_greater", "reserved")
+VALID_SEMANTIC, VALID_CONFIDENCE, VALID_PER_CLASS = 1, 2, 4
+SCORES_FILE = "filter_scores.json"
+SCORES_VERSION = 1
+
+
+def decide(records, *, semantic, top_k, too_high, pc_threshold):
+    """The decisions of `apply_filters` from score records, on the host, without a GPU.  records: fp32 [n, 8] (the fields of
+    `saspa_filter_record`).  semantic: apply the semantic filter; top_k: the classifier's k, None = the confidence filter is off;
+    too_high: its upper bound on softmax(label) or None; pc_threshold: the per-class CLIP filter's threshold, None = off.
+    -> (keep mask bool [n], counters) with the comparisons and the order of attribution of `apply_filters`: top-k
+    (`conf_n_greater < top_k`), too-high (`float64(conf_p_label) > too_high`, only where top-k passed), per-class
+    (`float64(pc_p_label) >= pc_threshold`), semantic (`sem_argmax == 0`); a dropped image counts once, under the first that drops it.
+    A record that lacks a score an enabled filter needs (its `valid` bit is clear, or the row is still NaN) is a ValueError."""
+    rec = np.asarray(records, dtype=np.float32).reshape(-1, len(RECORD_FIELDS))
+    n = rec.shape[0]
+    too_high = too_high or None                                  # `if filter_confidence_higher_than:` (ConfidenceFilter)
+    need = (VALID_SEMANTIC if semantic else 0) | (VALID_CONFIDENCE if top_k is not None else 0) | (VALID_PER_CLASS if pc_threshold is not None else 0)
+    valid = np.where(np.isnan(rec[:, 0]), 0, rec[:, 0]).astype(np.int64)
+    lacking = np.nonzero((valid & need) != need)[0]
+    if lacking.size:
+        raise ValueError(f"{lacking.size} of {n} records lack a score the enabled filters need (first: row {int(lacking[0])}, valid = {int(valid[lacking[0]])}, needed {need})")
+    ok_c, high = np.ones(n, bool), np.zeros(n, bool)
+    counters = dict(not_in_top_k=0, semantic=0)
+    if top_k is not None:
+        ok_c = rec[:, 3] < top_k
+        if too_high is not None:
+            counters["too_high_confidence"] = 0
+            high = (rec[:, 4].astype(np.float64) > too_high) & ok_c
+    ok_p = np.ones(n, bool)
+    if pc_threshold is not None:
+        counters["clip_filtering"] = 0
+        ok_p = rec[:, 5].astype(np.float64) >= pc_threshold
+    ok_s = rec[:, 1] == 0 if semantic else np.ones(n, bool)
+    counters["not_in_top_k"] = int((~ok_c).sum())
+    if "too_high_confidence" in counters:
+        counters["too_high_confidence"] = int(high.sum())
+    alive = ok_c & ~high
+    if "clip_filtering" in counters:
+        counters["clip_filtering"] = int((alive & ~ok_p).sum())
+    alive &= ok_p
+    counters["semantic"] = int((alive & ~ok_s).sum())
+    return alive & ok_s, counters
+
+
+class FilterRecorder:
+    """The filter models over device-resident batches, scores kept on the device: `record` launches the towers, the heads and
+    `ops.filter_record` on the current stream and returns without synchronising; `table_host()` is the one synchronising read, after
+    the loop.  Owns the table fp32 [n_rows, 8], NaN = "no record".  The same object scores the batches of the generation loop and the
+    PNGs of the backfill, so there is ONE scoring path.  The models keep their dtype: the scores are those of the post-hoc stage."""
+
+    def __init__(self, semantic, confidence, class_filter, n_rows, dev):
+        if semantic is None and confidence is None and class_filter is None:
+            raise ValueError("FilterRecorder needs at least one filter model")
+        self.semantic, self.confidence, self.class_filter, self.dev = semantic, confidence, class_filter, dev
+        self.shared_tower = class_filter is not None and semantic is not None and getattr(semantic, "visual", None) is class_filter.visual
+        self.n_rows = int(n_rows)
+        self.table = torch.full((self.n_rows, len(RECORD_FIELDS)), float("nan"), device=dev, dtype=torch.float32)
+
+    def reset(self, n_rows):
+        self.n_rows = int(n_rows)
+        self.table = torch.full((self.n_rows, len(RECORD_FIELDS)), float("nan"), device=self.dev, dtype=torch.float32)
+
+    @staticmethod
+    def _labels(labels, n, n_classes, what):
+        lb = np.asarray(labels).astype(np.int64).reshape(-1)
+        if lb.size != n or (lb.size and (lb.min() < 0 or lb.max() >= n_classes)):
+            raise ValueError(f"{what} labels must hold {n} values in [0, {n_classes})")
+        return lb.astype(np.int32)
+
+    @torch.no_grad()
+    def record(self, images_u8, conf_labels, pc_labels, slots, bad=None):
+        """device u8 [n,H,W,3]; conf_labels / pc_labels: host ints per image (ignored where that filter is off); slots: host ints, the
+        table rows; bad: device bool [n] of images to invalidate, or None.  Everything is validated before the first launch."""
+        n = images_u8.shape[0]
+        conf, cls, sem = self.confidence, self.class_filter, self.semantic
+        cl = self._labels(conf_labels, n, conf.model.num_classes, "classifier") if conf is not None else None
+        pl = self._labels(pc_labels, n, len(cls.class_names), "per-class") if cls is not None else None
+        c_pair = p_pair = s_logits = None
+        if conf is not None:
+            lg = conf.logits(images_u8).float()
+            stats, idx, _ = ops.class_head(lg, ops.h2d(torch.from_numpy(cl), lg.device), width=conf.model.num_classes)
+            c_pair = (stats, idx)
+        emb = cls.embed(images_u8) if self.shared_tower else None               # one image-tower pass for both CLIP filters
+        if cls is not None:
+            e = cls.embed(images_u8) if emb is None else emb
+            stats, idx, _ = ops.class_head(e, ops.h2d(torch.from_numpy(pl), e.device), cls.text_unit, cls.scale, True, width=cls.cfg["embed_dim"])
+            p_pair = (stats, idx)
+        if sem is not None:
+            s_logits = sem.logits(images_u8, embedding=emb) if self.shared_tower else sem.logits(images_u8)
+        ops.filter_record(self.table, slots, s_logits, c_pair, p_pair, bad)
+
+    def table_host(self):
+        return self.table.cpu().numpy()
+
+
+def recorder_header(semantic, confidence, class_filter, clip_source, cal_source):
+    """What the scores of a FilterRecorder depend on, as a JSON-able dict: where the weights came from (a checkpoint path, "synthetic",
+    or "handed in" for models the caller built), the prompts of the two CLIP filters (the positive prompt first; the class list through
+    its prompts), the classifier's class count, the dtypes.  Two runs may share records only when their headers are equal."""
+    h = dict(version=SCORES_VERSION, fields=list(RECORD_FIELDS))
+    if semantic is not None:
+        h["semantic"] = dict(weights=clip_source, prompts=list(semantic.prompts), dtype=str(semantic.dtype), image_size=semantic.cfg["image_size"])
+    if confidence is not None:
+        h["confidence"] = dict(weights=cal_source, num_classes=int(confidence.model.num_classes), dtype=str(confidence.dtype),
+                               image_size=confidence.cfg["image_size"])
+    if class_filter is not None:
+        h["per_class"] = dict(weights=clip_source, classes=list(class_filter.class_names), prompts=list(class_filter.prompts),
+                              scale=float(np.float32(class_filter.scale)), dtype=str(class_filter.dtype), image_size=class_filter.cfg["image_size"])
+    return h
+
+
+def scores_path(images_folder):
+    """`filter_scores.json` beside the aug JSONs: in the parent of `images/`."""
+    return str(Path(images_folder).parent / SCORES_FILE)
+
+
+def _enc(x):
+    x = np.float32(x)
+    if np.isnan(x):
+        return None
+    if np.isinf(x):
+        return "Infinity" if x > 0 else "-Infinity"              # (JSON has no literal for them; `sem_margin` of a one-prompt filter)
+    return float(x)                                               # fp32 -> double is exact and repr(double) round-trips
+
+
+def _dec(v):
+    return np.float32("nan") if v is None else np.float32(v)
+
+
+def save_scores(path, header, records, sizes):
+    """records: {png file name: 8 fp32}; sizes: {png file name: bytes of the PNG the record was taken from}."""
+    import json
+    body = dict(header=header, records={k: [_enc(x) for x in np.asarray(v, np.float32).reshape(-1)] for k, v in records.items()},
+                sizes={k: int(sizes[k]) for k in records})
+    tmp = str(path) + ".tmp"
+    with open(tmp, "w") as f:
+        json.dump(body, f, allow_nan=False)
+    os.replace(tmp, path)
+
+
+def load_scores(path):
+    """-> (header, {name: fp32 [8]}, {name: bytes}), or (None, {}, {}) when there is no sidecar."""
+    import json
+    if not os.path.exists(path):
+        return None, {}, {}
+    with open(path, "r") as f:
+        body = json.load(f)
+    recs = {k: np.array([_dec(x) for x in v], np.float32) for k, v in body.get("records", {}).items()}
+    return body.get("header"), recs, {k: int(v) for k, v in body.get("sizes", {}).items()}
+
+
+def merge_scores(images_folder, header, new_records):
+    """The sidecar of `images_folder` brought up to date and written: an existing one with an equal header is merged (new records replace
+    old ones), a different header discards the old records with a log line; a record whose PNG is gone or whose byte size differs is
+    dropped.  -> (records, sizes) as written."""
+    path = scores_path(images_folder)
+    old_header, records, sizes = load_scores(path)
+    if old_header is not None and old_header != header:
+        logging.info(f"{path}: written for other filter models / prompts (header differs) -- its {len(records)} records are discarded")
+        records, sizes = {}, {}
+    for name, rec in new_records.items():
+        records[name] = np.asarray(rec, np.float32).reshape(-1)
+        sizes.pop(name, None)
+    kept, kept_sizes = {}, {}
+    for name, rec in records.items():
+        try:
+            size = os.path.getsize(os.path.join(images_folder, name))
+        except OSError:
+            continue                                              # the PNG is gone
+        if name in sizes and sizes[name] != size:
+            continue                                              # another file now carries the name
+        kept[name], kept_sizes[name] = rec, size
+    if len(kept) != len(records):
+        logging.info(f"{path}: dropped {len(records) - len(kept)} stale records (PNG missing or of another size)")
+    save_scores(path, header, kept, kept_sizes)
+    return kept, kept_sizes
+
+
+def backfill_scores(recorder, missing, conf_label_of, pc_label_of, planned_batches=None, batch_size=32):
+    """Scores for PNGs that have no record -- files an earlier run wrote -- through the SAME `FilterRecorder.record` as the generation
+    loop, from decoded pixels.  missing: [png path]; `conf_label_of` / `pc_label_of`: path -> label (or None when the filter is off);
+    planned_batches: [[png path]] = the batches the generation loop would have formed: a missing image is scored with the missing images
+    of its planned batch, in that order; the rest is grouped by size into chunks of `batch_size`.  -> {png file name: fp32 [8]}."""
+    want = list(dict.fromkeys(missing))
+    left = set(want)
+    chunks = []
+    for b in planned_batches or ():
+        c = [p for p in b if p in left]
+        if c:
+            chunks.append(c)
+            left -= set(c)
+    groups = {}
+    for p in want:
+        if p in left:
+            groups.setdefault(_image_size(p), []).append(p)
+    chunks += [items[i:i + batch_size] for _, items in sorted(groups.items()) for i in range(0, len(items), batch_size)]
+    order = [p for c in chunks for p in c]
+    if not order:
+        return {}
+    recorder.reset(len(order))
+    row = 0
+    for c in chunks:
+        batch = ops.h2d(torch.from_numpy(np.stack([_load_u8(p) for p in c])), recorder.dev)
+        recorder.record(batch, [conf_label_of(p) for p in c] if conf_label_of else None, [pc_label_of(p) for p in c] if pc_label_of else None,
+                        list(range(row, row + len(c))))
+        row += len(c)
+    table = recorder.table_host()
+    return {Path(p).name: table[k].copy() for k, p in enumerate(order)}

@@ -1446,6 +1446,54 @@ def class_head(feat, labels, cls=None, scale=1.0, normalize=True, width=None, wa
     return stats, idx, (logits[:, :c] if want_logits else None)
 
 
+def filter_record(table, slots, sem=None, conf=None, pc=None, bad=None, n_prompts=None):
+    """One score record per image of a batch into rows `slots` of the run's table (saspa_filter_record; the fields are listed in
+    include/saspa_hip.h).  table: device fp32 [n_rows, 8], contiguous.  slots: HOST ints, one per image -- checked here, before anything
+    is uploaded: in [0, n_rows) and distinct (two images of a batch must never share a row).  sem: fp32 [n, >= P] semantic logits with a
+    contiguous last dim (`n_prompts` = P, default: every column; P <= 64); conf / pc: the (stats, idx) pairs of the classifier's and of
+    the per-class filter's `class_head` launch; bad: device bool [n], True = the image gets valid = 0.  Each of the three inputs may be
+    None: that filter is off, its fields stay NaN.  Stream-ordered; nothing here waits for the GPU.  -> table."""
+    import numpy as np
+    _check_dev(table, sem, bad, *(conf or ()), *(pc or ()))
+    f = _lib.FILTER_RECORD_FIELDS
+    if table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] != f or not table.is_contiguous() or table.shape[0] < 1:
+        raise ValueError(f"filter_record: the table is a contiguous fp32 [n_rows, {f}] device tensor")
+    n_rows = table.shape[0]
+    sl = np.asarray(slots)
+    if sl.ndim != 1 or sl.size < 1 or sl.dtype.kind not in "iu":
+        raise ValueError("filter_record: slots are a non-empty 1-D sequence of host integers")
+    sl = sl.astype(np.int64)
+    n = sl.size
+    if sl.min() < 0 or sl.max() >= n_rows:
+        raise ValueError(f"filter_record: slots must lie in [0, {n_rows}), got [{sl.min()}, {sl.max()}]")
+    if np.unique(sl).size != n:
+        raise ValueError("filter_record: two images of a batch share a slot")
+    ld = p = 0
+    if sem is not None:
+        if sem.dtype != torch.float32 or sem.dim() != 2 or sem.shape[0] != n or sem.stride(1) != 1:
+            raise ValueError(f"filter_record: sem is an fp32 [{n}, P] matrix with a contiguous last dim")
+        p = int(sem.shape[1] if n_prompts is None else n_prompts)
+        if p < 1 or p > sem.shape[1] or p > _lib.FILTER_RECORD_MAX_P:
+            raise ValueError(f"filter_record: one lane per prompt, 1 <= P <= {min(_lib.FILTER_RECORD_MAX_P, sem.shape[1])}, got {p}")
+        ld = sem.stride(0) if n > 1 else sem.shape[1]
+    for name, pair in (("conf", conf), ("pc", pc)):
+        if pair is None:
+            continue
+        st, ix = pair
+        if st.dtype != torch.float32 or tuple(st.shape) != (n, 4) or not st.is_contiguous():
+            raise ValueError(f"filter_record: {name} stats are the contiguous fp32 [{n}, 4] of class_head")
+        if ix.dtype != torch.int32 or tuple(ix.shape) != (n, 2) or not ix.is_contiguous():
+            raise ValueError(f"filter_record: {name} idx are the contiguous int32 [{n}, 2] of class_head")
+    if bad is not None and (bad.dtype != torch.bool or tuple(bad.shape) != (n,) or not bad.is_contiguous()):
+        raise ValueError(f"filter_record: bad is a contiguous bool [{n}] device tensor")
+    slot_d = h2d(torch.from_numpy(sl.astype(np.int32)), table.device)
+    cs, ci = conf if conf is not None else (None, None)
+    ps, pi = pc if pc is not None else (None, None)
+    _lib.check(_L().saspa_filter_record(_ptr(sem), ld, p, _ptr(cs), _ptr(ci), _ptr(ps), _ptr(pi), _ptr(bad), _ptr(slot_d), _ptr(table),
+                                        n_rows, n, _stream()), "saspa_filter_record")
+    return table
+
+
 def u8_luma(img_u8):
     """PIL convert("L").convert("RGB") of a device u8 [..., 3] tensor (saspa_u8_luma; integer exact)."""
     _check_dev(img_u8)

@@ -15,7 +15,8 @@ What is different by design (MI355X-first; results per work item are unchanged):
   * Canny runs once per source image on the GPU (the reference recomputes it per variant);
   * PNG encoding is asynchronous (thread pool) so it does not serialise the GPU;
   * one process per GPU (`torchrun`), no model parallelism; the only collective is one gather
-    of the per-item status vector to rank 0, which then writes the JSON manifest."""
+    of the per-item status vector to rank 0, which then writes the JSON manifest (with
+    FILTER_INLINE a second gather of the same size class carries the items' score records)."""
 import logging
 import os
 import random
@@ -185,6 +186,8 @@ class Settings:
     FP16_VAE: str = "bf16"             # with FP16: "bf16" keeps the VAE as it is, "x3" runs it on fp32 storage with SASPA_F32X3 GEMMs
     MAX_BATCHES: int = 0               # > 0: stop this rank after that many batches (rehearsals / diagnostics; the rest stays status 0)
     XL_VAE: str = None                 # sd_xl-turbo: pipe.set_vae_mode -- None (upcast_vae() decides: fp32 storage) | "x3" | "exact" | "bf16" | "f16"
+    FILTER_INLINE: bool = False        # score every batch for the semantic / confidence / per-class filters while it is on the device
+                                       # (filters.FilterRecorder); the JSON stage then decides from the records and decodes no PNG
 
 
 @dataclass
@@ -679,9 +682,11 @@ class _EncodedBatch:
         return self.streams[k, :int(self.sizes[k])].tobytes()
 
 
-def hip_batch_generator(pipe, s: Settings):
+def hip_batch_generator(pipe, s: Settings, record=None):
     """Returns fn(batch_items, noises[list of [1,4,h,w]], source_u8 [B,H,W,3]) -> (images u8
-    [B,H,W,3] numpy, control u8 [B,H,W,3] numpy), running Canny + sampling on the device."""
+    [B,H,W,3] numpy, control u8 [B,H,W,3] numpy), running Canny + sampling on the device.
+    `record` (FILTER_INLINE): fn(batch_items, images u8 [B,H,W,3] on the device, non-finite flags | None), called right behind the
+    generation on the same stream; it must not wait for the GPU."""
     from . import ops
     tok = pipe.tokenizer
     neg_ids = tok(NEGATIVE_PROMPT)
@@ -748,6 +753,8 @@ def hip_batch_generator(pipe, s: Settings):
                                       s.CONTROLNET_CONDITIONING_SCALE)
         # PNG_DEVICE: the two sets of files every batch writes are compressed right behind the generation, on the same stream
         enc = (ops.png_deflate(out), ops.png_deflate(src)) if s.PNG_DEVICE else None
+        if record is not None:
+            record(batch, out, getattr(pipe, "last_nonfinite", None))
         ev = torch.cuda.Event()
         ev.record()
         # SDXL, VAE mode "f16": per-image flags of a non-finite decoder output (device bool [B]); None in every other mode
@@ -847,25 +854,83 @@ def host_threads(local_world=1):
     return max(1, min(4, n // max(1, int(local_world))))
 
 
+def _inline_recorder(s, ds_utils, filter_models, class_filter, filter_recorder, need_two, need_class, n_rows):
+    """FILTER_INLINE: the filter models, built here on s.DEVICE (every rank scores its own batches) or taken from the caller, behind one
+    `filters.FilterRecorder` with a row per item of this rank -> (recorder, header of the score sidecar)."""
+    from . import filters as _filters
+    if filter_recorder is not None:
+        filter_recorder.reset(max(1, n_rows))
+        return filter_recorder, _filters.recorder_header(filter_recorder.semantic, filter_recorder.confidence, filter_recorder.class_filter,
+                                                         "handed in", "handed in")
+    dev = torch.device(s.DEVICE)
+    sem, conf = filter_models if filter_models is not None else (None, None)
+    clip_src = cal_src = "handed in"
+    if need_two or need_class:
+        rn, cp = _filters.filter_checkpoints(ds_utils, s.WEIGHTS_DIR, bool(s.SEMANTIC_FILTERING) and need_two,
+                                             bool(s.MODEL_CONFIDENCE_BASED_FILTERING) and need_two, per_class=need_class)
+        built = _filters.build_filters(ds_utils, dev, bool(s.SEMANTIC_FILTERING) and need_two,
+                                       bool(s.MODEL_CONFIDENCE_BASED_FILTERING) and need_two, s.WEIGHTS_DIR, per_class=need_class,
+                                       discount=s.CLIP_FILTERING_DISCOUNT)
+        if need_two:
+            sem, conf = built[:2]
+            cal_src = cp or "synthetic"
+        if need_class:
+            class_filter = built[2]
+        if (need_two and s.SEMANTIC_FILTERING) or need_class:
+            clip_src = rn or "synthetic"
+    sem = sem if s.SEMANTIC_FILTERING else None
+    conf = conf if s.MODEL_CONFIDENCE_BASED_FILTERING else None
+    class_filter = class_filter if s.CLIP_FILTERING_TYPE else None
+    recorder = _filters.FilterRecorder(sem, conf, class_filter, max(1, n_rows), dev)
+    return recorder, _filters.recorder_header(sem, conf, class_filter, clip_src, cal_src)
+
+
+def gather_records(items, mine, table, world, rank, dist, device):
+    """The second collective of a FILTER_INLINE run.  table: this rank's fp32 [len(mine), 8] score rows (row k = mine[k]), or None.
+    Every rank places its rows at `it.order` in an [n_items, 8] tensor -- NaN = no record; an item that did not end with status 1
+    keeps NaN -- and one gather carries them to rank 0 (13 336 items: 427 KB), which takes from each rank the rows of its shard.
+    -> fp32 [n_items, 8] numpy on rank 0 (on every rank without `dist`), None elsewhere."""
+    rec = torch.full((len(items), 8), float("nan"), dtype=torch.float32)
+    for k, it in enumerate(mine):
+        if it.status == 1:
+            rec[it.order] = torch.from_numpy(np.asarray(table[k], np.float32))
+    if dist is None:
+        return rec.numpy()
+    dev = torch.device(device) if dist.get_backend() == "nccl" else torch.device("cpu")
+    r = rec.to(dev)
+    gathered = [torch.empty_like(r) for _ in range(world)] if rank == 0 else None
+    dist.gather(r, gathered, dst=0)
+    if rank != 0:
+        return None
+    out = torch.full_like(rec, float("nan"))
+    for shard, g in zip(shard_items(items, world), gathered):
+        rows = [it.order for it in shard]
+        if rows:
+            out[rows] = g.cpu()[rows]
+    return out.numpy()
+
+
 def main(s: Settings, ds_utils=None, batch_generator=None, dist=None, pipe=None, filter_models=None, lpips_model=None,
-         class_filter=None):
+         class_filter=None, filter_recorder=None):
     """`_main` with torch's CPU pool held at `host_threads()` for the duration of the run (restored afterwards)."""
     world = dist.get_world_size() if dist is not None else 1
     before = torch.get_num_threads()
     torch.set_num_threads(host_threads(int(os.environ.get("LOCAL_WORLD_SIZE", world))))
     try:
         return _main(s, ds_utils=ds_utils, batch_generator=batch_generator, dist=dist, pipe=pipe, filter_models=filter_models,
-                     lpips_model=lpips_model, class_filter=class_filter)
+                     lpips_model=lpips_model, class_filter=class_filter, filter_recorder=filter_recorder)
     finally:
         torch.set_num_threads(before)
 
 
 def _main(s: Settings, ds_utils=None, batch_generator=None, dist=None, pipe=None, filter_models=None, lpips_model=None,
-          class_filter=None):
+          class_filter=None, filter_recorder=None):
     """The generation loop.  `batch_generator` is injectable for host-logic tests; the default
     builds the HIP pipeline (fails loudly without an MI355X).  `filter_models` = (SemanticFilter | None,
     ConfidenceFilter | None) to reuse built filter models; None builds them on s.DEVICE when a filter flag is set.
-    `class_filter`: a built ClassFilter for CLIP_FILTERING_TYPE = "per_class", likewise."""
+    `class_filter`: a built ClassFilter for CLIP_FILTERING_TYPE = "per_class", likewise.  `filter_recorder` (FILTER_INLINE): a built
+    recorder (anything with `record`, `table_host`, `reset` and the three model attributes of filters.FilterRecorder) to use instead
+    of one over the filter models."""
     rank = dist.get_rank() if dist is not None else 0
     world = dist.get_world_size() if dist is not None else 1
     png = _PngWriters(4)
@@ -905,6 +970,13 @@ def _main(s: Settings, ds_utils=None, batch_generator=None, dist=None, pipe=None
         raise NotImplementedError(f'CLIP_FILTERING_TYPE = {s.CLIP_FILTERING_TYPE!r}: "per_class" is the only type')
     assert not (s.CLIP_FILTERING_TYPE and s.MODEL_CONFIDENCE_BASED_FILTERING), \
         "can't use both CLIP_FILTERING_TYPE and MODEL_CONFIDENCE_BASED_FILTERING"
+    inline = bool(s.FILTER_INLINE)
+    if inline and (s.LPIPS_MIN or s.LPIPS_MAX):
+        raise ValueError("FILTER_INLINE records the semantic, model-confidence and per-class CLIP filters; the LPIPS filter is not recorded "
+                         "in-line: unset LPIPS_MIN / LPIPS_MAX or FILTER_INLINE")
+    if inline and not (s.SEMANTIC_FILTERING or s.MODEL_CONFIDENCE_BASED_FILTERING or s.CLIP_FILTERING_TYPE):
+        logging.info("FILTER_INLINE: no filter is on, nothing to record")
+        inline = False
     aug_json_path = utils.get_aug_json_path(output_folder, lpips_min=s.LPIPS_MIN, lpips_max=s.LPIPS_MAX,
                                             clip_filtering=s.CLIP_FILTERING_TYPE or False,
                                             clip_filtering_discount=s.CLIP_FILTERING_DISCOUNT,
@@ -934,16 +1006,33 @@ def _main(s: Settings, ds_utils=None, batch_generator=None, dist=None, pipe=None
     mine = shard_items(items, world)[rank]
     logging.info(f"rank {rank}/{world}: {len(mine)} of {len(items)} work items ({sum(i.skip for i in items)} already exist)")
 
+    recorder, record_batch, scores_header = None, None, None
+    if inline:
+        from . import filters as _filters
+        recorder, scores_header = _inline_recorder(s, ds_utils, filter_models, class_filter, filter_recorder, need_two, need_class, len(mine))
+        filter_models, class_filter = (recorder.semantic, recorder.confidence), recorder.class_filter
+        slot_of = {it.order: k for k, it in enumerate(mine)}       # row = the item's position among this rank's items
+        conf_label = ds_utils.get_image_path_to_class_id_dict() if recorder.confidence is not None else None
+        pc_label = (_filters.class_labels(ds_utils, ds_utils.original_images_paths, recorder.class_filter.class_names)
+                    if recorder.class_filter is not None else None)
+
+        def record_batch(batch, images_u8, bad=None):
+            recorder.record(images_u8, [conf_label[it.source_path] for it in batch] if conf_label is not None else None,
+                            [pc_label[Path(it.source_path).name] for it in batch] if pc_label is not None else None,
+                            [slot_of[it.order] for it in batch], bad)
+
     if batch_generator is None:
         if pipe is None:
             pipe = init_pipeline(s.BASE_MODEL, s.CONTROLNET, s.SDEDIT, weights_dir=s.WEIGHTS_DIR, xl_vae=s.XL_VAE)
             if s.FP16 and s.PRECISION != "fp32":
                 pipe.enable_fp16(True, vae=s.FP16_VAE)          # (raises on the BLIP-Diffusion / SDXL pipelines)
             pipe = pipe.to(s.DEVICE, torch.float32 if s.PRECISION == "fp32" else torch.float16)
-        batch_generator = hip_batch_generator(pipe, s)
+        batch_generator = hip_batch_generator(pipe, s, record=record_batch) if inline else hip_batch_generator(pipe, s)
         noise_dtype = pipe.noise_dtype
     else:
         noise_dtype = torch.float32 if s.PRECISION == "fp32" else torch.float16
+        if inline and hasattr(batch_generator, "enqueue"):
+            raise NotImplementedError("FILTER_INLINE with an injected generator: only the synchronous call form is recorded")
     noises = noise_for_items(items, mine, s.SEED, noise_dtype, draws=2 if s.SDEDIT else 1)   # generator = torch.manual_seed(SEED) (:324)
 
     first_variant = {}
@@ -1033,6 +1122,12 @@ def _main(s: Settings, ds_utils=None, batch_generator=None, dist=None, pipe=None
                 handle = batch_generator.enqueue(*args)
             else:
                 images, controls, *bad = batch_generator(*args)
+                if inline:               # an injected (host) generator: the finished pixels are handed to the recorder as they are
+                    px = torch.from_numpy(np.ascontiguousarray(images))
+                    if torch.device(recorder.dev).type == "cuda":
+                        from . import ops as _ops
+                        px = _ops.h2d(px, recorder.dev)
+                    record_batch(batch, px)
             if prof:
                 print(f"[loop] batch {bi}: wait for sources {t1 - t0:.3f} s, enqueue {_time.time() - t1:.3f} s", flush=True)
         except KeyboardInterrupt:
@@ -1076,6 +1171,15 @@ def _main(s: Settings, ds_utils=None, batch_generator=None, dist=None, pipe=None
         dist.gather(st, gathered, dst=0)
         if rank == 0:
             status = torch.stack([g.cpu() for g in gathered]).sum(0).to(torch.int32)   # shards are disjoint
+    scores = planned = None
+    if inline:
+        # ---- the second collective, in this mode only: the items' score records [n_items, 8] fp32 -> rank 0 ----
+        records = gather_records(items, mine, recorder.table_host() if mine else None, world, rank, dist, s.DEVICE)
+        if rank == 0:
+            scores = {Path(it.output_path).name: records[it.order] for it in items
+                      if int(status[it.order]) == 1 and not np.isnan(records[it.order, 0])}
+            # files that already existed are scored from their PNGs, in the batches the loop would have formed for them
+            planned = [[it.output_path for it in b] for b in make_batches([it for it in items if it.skip], s.BATCH_SIZE)]
     json_path = None
     if rank == 0:
         logging.info(f"Done Generating: {(status == 1).sum().item()} generated, {(status == -1).sum().item()} failed, "
@@ -1089,8 +1193,9 @@ def _main(s: Settings, ds_utils=None, batch_generator=None, dist=None, pipe=None
             clip_filtering_discount=s.CLIP_FILTERING_DISCOUNT, class_filter=class_filter, semantic_filtering=s.SEMANTIC_FILTERING,
             model_confidence_based_filtering=s.MODEL_CONFIDENCE_BASED_FILTERING, init_log=False,
             original_images_paths=ds_utils.original_images_paths, min_files=min(10, max(1, n_files)),
-            filter_models=filter_models, weights_dir=s.WEIGHTS_DIR, device=fdev, lpips_model=lpips_model)
+            filter_models=filter_models, weights_dir=s.WEIGHTS_DIR, device=fdev, lpips_model=lpips_model,
+            **(dict(scores=scores, recorder=recorder, scores_header=scores_header, planned_batches=planned) if inline else {}))
     if dist is not None:
         dist.barrier()
     return dict(items=items, status=status, json_path=json_path, output_folder=output_folder, mine=mine, n_batches=len(batches),
-                png_submitted=png.submitted, png_max_queue=png.max_depth, batch_log=batch_log)
+                png_submitted=png.submitted, png_max_queue=png.max_depth, batch_log=batch_log, filter_scores=scores)

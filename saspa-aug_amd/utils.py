@@ -182,7 +182,8 @@ def create_json_of_image_name_to_augmented_images_paths(dataset, augmented_image
                                                         conf_top_k: int = 10, filter_confidence_higher_than: int = None,
                                                         init_log=True, alia_conf_filtering=False, original_images_paths=None,
                                                         min_files=10, filter_models=None, weights_dir=None, device=None,
-                                                        lpips_model=None, class_filter=None):
+                                                        lpips_model=None, class_filter=None, scores=None, recorder=None,
+                                                        scores_header=None, planned_batches=None, backfill=True):
     """`dataset` may be a dataset name (resolved through dataset_utils.DS_UTILS_DICT) or any
     object with `.original_images_paths`.  `filter_models` = (semantic, confidence) models built by the caller, `lpips_model` an
     `filters.LpipsAlex`; each is built here from `weights_dir` when its filter is on and it is not given.  `lpips_min` / `lpips_max`
@@ -192,7 +193,13 @@ def create_json_of_image_name_to_augmented_images_paths(dataset, augmented_image
     augmented image when CLIP-RN50's softmax over the class prompts of the whole dataset gives the source image's class at least
     `1 / n_classes / clip_filtering_discount`; `class_filter` = a built `filters.ClassFilter` (its own discount then holds).
     `filter_confidence_higher_than` drops, among the images that pass top-k, those whose softmax probability of the source label
-    exceeds it; a `filter_models` confidence model handed in must have been built with the same `too_high`."""
+    exceeds it; a `filter_models` confidence model handed in must have been built with the same `too_high`.
+    `scores` (default None: the stage as it always was) = {png file name: 8 fp32} score records of this run (`filters.FilterRecorder`; may
+    be empty): the mapping is then filtered by `filters.decide` from the records of `filter_scores.json` merged with `scores`, and no PNG
+    is decoded for an image that has a record.  Images without one are scored through `recorder` (built from the models when not given)
+    from their PNGs, `planned_batches` ([[png path]]) naming the batches to keep together, and the sidecar is completed; with
+    `backfill=False` (no GPU: run_aug/filter_json.py) a missing record is an error.  `scores_header`: what the scores depend on
+    (`filters.recorder_header`); None = take the sidecar's."""
     assert not (clip_filtering and model_confidence_based_filtering), "can't use both clip_filtering and model_confidence_based_filtering"
     if alia_conf_filtering or (clip_filtering and clip_filtering != "per_class"):
         raise NotImplementedError('clip_filtering knows the type "per_class" only; the ALIA confidence filter is a baseline branch '
@@ -218,7 +225,12 @@ def create_json_of_image_name_to_augmented_images_paths(dataset, augmented_image
         raise FileNotFoundError(f"augmented_image_folder_path = {augmented_image_folder_path} doesn't exist or has less "
                                 f"than {min_files} images")
     mapping = match_augmented_images(original_images_paths, os.listdir(augmented_image_folder_path), augmented_image_folder_path)
-    if semantic_filtering or model_confidence_based_filtering or lpips_filtering or clip_filtering:
+    if scores is not None and (semantic_filtering or model_confidence_based_filtering or clip_filtering):
+        mapping = _filter_by_scores(mapping, dataset, augmented_image_folder_path, original_images_paths, scores, recorder, scores_header,
+                                    planned_batches, backfill, lpips_filtering, semantic_filtering, model_confidence_based_filtering,
+                                    clip_filtering, clip_filtering_discount, conf_top_k, filter_confidence_higher_than, filter_models,
+                                    class_filter, weights_dir, device)
+    elif semantic_filtering or model_confidence_based_filtering or lpips_filtering or clip_filtering:
         # the filter stage: CLIP-RN50 semantic and per-class filters, baseline-classifier top-k / too-high filter and
         # LPIPS min / max filter on the gfx950 kernels
         from . import filters
@@ -282,6 +294,90 @@ def create_json_of_image_name_to_augmented_images_paths(dataset, augmented_image
         counts[len(v)] = counts.get(len(v), 0) + 1
     logging.info(f"dict_num_augmentations_per_image = {dict(sorted(counts.items()))}")
     return json_path
+
+
+def _filter_by_scores(mapping, dataset, folder, original_images_paths, scores, recorder, header, planned_batches, backfill,
+                      lpips_filtering, semantic_filtering, model_confidence_based_filtering, clip_filtering, clip_filtering_discount,
+                      conf_top_k, filter_confidence_higher_than, filter_models, class_filter, weights_dir, device):
+    """The filter stage from score records (`create_json_of_image_name_to_augmented_images_paths(scores=...)`): merge the sidecar,
+    score what has no record yet, decide on the host, log the counters like the post-hoc stage does."""
+    from . import filters
+    if lpips_filtering:
+        raise ValueError("the LPIPS filter is not recorded in-line: drop the lpips bounds or the score records")
+    if isinstance(dataset, str):
+        from . import dataset_utils
+        dataset = dataset_utils.DS_UTILS_DICT[dataset](print_func=logging.info)
+    sem, conf = filter_models if filter_models is not None else (None, None)
+    if recorder is not None:
+        sem, conf, class_filter = recorder.semantic, recorder.confidence, recorder.class_filter
+    if header is None:
+        header = filters.load_scores(filters.scores_path(folder))[0]
+        if header is None:
+            raise FileNotFoundError(f"{filters.scores_path(folder)} not found: no score records for {folder}")
+    records, _ = filters.merge_scores(folder, header, scores)
+    work = [ap for aps in mapping.values() for ap in aps]
+    missing = [ap for ap in work if Path(ap).name not in records]
+    if missing:
+        if not backfill:
+            raise FileNotFoundError(f"{len(missing)} of {len(work)} augmented images have no record in {filters.scores_path(folder)} "
+                                    f"(first: {Path(missing[0]).name}); score them on a GPU first (run_aug with FILTER_INLINE)")
+        if recorder is None:
+            need_two = bool(semantic_filtering or model_confidence_based_filtering) and filter_models is None
+            need_class = bool(clip_filtering) and class_filter is None
+            if device is None:
+                device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
+            if device is None:
+                raise RuntimeError(f"{len(missing)} augmented images have no score record and scoring them needs the MI355X (no CPU path)")
+            if need_two or need_class:
+                built = filters.build_filters(dataset, device, bool(semantic_filtering) and need_two,
+                                              bool(model_confidence_based_filtering) and need_two, weights_dir, conf_top_k,
+                                              per_class=need_class, discount=clip_filtering_discount, too_high=filter_confidence_higher_than)
+                if need_two:
+                    sem, conf = built[:2]
+                if need_class:
+                    class_filter = built[2]
+            recorder = filters.FilterRecorder(sem if semantic_filtering else None, conf if model_confidence_based_filtering else None,
+                                              class_filter if clip_filtering else None, 1, device)
+        source_of = {ap: name for name, aps in mapping.items() for ap in aps}
+        conf_of = pc_of = None
+        if recorder.confidence is not None:
+            table = dataset.get_image_path_to_class_id_dict()
+            by_name = {Path(ip).name: table[ip] for ip in original_images_paths}
+            conf_of = lambda ap: by_name[source_of[ap]]     # noqa: E731
+        if recorder.class_filter is not None:
+            cls_labels = filters.class_labels(dataset, original_images_paths, recorder.class_filter.class_names)
+            pc_of = lambda ap: cls_labels[source_of[ap]]    # noqa: E731
+        logging.info(f"{len(missing)} augmented images have no score record: scoring them from their PNGs")
+        records, _ = filters.merge_scores(folder, header, filters.backfill_scores(recorder, missing, conf_of, pc_of, planned_batches))
+    top_k = too_high = pc_threshold = None
+    if model_confidence_based_filtering:
+        top_k = conf.top_k if conf is not None else conf_top_k
+        too_high = conf.too_high if conf is not None else filter_confidence_higher_than
+        if filter_confidence_higher_than and too_high != filter_confidence_higher_than:
+            raise ValueError(f"filter_confidence_higher_than = {filter_confidence_higher_than} but the confidence model handed in was "
+                             f"built with too_high = {too_high}")
+    if clip_filtering:
+        if class_filter is not None:
+            n_classes, pc_threshold = len(class_filter.class_names), class_filter.threshold
+        else:
+            n_classes = len(header["per_class"]["classes"])
+            pc_threshold = filters.class_threshold(n_classes, clip_filtering_discount)
+        logging.info(f"using CLIP filtering, of type {clip_filtering}")
+        logging.info(f"total number of classes = {n_classes}")
+        logging.info(f"using CLIP filtering with threshold = {pc_threshold}")
+    if too_high:
+        logging.info(f"using model_confidence_based_filtering with filter_confidence_higher_than = {too_high}")
+    rec = np.stack([records[Path(ap).name] for ap in work]) if work else np.zeros((0, 8), np.float32)
+    keep, counters = filters.decide(rec, semantic=bool(semantic_filtering), top_k=top_k, too_high=too_high, pc_threshold=pc_threshold)
+    kept = {ap for ap, k in zip(work, keep) if k}
+    if clip_filtering:
+        logging.info(f"For filter = clip_filtering, filtered {counters['clip_filtering']} images")
+    if semantic_filtering:
+        logging.info(f"For filter = semantic_filtering, filtered {counters['semantic']} images")
+    if model_confidence_based_filtering:
+        logging.info(f"For filter = not_in_top_{conf_top_k}, filtered {counters['not_in_top_k']} images")
+        logging.info(f"For filter = too_high_confidence, filtered {counters.get('too_high_confidence', 0)} images")
+    return {name: [ap for ap in aps if ap in kept] for name, aps in mapping.items()}
 
 
 def calc_lpips_given_aug_json(dataset, aug_json, net="alex", compute_on=3000, resize_to=None, lpips_model=None, weights_dir=None,

@@ -482,6 +482,25 @@ int saspa_cfg_unipc_step(int dtype, const void* eps, void* x, void* state, int n
 int saspa_unipc_step(int dtype, const void* eps, void* x, void* state, int nimg, long long hw, int C, int ldc,
                      const float* row, const float* table, const int* index, void* stream);
 
+/* ---- v-prediction forms of the DDIM / UniPC steps (scheduler prediction_type "v_prediction": the 768-pixel
+ * stabilityai/stable-diffusion-2-1 checkpoint).  `v` is the network output in the layout `eps` has above; all other
+ * arguments, the host-side checks and their error codes are those of the epsilon entry point of the same name.
+ *   v = vu + g (vc - vu)                                  (guidance on v, the order of the epsilon kernels' guidance line)
+ *   DDIM:  x0 = sqrt(a_t) x - sqrt(1-a_t) v;  e = sqrt(a_t) v + sqrt(1-a_t) x;  x' = sqrt(a_p) x0 + sqrt(1-a_p) e
+ *   UniPC: x0 = r10 * x - r1 * v  (r10 = alpha_t, r1 = sigma_t; r0 is not read), then the update of saspa_cfg_unipc_step
+ * fp32 arithmetic in this order, one rounding to the storage type; an element's result does not depend on the launch.
+ * saspa_ddim_step_v_dev serves both the CFG (cfg = 1) and the plain (cfg = 0) form, as saspa_ddim_step_dev.  ABI 20. */
+int saspa_cfg_ddim_step_v(int dtype, const void* v, void* x, int nimg, long long hw, int C, int ldc, float guidance,
+                          float sqrt_a_t, float sqrt_1m_a_t, float sqrt_a_prev, float sqrt_1m_a_prev, void* stream);
+int saspa_ddim_step_v(int dtype, const void* v, void* x, int nimg, long long hw, int C, int ldc, float sqrt_a_t,
+                      float sqrt_1m_a_t, float sqrt_a_prev, float sqrt_1m_a_prev, void* stream);
+int saspa_ddim_step_v_dev(int dtype, const void* v, void* x, int nimg, long long hw, int C, int ldc, int cfg, float guidance,
+                          const float* coefs, const int* index, void* stream);
+int saspa_cfg_unipc_step_v(int dtype, const void* v, void* x, void* state, int nimg, long long hw, int C, int ldc, float guidance,
+                           const float* row, const float* table, const int* index, void* stream);
+int saspa_unipc_step_v(int dtype, const void* v, void* x, void* state, int nimg, long long hw, int C, int ldc,
+                       const float* row, const float* table, const int* index, void* stream);
+
 /* SDEdit / img2img start latents (StableDiffusionControlNetImg2ImgPipeline.prepare_latents): per 8-channel
  * latent pixel, moments = AutoencoderKL.encode's quant_conv output (mean | logvar), e1 / e2 = the two generator draws:
  * out = sa * ((mean + exp(0.5 * clamp(logvar, -30, 20)) * e1) * scaling) + s1m * e2, pad channels zero. */

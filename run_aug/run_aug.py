@@ -13,8 +13,10 @@ started again ONCE as fresh processes with SASPA_FORK=0 (single-branch step grap
 exist; the exit code is non-zero if that fails too.  SASPA_FORK=0 by hand rules the two-branch capture out from the start.
 
 Environment overlays (optional): SASPA_DATASET, SASPA_WEIGHTS_DIR, SASPA_PROMPTS_FILE,
-SASPA_NUM_INFERENCE_STEPS, SASPA_NUM_PER_IMAGE, SASPA_PRECISION, SASPA_BASE_MODEL (sd_v1.5 | blip_diffusion | sd_xl-turbo | ip2p),
-SASPA_CONTROLNET (canny | hed; empty or "None": no ControlNet -- what ip2p, the ALIA baseline's InstructPix2Pix, runs with),
+SASPA_NUM_INFERENCE_STEPS, SASPA_NUM_PER_IMAGE, SASPA_PRECISION, SASPA_BASE_MODEL (sd_v1.5 | sd_v2.1 | blip_diffusion | sd_xl-turbo | ip2p),
+SASPA_CONTROLNET (canny | hed; empty or "None": no ControlNet -- what ip2p, the ALIA baseline's InstructPix2Pix, and sd_v2.1 run with; for
+sd_v1.5 / sd_v2.1 that is the ControlNet-free text-to-image pipeline, or with SASPA_SDEDIT=1 the ControlNet-free img2img one),
+SASPA_SDEDIT (0 | 1: SDEdit img2img from the source image; default 0, as the reference's constant),
 SASPA_LPIPS_MIN / SASPA_LPIPS_MAX (the LPIPS filter's bounds; both or neither), SASPA_CLIP_FILTERING=per_class with
 SASPA_CLIP_FILTERING_DISCOUNT (the per-class CLIP filter; it replaces the model-confidence filter, which it cannot be combined with),
 SASPA_PNG_DEVICE=1 (generated and source PNGs are compressed on the device; off by default), SASPA_FP16=1 with SASPA_FP16_VAE=bf16|x3
@@ -44,10 +46,10 @@ if __name__ == "__main__":
     version = "v1"
     DATASET = os.environ.get("SASPA_DATASET", "planes")
     BASE_MODEL = os.environ.get("SASPA_BASE_MODEL") or ("sd_v1.5" if DATASET in ("planes", "synthetic") else "blip_diffusion")
-    CONTROLNET = os.environ.get("SASPA_CONTROLNET", "None" if BASE_MODEL == "ip2p" else "canny")
+    CONTROLNET = os.environ.get("SASPA_CONTROLNET", "None" if BASE_MODEL in ("ip2p", "sd_v2.1") else "canny")
     if CONTROLNET in ("", "None"):
         CONTROLNET = None
-    SDEDIT = 0
+    SDEDIT = int(os.environ.get("SASPA_SDEDIT") or 0)
     NUM_PER_IMAGE = int(os.environ.get("SASPA_NUM_PER_IMAGE", 2))
     SEED = 1
     PROMPT_TYPE = "gpt-meta_class"

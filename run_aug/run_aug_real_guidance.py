@@ -8,7 +8,7 @@ model-confidence filters.  Same launch forms as run_aug/run_aug.py:
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 run_aug/run_aug_real_guidance.py
 
 and the same environment overlays: SASPA_DATASET, SASPA_WEIGHTS_DIR, SASPA_PROMPTS_FILE, SASPA_NUM_INFERENCE_STEPS,
-SASPA_NUM_PER_IMAGE, SASPA_PRECISION, SASPA_BASE_MODEL, SASPA_LPIPS_MIN / SASPA_LPIPS_MAX, SASPA_CLIP_FILTERING (default
+SASPA_NUM_PER_IMAGE, SASPA_PRECISION, SASPA_BASE_MODEL (sd_v1.5 | sd_v2.1: the two ControlNet-free img2img pipelines), SASPA_LPIPS_MIN / SASPA_LPIPS_MAX, SASPA_CLIP_FILTERING (default
 "per_class"; "none" switches the filter off), SASPA_CLIP_FILTERING_DISCOUNT, SASPA_PNG_DEVICE and SASPA_FP16 / SASPA_FP16_VAE.  The output folder carries the step count and
 guidance scale after the seed (`..._seed_1_num_inf_steps_50_gs_7.5/images`), as the reference's script names it."""
 import os

@@ -187,6 +187,11 @@ SYMBOLS = {
     "saspa_vae_sample_noise": (_I, [_I, _P, _P, _P, _P, _LL, _F, _F, _F, _P]),
     "saspa_cfg_unipc_step": (_I, [_I, _P, _P, _P, _I, _LL, _I, _I, _F, C.POINTER(C.c_float), _P, _P, _P]),
     "saspa_unipc_step": (_I, [_I, _P, _P, _P, _I, _LL, _I, _I, C.POINTER(C.c_float), _P, _P, _P]),
+    "saspa_cfg_ddim_step_v": (_I, [_I, _P, _P, _I, _LL, _I, _I, _F, _F, _F, _F, _F, _P]),
+    "saspa_ddim_step_v": (_I, [_I, _P, _P, _I, _LL, _I, _I, _F, _F, _F, _F, _P]),
+    "saspa_ddim_step_v_dev": (_I, [_I, _P, _P, _I, _LL, _I, _I, _I, _F, _P, _P, _P]),
+    "saspa_cfg_unipc_step_v": (_I, [_I, _P, _P, _P, _I, _LL, _I, _I, _F, C.POINTER(C.c_float), _P, _P, _P]),
+    "saspa_unipc_step_v": (_I, [_I, _P, _P, _P, _I, _LL, _I, _I, C.POINTER(C.c_float), _P, _P, _P]),
     "saspa_xattn_block": (_I, [C.POINTER(XattnBlockParams), _P]),
     "saspa_xattn_block_bcast": (_I, [C.POINTER(XattnBlockParams), _LL, _P]),
     "saspa_groupnorm_onepass_eligible": (_I, [C.POINTER(GroupNormParams)]),
@@ -223,6 +228,7 @@ F16_SYMBOL_NAMES = (
     "saspa_splitk_groupnorm_eligible", "saspa_splitk_groupnorm", "saspa_layernorm", "saspa_geglu", "saspa_activation",
     "saspa_embed_tokens", "saspa_embed_tokens_ctx", "saspa_cfg_plms_step", "saspa_cfg_plms_step_dev", "saspa_cfg_ddim_step",
     "saspa_ddim_step", "saspa_ddim_step_dev", "saspa_cfg3_ddim_step", "saspa_cfg3_ddim_step_dev", "saspa_cfg_unipc_step", "saspa_unipc_step",
+    "saspa_cfg_ddim_step_v", "saspa_ddim_step_v", "saspa_ddim_step_v_dev", "saspa_cfg_unipc_step_v", "saspa_unipc_step_v",
     "saspa_vae_sample_noise", "saspa_scale", "saspa_u8_to_act", "saspa_act_to_u8", "saspa_abi_version", "saspa_half_type",
     "saspa_build_arch",
 )

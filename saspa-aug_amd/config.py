@@ -27,6 +27,20 @@ SD15 = dict(unet=SD15_UNET, controlnet=SD15_CONTROLNET, vae=SD15_VAE, text=CLIP_
 # 8 channels (4 noisy latents | 4 image latents).  Everything else recalled as SD-1.5's (no network here): parity unpinned.
 IP2P = dict({k: v for k, v in SD15.items() if k != "controlnet"}, unet=dict(SD15_UNET, in_channels=8))
 
+# stabilityai/stable-diffusion-2-1-base (run_aug/run_aug.py BASE_MODEL_DICT "sd_v2.1") : unet/config.json.  SD-1.5's channel plan and
+# attention levels, one transformer block per level; attention_head_dim (5, 10, 20, 20) is again the head COUNT per level, so the
+# head width is 64 everywhere; cross_attention_dim 1024, use_linear_projection.  The repository ships no ControlNet and no safety
+# checker.  RECALLED from the public repo (no checkpoint here): parity unpinned.
+SD21_UNET = dict(
+    in_channels=4, out_channels=4, block_out=(320, 640, 1280, 1280),
+    attn=(True, True, True, False), layers=2, heads=(5, 10, 20, 20), ctx_dim=1024, groups=32, temb_dim=1280, linear_proj=True,
+)
+# stabilityai/stable-diffusion-2-1-base : text_encoder/config.json -- the OpenCLIP ViT-H/14 text tower as the diffusers repository
+# stores it: 23 layers (the conversion dropped the 24th, so the LAST hidden state is what OpenCLIP calls the penultimate one, and the
+# final LayerNorm is applied to it), width 1024, 16 heads, MLP 4096, erf-GELU, pad token id 0.  RECALLED: parity unpinned.
+OPENCLIP_H = dict(vocab=49408, width=1024, layers=23, heads=16, mlp=4096, max_pos=77, act="gelu", pad_id=0)
+SD21 = dict(unet=SD21_UNET, vae=SD15_VAE, text=OPENCLIP_H)
+
 # stabilityai/sdxl-turbo (= SDXL-base architecture) : unet/config.json.  Three levels, no attention at level 0,
 # transformer_layers_per_block (1, 2, 10) -> "depth" (level 0 unused), attention_head_dim (5, 10, 20) = heads per
 # level (head dim 64 everywhere), cross_attention_dim 2048 (CLIP-L 768 | OpenCLIP-bigG 1280), use_linear_projection,
@@ -160,6 +174,19 @@ def tiny(width=32, ctx=64, groups=8, heads=4, vae_width=16):
                    proj_hidden=2 * ctx, out_dim=ctx)
     safety = dict(image_size=56, patch=14, width=64, layers=2, heads=4, mlp=128, proj_dim=48, n_concepts=17, n_special=3)
     return dict(unet=unet, controlnet=cn, vae=vae, text=text, qformer=qformer, ctx_begin_pos=2, safety=safety)
+
+
+def tiny_sd21(width=32, ctx=96, groups=8, vae_width=16):
+    """Reduced-width `SD21` with the same topology: four levels with per-level head counts (head width 16 everywhere), one transformer
+    block per level, linear projections, a context width different from the UNet's, a GELU text tower with pad id 0; no ControlNet,
+    no safety checker."""
+    unet = dict(in_channels=4, out_channels=4, block_out=(width, 2 * width, 4 * width, 4 * width), attn=(True, True, True, False),
+                layers=2, heads=(width // 16, width // 8, width // 4, width // 4), ctx_dim=ctx, groups=groups, temb_dim=4 * width,
+                linear_proj=True)
+    vae = dict(latent_channels=4, out_channels=3, block_out=(vae_width, 2 * vae_width, 4 * vae_width, 4 * vae_width),
+               layers=2, groups=groups, scaling_factor=0.18215)
+    text = dict(vocab=512, width=ctx, layers=3, heads=ctx // 16, mlp=4 * ctx, max_pos=77, act="gelu", pad_id=0)
+    return dict(unet=unet, vae=vae, text=text)
 
 
 def tiny_ip2p(**kw):

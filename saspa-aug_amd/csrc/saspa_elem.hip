@@ -271,6 +271,76 @@ __global__ __launch_bounds__(256) void cfg_ddim_kernel(const T* eps, T* x, int n
   }
 }
 
+// v-prediction forms (prediction_type "v_prediction": the 768-pixel stable-diffusion-2-1 checkpoint).  The network output is
+// v = sqrt(a_t) eps - sqrt(1 - a_t) x0; everything else (layouts, CFG flag, coefs / index) is as in cfg_ddim_kernel.
+//   v = vu + g (vc - vu);  x0 = sa_t x - s1m_t v;  e = sa_t v + s1m_t x;  x' = sa_p x0 + s1m_p e
+// fp32 throughout, one rounding at the store; no division, so the result is finite for every a_t.
+template <typename T, bool CFG>
+__global__ __launch_bounds__(256) void cfg_ddim_v_kernel(const T* vout, T* x, int nimg, long long hw, int C, float g, float sa_t,
+                                                         float s1m_t, float sa_p, float s1m_p, const float* coefs = nullptr,
+                                                         const int* index = nullptr) {
+  if (coefs) {
+    const float* c4 = coefs + 4ll * (*index);
+    sa_t = c4[0]; s1m_t = c4[1]; sa_p = c4[2]; s1m_p = c4[3];
+  }
+  const long long total = (long long)nimg * hw;
+  const long long half = total * 8;  // elements in one CFG half
+  for (long long it = (long long)blockIdx.x * 256 + threadIdx.x; it < total; it += (long long)gridDim.x * 256) {
+    float vu[8], vc[8], xv[8], o[8];
+    load8(vout + it * 8, vu);
+    if (CFG) load8(vout + half + it * 8, vc);
+    load8(x + it * 8, xv);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float v = CFG ? vu[j] + g * (vc[j] - vu[j]) : vu[j];
+      const float x0 = sa_t * xv[j] - s1m_t * v;
+      const float e = sa_t * v + s1m_t * xv[j];
+      o[j] = (j < C) ? (sa_p * x0 + s1m_p * e) : 0.f;
+    }
+    store8(x + it * 8, o);
+    if (CFG) store8(x + half + it * 8, o);
+  }
+}
+
+// cfg_unipc_kernel with a v-prediction network: x0 = r[10] * x - r[1] * v (r[10] = alpha_t, r[1] = sigma_t; r[0] is not read),
+// then the unchanged corrector / predictor update on x0.
+template <typename T, bool CFG>
+__global__ __launch_bounds__(256) void cfg_unipc_v_kernel(const T* vout, T* x, T* state, int nimg, long long hw, int C, float g,
+                                                          UniPcRow row, const float* table, const int* index) {
+  const long long total = (long long)nimg * hw;
+  const long long half = total * 8;
+  float r[12];
+#pragma unroll
+  for (int j = 0; j < 12; ++j) r[j] = table ? table[12ll * (*index) + j] : row.v[j];
+  T* last = state;
+  T* m0p = state + half;
+  T* m1p = state + 2 * half;
+  for (long long it = (long long)blockIdx.x * 256 + threadIdx.x; it < total; it += (long long)gridDim.x * 256) {
+    float vu[8], vc[8], xv[8], lv[8], m0[8], m1[8], x0[8], o[8];
+    load8(vout + it * 8, vu);
+    if (CFG) load8(vout + half + it * 8, vc);
+    load8(x + it * 8, xv);
+    load8(m0p + it * 8, m0);
+    load8(m1p + it * 8, m1);
+    if (r[2] != 0.f) load8(last + it * 8, lv);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float v = CFG ? vu[j] + g * (vc[j] - vu[j]) : vu[j];
+      x0[j] = r[10] * xv[j] - r[1] * v;
+      float xc = xv[j];
+      if (r[2] != 0.f) xc = r[3] * lv[j] + r[4] * m0[j] + r[5] * m1[j] + r[6] * x0[j];
+      lv[j] = (j < C) ? xc : 0.f;
+      o[j] = (j < C) ? (r[7] * xc + r[8] * x0[j] + r[9] * m0[j]) : 0.f;        // new m0 = x0, new m1 = old m0
+      if (j >= C) x0[j] = 0.f;
+    }
+    store8(last + it * 8, lv);
+    store8(m1p + it * 8, m0);
+    store8(m0p + it * 8, x0);
+    store8(x + it * 8, o);
+    if (CFG) store8(x + half + it * 8, o);
+  }
+}
+
 // Three-branch guidance + DDIM (eta = 0): the InstructPix2Pix update.  eps / x: [3 * nimg][hw][8] in the groups (uncond | image |
 // text); the UNet input carries the noisy latents in channels < C and the image latents (zeros in group 0) in channels C..7.
 //   e = e0 + g (e2 - e1) + ig (e1 - e0), then the DDIM step of cfg_ddim_kernel on e and the x of group 0.
@@ -548,6 +618,104 @@ extern "C" int saspa_ddim_step_dev(int dtype, const void* eps, void* x, int nimg
   } else {
     return SASPA_EINVAL;
   }
+  SASPA_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---- v-prediction sampler steps: the entry points above with cfg_ddim_v_kernel / cfg_unipc_v_kernel; the host-side checks and
+// their order are those of the epsilon entry points ----
+extern "C" int saspa_cfg_ddim_step_v(int dtype, const void* v, void* x, int nimg, long long hw, int C, int ldc, float guidance,
+                                     float sqrt_a_t, float sqrt_1m_a_t, float sqrt_a_prev, float sqrt_1m_a_prev, void* stream) {
+  if (!v || !x || nimg <= 0 || hw <= 0 || C <= 0) return SASPA_EINVAL;
+  if (ldc != 8 || C > 8) return SASPA_ERANGE;
+  if (!aligned16(v) || !aligned16(x)) return SASPA_EALIGN;
+  if (!(sqrt_a_t > 0.f)) return SASPA_EINVAL;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const unsigned grid = grid_for((long long)nimg * hw);
+  if (dtype == SASPA_HALF)
+    hipLaunchKernelGGL((cfg_ddim_v_kernel<h16_t, true>), dim3(grid), dim3(256), 0, s, (const h16_t*)v, (h16_t*)x, nimg, hw, C, guidance, sqrt_a_t, sqrt_1m_a_t, sqrt_a_prev, sqrt_1m_a_prev);
+  else if (dtype == SASPA_F32 && kServesF32)
+    hipLaunchKernelGGL((cfg_ddim_v_kernel<float, true>), dim3(grid), dim3(256), 0, s, (const float*)v, (float*)x, nimg, hw, C, guidance, sqrt_a_t, sqrt_1m_a_t, sqrt_a_prev, sqrt_1m_a_prev);
+  else
+    return SASPA_EINVAL;
+  SASPA_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int saspa_ddim_step_v(int dtype, const void* v, void* x, int nimg, long long hw, int C, int ldc, float sqrt_a_t,
+                                 float sqrt_1m_a_t, float sqrt_a_prev, float sqrt_1m_a_prev, void* stream) {
+  if (!v || !x || nimg <= 0 || hw <= 0 || C <= 0) return SASPA_EINVAL;
+  if (ldc != 8 || C > 8) return SASPA_ERANGE;
+  if (!aligned16(v) || !aligned16(x)) return SASPA_EALIGN;
+  if (!(sqrt_a_t > 0.f)) return SASPA_EINVAL;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const unsigned grid = grid_for((long long)nimg * hw);
+  if (dtype == SASPA_HALF)
+    hipLaunchKernelGGL((cfg_ddim_v_kernel<h16_t, false>), dim3(grid), dim3(256), 0, s, (const h16_t*)v, (h16_t*)x, nimg, hw, C, 0.f, sqrt_a_t, sqrt_1m_a_t, sqrt_a_prev, sqrt_1m_a_prev);
+  else if (dtype == SASPA_F32 && kServesF32)
+    hipLaunchKernelGGL((cfg_ddim_v_kernel<float, false>), dim3(grid), dim3(256), 0, s, (const float*)v, (float*)x, nimg, hw, C, 0.f, sqrt_a_t, sqrt_1m_a_t, sqrt_a_prev, sqrt_1m_a_prev);
+  else
+    return SASPA_EINVAL;
+  SASPA_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int saspa_ddim_step_v_dev(int dtype, const void* v, void* x, int nimg, long long hw, int C, int ldc, int cfg,
+                                     float guidance, const float* coefs, const int* index, void* stream) {
+  if (!v || !x || !coefs || !index || nimg <= 0 || hw <= 0 || C <= 0) return SASPA_EINVAL;
+  if (ldc != 8 || C > 8) return SASPA_ERANGE;
+  if (!aligned16(v) || !aligned16(x)) return SASPA_EALIGN;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const unsigned grid = grid_for((long long)nimg * hw);
+  if (dtype == SASPA_HALF) {
+    if (cfg) hipLaunchKernelGGL((cfg_ddim_v_kernel<h16_t, true>), dim3(grid), dim3(256), 0, s, (const h16_t*)v, (h16_t*)x, nimg, hw, C, guidance, 1.f, 0.f, 1.f, 0.f, coefs, index);
+    else hipLaunchKernelGGL((cfg_ddim_v_kernel<h16_t, false>), dim3(grid), dim3(256), 0, s, (const h16_t*)v, (h16_t*)x, nimg, hw, C, 0.f, 1.f, 0.f, 1.f, 0.f, coefs, index);
+  } else if (dtype == SASPA_F32 && kServesF32) {
+    if (cfg) hipLaunchKernelGGL((cfg_ddim_v_kernel<float, true>), dim3(grid), dim3(256), 0, s, (const float*)v, (float*)x, nimg, hw, C, guidance, 1.f, 0.f, 1.f, 0.f, coefs, index);
+    else hipLaunchKernelGGL((cfg_ddim_v_kernel<float, false>), dim3(grid), dim3(256), 0, s, (const float*)v, (float*)x, nimg, hw, C, 0.f, 1.f, 0.f, 1.f, 0.f, coefs, index);
+  } else {
+    return SASPA_EINVAL;
+  }
+  SASPA_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int saspa_unipc_step_v(int dtype, const void* v, void* x, void* state, int nimg, long long hw, int C, int ldc,
+                                  const float* row, const float* table, const int* index, void* stream) {
+  if (!v || !x || !state || nimg <= 0 || hw <= 0 || C <= 0 || (!row && !(table && index))) return SASPA_EINVAL;
+  if (ldc != 8 || C > 8) return SASPA_ERANGE;
+  if (!aligned16(v) || !aligned16(x) || !aligned16(state)) return SASPA_EALIGN;
+  UniPcRow rr{};
+  if (row && !table)
+    for (int j = 0; j < 12; ++j) rr.v[j] = row[j];
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const unsigned grid = grid_for((long long)nimg * hw);
+  if (dtype == SASPA_HALF)
+    hipLaunchKernelGGL((cfg_unipc_v_kernel<h16_t, false>), dim3(grid), dim3(256), 0, s, (const h16_t*)v, (h16_t*)x, (h16_t*)state, nimg, hw, C, 0.f, rr, table, index);
+  else if (dtype == SASPA_F32 && kServesF32)
+    hipLaunchKernelGGL((cfg_unipc_v_kernel<float, false>), dim3(grid), dim3(256), 0, s, (const float*)v, (float*)x, (float*)state, nimg, hw, C, 0.f, rr, table, index);
+  else
+    return SASPA_EINVAL;
+  SASPA_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int saspa_cfg_unipc_step_v(int dtype, const void* v, void* x, void* state, int nimg, long long hw, int C, int ldc,
+                                      float guidance, const float* row, const float* table, const int* index, void* stream) {
+  if (!v || !x || !state || nimg <= 0 || hw <= 0 || C <= 0 || (!row && !(table && index))) return SASPA_EINVAL;
+  if (ldc != 8 || C > 8) return SASPA_ERANGE;
+  if (!aligned16(v) || !aligned16(x) || !aligned16(state)) return SASPA_EALIGN;
+  UniPcRow rr{};
+  if (row && !table)
+    for (int j = 0; j < 12; ++j) rr.v[j] = row[j];
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const unsigned grid = grid_for((long long)nimg * hw);
+  if (dtype == SASPA_HALF)
+    hipLaunchKernelGGL((cfg_unipc_v_kernel<h16_t, true>), dim3(grid), dim3(256), 0, s, (const h16_t*)v, (h16_t*)x, (h16_t*)state, nimg, hw, C, guidance, rr, table, index);
+  else if (dtype == SASPA_F32 && kServesF32)
+    hipLaunchKernelGGL((cfg_unipc_v_kernel<float, true>), dim3(grid), dim3(256), 0, s, (const float*)v, (float*)x, (float*)state, nimg, hw, C, guidance, rr, table, index);
+  else
+    return SASPA_EINVAL;
   SASPA_CHECK_LAUNCH();
   return 0;
 }

@@ -1677,6 +1677,68 @@ def unipc_step(eps, x, state, nimg, hw, c, row=None, table=None, index=None):
     return x
 
 
+def _vstep_shapes(what, v, x, nimg, hw, groups, state=None):
+    """Operands of a v-prediction step: v, x contiguous [groups * nimg, hw, 8] of one element type (state: [3, nimg, hw, 8])."""
+    _same_dtype(what, x, v=v, state=state)
+    n = groups * nimg * hw * 8
+    if nimg < 1 or hw < 1 or x.numel() != n or v.numel() != n or not x.is_contiguous() or not v.is_contiguous():
+        raise ValueError(f"{what}: v, x contiguous [{groups} * nimg, hw, 8]")
+    if state is not None and (state.numel() != 3 * nimg * hw * 8 or not state.is_contiguous()):
+        raise ValueError(f"{what}: state contiguous [3, nimg, hw, 8]")
+
+
+def cfg_ddim_step_v(v, x, nimg, hw, c, guidance, sa_t, s1m_t, sa_p, s1m_p):
+    """cfg_ddim_step for a v-prediction network (saspa_cfg_ddim_step_v): v, x [2*nimg, hw, 8]; x in place, both CFG halves."""
+    _check_dev(v, x)
+    _vstep_shapes("cfg_ddim_step_v", v, x, nimg, hw, 2)
+    _lib.check(_L(x).saspa_cfg_ddim_step_v(_dt(x), _ptr(v), _ptr(x), nimg, hw, c, 8, float(guidance), float(sa_t), float(s1m_t),
+                                           float(sa_p), float(s1m_p), _stream()), "saspa_cfg_ddim_step_v")
+    return x
+
+
+def ddim_step_v(v, x, nimg, hw, c, sa_t, s1m_t, sa_p, s1m_p):
+    """ddim_step for a v-prediction network (no CFG): v, x [nimg, hw, 8]; x in place."""
+    _check_dev(v, x)
+    _vstep_shapes("ddim_step_v", v, x, nimg, hw, 1)
+    _lib.check(_L(x).saspa_ddim_step_v(_dt(x), _ptr(v), _ptr(x), nimg, hw, c, 8, float(sa_t), float(s1m_t), float(sa_p),
+                                       float(s1m_p), _stream()), "saspa_ddim_step_v")
+    return x
+
+
+def ddim_step_v_dev(v, x, nimg, hw, c, guidance, coefs, index, cfg=True):
+    """ddim_step_dev for a v-prediction network: the coefficients of row index[0] of the device table coefs [steps, 4]."""
+    _check_dev(v, x, coefs, index)
+    _vstep_shapes("ddim_step_v_dev", v, x, nimg, hw, 2 if cfg else 1)
+    _check_table("ddim_step_v_dev", "coefs", coefs, "steps", 4, index)
+    _lib.check(_L(x).saspa_ddim_step_v_dev(_dt(x), _ptr(v), _ptr(x), nimg, hw, c, 8, int(bool(cfg)), float(guidance), _ptr(coefs),
+                                           _ptr(index), _stream()), "saspa_ddim_step_v_dev")
+    return x
+
+
+def cfg_unipc_step_v(v, x, state, nimg, hw, c, guidance, row=None, table=None, index=None):
+    """cfg_unipc_step for a v-prediction network; the 12-float row carries alpha_t in slot 10 (UniPCMultistepScheduler.plan)."""
+    _check_dev(v, x, state, table, index)
+    _vstep_shapes("cfg_unipc_step_v", v, x, nimg, hw, 2, state)
+    if table is not None:
+        _check_table("cfg_unipc_step_v", "table", table, "steps", 12, index)
+    r = None if row is None else (C.c_float * 12)(*[float(t) for t in row])
+    _lib.check(_L(x).saspa_cfg_unipc_step_v(_dt(x), _ptr(v), _ptr(x), _ptr(state), nimg, hw, c, 8, float(guidance), r,
+                                            _ptr(table), _ptr(index), _stream()), "saspa_cfg_unipc_step_v")
+    return x
+
+
+def unipc_step_v(v, x, state, nimg, hw, c, row=None, table=None, index=None):
+    """unipc_step (no CFG) for a v-prediction network: v, x [nimg, hw, 8]; state [3, nimg, hw, 8]."""
+    _check_dev(v, x, state, table, index)
+    _vstep_shapes("unipc_step_v", v, x, nimg, hw, 1, state)
+    if table is not None:
+        _check_table("unipc_step_v", "table", table, "steps", 12, index)
+    r = None if row is None else (C.c_float * 12)(*[float(t) for t in row])
+    _lib.check(_L(x).saspa_unipc_step_v(_dt(x), _ptr(v), _ptr(x), _ptr(state), nimg, hw, c, 8, r, _ptr(table), _ptr(index),
+                                        _stream()), "saspa_unipc_step_v")
+    return x
+
+
 def index_add(index, delta=1):
     _check_dev(index)
     _lib.check(_L().saspa_index_add(_ptr(index), int(delta), _stream()), "saspa_index_add")

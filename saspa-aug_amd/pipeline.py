@@ -19,6 +19,7 @@ SASPA_FP16=1) makes `torch.float16` mean IEEE fp16 for the text tower, UNet, Con
 scheduler steps (the f16-MFMA build of the kernels); the VAE and the safety checker stay out
 of fp16 (`enable_fp16` docstring).  Off by default."""
 import contextlib
+import json
 import os
 
 import numpy as np
@@ -49,6 +50,19 @@ def _first_safetensors(d, names):
         if os.path.exists(p):
             return W.load_safetensors(p)
     raise FileNotFoundError(f"no safetensors weights in {d}")
+
+
+def _checkpoint_scheduler(base_dir):
+    """The scheduler a ControlNet-free checkpoint directory asks for: {base}/scheduler/scheduler_config.json's `prediction_type` on top
+    of the SD defaults (the SD-1.5 and SD-2.1-base repositories say "epsilon", which is the default; the 768-pixel
+    stabilityai/stable-diffusion-2-1 says "v_prediction").  None without the file.  An unserved type raises here, before any weight
+    is packed (scheduler.PREDICTION_TYPES)."""
+    path = os.path.join(base_dir, "scheduler", "scheduler_config.json")
+    if not os.path.exists(path):
+        return None
+    with open(path, encoding="utf-8") as f:
+        cfg = json.load(f)
+    return DDIMScheduler(prediction_type=cfg.get("prediction_type", "epsilon"))
 
 
 def _rgb_u8(image):
@@ -168,7 +182,21 @@ def _update(sch, eps, x, mem, nimg, hw, nc, cfg, guidance, branches=2, image_gui
     """The scheduler update that closes an evaluation, (guided) eps -> x in place, in one of two forms: `table` + `index` (the
     captured step: the evaluation's coefficients are read on the device) or `row` (the eager loop: the plan's entry of the
     evaluation; for DDIM, which has no plan, its timestep).  branches = 3: x holds the groups (uncond | image | text)."""
-    if isinstance(sch, UniPCMultistepScheduler):
+    if sch.config["prediction_type"] == "v_prediction":     # DDIM / UniPC only (PNDM refuses it at construction)
+        if branches == 3:
+            raise NotImplementedError("three guidance branches (InstructPix2Pix) with a v-prediction scheduler")
+        if isinstance(sch, UniPCMultistepScheduler):
+            if cfg:
+                ops.cfg_unipc_step_v(eps, x, mem["state"], nimg, hw, nc, guidance, row=row, table=table, index=index)
+            else:
+                ops.unipc_step_v(eps, x, mem["state"], nimg, hw, nc, row=row, table=table, index=index)
+        elif table is not None:
+            ops.ddim_step_v_dev(eps, x, nimg, hw, nc, guidance, table, index, cfg=cfg)
+        elif cfg:
+            ops.cfg_ddim_step_v(eps, x, nimg, hw, nc, guidance, *sch.step_coefficients(row))
+        else:
+            ops.ddim_step_v(eps, x, nimg, hw, nc, *sch.step_coefficients(row))
+    elif isinstance(sch, UniPCMultistepScheduler):
         if cfg:
             ops.cfg_unipc_step(eps, x, mem["state"], nimg, hw, nc, guidance, row=row, table=table, index=index)
         else:
@@ -353,7 +381,7 @@ class StableDiffusionControlNetPipeline:
         self._state_dicts = state_dicts
         self.cfgs = cfgs
         self.scheduler = scheduler or DDIMScheduler()
-        self.tokenizer = tokenizer or make_tokenizer(vocab=cfgs["text"]["vocab"])
+        self.tokenizer = tokenizer or make_tokenizer(vocab=cfgs["text"]["vocab"], pad_id=cfgs["text"].get("pad_id"))
         self.device = None
         self.dtype = None
         self.noise_dtype = None
@@ -803,7 +831,8 @@ class StableDiffusionImg2ImgPipeline(StableDiffusionControlNetImg2ImgPipeline):
     @classmethod
     def from_pretrained(cls, base_dir, cfgs=SD15):
         return cls(cls._base_state_dicts(base_dir, cfgs), cfgs,
-                   tokenizer=make_tokenizer(os.path.join(base_dir, "tokenizer"), cfgs["text"]["vocab"]))
+                   tokenizer=make_tokenizer(os.path.join(base_dir, "tokenizer"), cfgs["text"]["vocab"], cfgs["text"].get("pad_id")),
+                   scheduler=_checkpoint_scheduler(base_dir))
 
     def generate_batch_img2img(self, prompt_ids, negative_ids, source_u8, sample_noise, noise, num_inference_steps, strength,
                                guidance_scale=7.5, return_latents=False):
@@ -822,6 +851,56 @@ class StableDiffusionImg2ImgPipeline(StableDiffusionControlNetImg2ImgPipeline):
         ids = self.tokenizer(str(prompt))
         neg = self.tokenizer(negative_prompt if negative_prompt is not None else "")
         return self._output(self.generate_batch_img2img(ids, neg, src[None], e1, e2, num_inference_steps, strength, guidance_scale))
+
+
+class StableDiffusionPipeline(StableDiffusionControlNetPipeline):
+    """Drop-in for diffusers' `StableDiffusionPipeline` -- the reference's CONTROLNET = None, SDEDIT = 0 branch for sd_v1.5 and
+    sd_v2.1 (run_aug/run_aug.py:165-169; the "no structural conditioning" row of the ablations), called as `pipe(prompt,
+    num_inference_steps, generator, guidance_scale, negative_prompt)` (:235-241): text-to-image at the UNet's sample size (512 x 512
+    unless height / width are given).  The ControlNet pipeline without its ControlNet: the same CPU-generator noise, negative-prompt
+    cache, CFG (shared encoder prefix included) and the one-branch captured step of the ControlNet-free img2img pipeline; every
+    evaluation is the UNet alone.  The safety checker is built when the family ships one (SD15) and absent otherwise (SD21)."""
+    HAS_CONTROLNET = False
+
+    @classmethod
+    def from_pretrained(cls, base_dir, cfgs=SD15):
+        return cls(cls._base_state_dicts(base_dir, cfgs), cfgs,
+                   tokenizer=make_tokenizer(os.path.join(base_dir, "tokenizer"), cfgs["text"]["vocab"], cfgs["text"].get("pad_id")),
+                   scheduler=_checkpoint_scheduler(base_dir))
+
+    @torch.no_grad()
+    def generate_batch(self, prompt_ids, negative_ids, latents, num_inference_steps, guidance_scale=7.5, return_latents=False,
+                       latents_on_device=False):
+        """prompt_ids [B,77], negative_ids [1,77] or [B,77], latents [B,4,h,w] noise (or, with latents_on_device, the channels-last
+        [B,h,w,8] device tensor from `latents_to_device`); the images are 8h x 8w.  Returns a device u8 tensor [B,8h,8w,3]."""
+        self._need_device()
+        if guidance_scale <= 1.0:
+            raise NotImplementedError("guidance_scale <= 1 (no CFG) belongs to the SDXL-Turbo branch (SURVEY a9)")
+        nch = self.cfgs["unet"]["in_channels"]
+        if latents.dim() != 4 or latents.shape[-1 if latents_on_device else 1] != (8 if latents_on_device else nch):
+            raise ValueError(f"latents shape {tuple(latents.shape)}: expected [B,{nch},h,w] noise (or [B,h,w,8] on the device)")
+        b, h, w = (latents.shape[0], latents.shape[1], latents.shape[2]) if latents_on_device else \
+            (latents.shape[0], latents.shape[2], latents.shape[3])
+        mult = 1 << (len(self.cfgs["unet"]["block_out"]) - 1)
+        if h % mult or w % mult:
+            raise ValueError(f"image sides must be multiples of {8 * mult} (got {8 * h}x{8 * w})")
+        ctx = self._guidance_context(self._negative_context(negative_ids), self._positive_context(prompt_ids))
+        x = latents if latents_on_device else self.latents_to_device(latents)
+        x2 = torch.cat([x, x], 0).contiguous()
+        cemb2 = torch.zeros((1,), device=self.device, dtype=self.dtype)           # placeholder: nothing reads it
+        self._sample(x2, b, h * w, ctx, cemb2, num_inference_steps, guidance_scale, 0.0)
+        return self._decode(x2[:b], return_latents)
+
+    def __call__(self, prompt=None, height=None, width=None, num_inference_steps=50, generator=None, guidance_scale=7.5,
+                 negative_prompt=None, **unused):
+        self._need_device()
+        if prompt is None:
+            raise ValueError("`prompt` is required")
+        side = 8 * self.cfgs["unet"].get("sample_size", 64)                       # diffusers: unet.config.sample_size * vae_scale_factor
+        lat = self._noise(np.empty((height or side, width or side, 3), np.uint8), generator)
+        ids = self.tokenizer(str(prompt))
+        neg = self.tokenizer(negative_prompt if negative_prompt is not None else "")
+        return self._output(self.generate_batch(ids, neg, lat, num_inference_steps, guidance_scale))
 
 
 class StableDiffusionInstructPix2PixPipeline(StableDiffusionImg2ImgPipeline):

@@ -315,18 +315,26 @@ def init_pipeline(base_model, controlnet, SDEdit, use_compile=False, sampler="dd
             pipe.set_vae_mode(xl_vae)
         pipe.upcast_vae()
         return pipe
-    if base_model == "sd_v1.5" and controlnet is None and SDEdit:
-        # run_aug/run_aug.py:163-165: StableDiffusionImg2ImgPipeline -- the Real-Guidance form (CONTROLNET = None, SDEDIT = 1;
-        # run_aug/run_aug_real_guidance.py:520-523), scheduler switched like every non-BLIP pipeline (:216-221)
-        from .pipeline import StableDiffusionImg2ImgPipeline
-        cfgs = cfgs or SD15
+    if base_model == "sd_v2.1" and controlnet is not None:
+        raise NotImplementedError(
+            f"(sd_v2.1, {controlnet}, SDEdit={SDEdit}): the reference pairs sd_v2.1 with the SD-1.5 ControlNets "
+            f"({CONTROLNET_DICT_SD[controlnet]}, run_aug/run_aug.py:184), whose cross-attention takes a 768-wide text context; the "
+            "SD-2.1 text tower is 1024 wide, so that pipeline cannot run.  sd_v2.1 is built without a ControlNet (CONTROLNET = None)")
+    if base_model in ("sd_v1.5", "sd_v2.1") and controlnet is None:
+        # run_aug/run_aug.py:165-169: StableDiffusionImg2ImgPipeline (SDEDIT = 1 -- for sd_v1.5 the Real-Guidance form,
+        # run_aug/run_aug_real_guidance.py:520-523) or StableDiffusionPipeline (SDEDIT = 0, text-to-image); scheduler switched like
+        # every non-BLIP pipeline (:216-221) -- the checkpoint's prediction_type travels with its config
+        from .config import SD21
+        from .pipeline import StableDiffusionImg2ImgPipeline, StableDiffusionPipeline
+        _Cls = StableDiffusionImg2ImgPipeline if SDEdit else StableDiffusionPipeline
+        cfgs = cfgs or (SD21 if base_model == "sd_v2.1" else SD15)
         if state_dicts is not None:
-            pipe = StableDiffusionImg2ImgPipeline(state_dicts, cfgs)
+            pipe = _Cls(state_dicts, cfgs)
         elif weights_dir:
-            pipe = StableDiffusionImg2ImgPipeline.from_pretrained(os.path.join(weights_dir, BASE_MODEL_DICT[base_model]), cfgs)
+            pipe = _Cls.from_pretrained(os.path.join(weights_dir, BASE_MODEL_DICT[base_model]), cfgs)
         else:
             logging.info("no WEIGHTS_DIR given: using architecture-exact SYNTHETIC weights (no checkpoint available offline)")
-            pipe = StableDiffusionImg2ImgPipeline.from_synthetic(cfgs, seed=0)
+            pipe = _Cls.from_synthetic(cfgs, seed=0)
         pipe.scheduler = _scheduler_for(pipe)
         return pipe
     if base_model == "ip2p":
@@ -351,10 +359,10 @@ def init_pipeline(base_model, controlnet, SDEdit, use_compile=False, sampler="dd
         return pipe
     if base_model != "sd_v1.5" or controlnet not in CONTROLNET_DICT_SD:
         raise NotImplementedError(
-            f"({base_model}, {controlnet}, SDEdit={SDEdit}): sd_v1.5 (text-to-image and SDEdit img2img with the canny or HED "
-            "ControlNet; ControlNet-free SDEdit img2img), blip_diffusion and sd_xl-turbo with the canny ControlNet, and ip2p without "
-            "a ControlNet are built; blip_diffusion-edit / sd_v2.1 / sd_xl and the ControlNet-free text-to-image pipelines are "
-            "baseline branches")
+            f"({base_model}, {controlnet}, SDEdit={SDEdit}): sd_v1.5 (text-to-image and SDEdit img2img, with the canny or HED "
+            "ControlNet or without one), sd_v2.1 without a ControlNet (text-to-image and SDEdit img2img), blip_diffusion and "
+            "sd_xl-turbo with the canny ControlNet, and ip2p without a ControlNet are built; blip_diffusion-edit, sd_xl and the "
+            "ControlNet-free forms of sd_xl-turbo / blip_diffusion are not")
     cfgs = cfgs or SD15
     if SDEdit:                                  # run_aug/run_aug.py:203-206: StableDiffusionControlNetImg2ImgPipeline
         from .pipeline import StableDiffusionControlNetImg2ImgPipeline as _Cls
@@ -379,10 +387,13 @@ def pass_thorugh_pipe(base_model, pipe, prompt, orig_img, SDEdit, SDEdit_strengt
     pipe_args = {"prompt": str(prompt), "num_inference_steps": num_inference_steps, "generator": generator,
                  "guidance_scale": guidance_scale, "negative_prompt": negative_prompt}
     ip2p = "ip2p" in base_model
-    built = (control_image is None and not SDEdit) if ip2p else (control_image is not None or SDEdit)
+    # (no control image, no SDEdit: StableDiffusionPipeline, built for the two base models init_pipeline builds it for)
+    built = (control_image is None and not SDEdit) if ip2p else \
+        (control_image is not None or SDEdit or base_model in ("sd_v1.5", "sd_v2.1"))
     if base_model == "blip_diffusion-edit" or not built:
         raise NotImplementedError("built call forms: ControlNet text-to-image / SDEdit img2img / BLIP-Diffusion, the "
-                                  "ControlNet-free SDEdit img2img (Real-Guidance) and ControlNet-free InstructPix2Pix")
+                                  "ControlNet-free SDEdit img2img (Real-Guidance), ControlNet-free text-to-image (sd_v1.5, sd_v2.1) "
+                                  "and ControlNet-free InstructPix2Pix")
     if "blip_diffusion" in base_model:                     # run_aug/run_aug.py:243-250
         pipe_args["reference_image"] = orig_img
         pipe_args["source_subject_category"] = blip_src_category
@@ -747,6 +758,12 @@ def hip_batch_generator(pipe, s: Settings, record=None):
             else:
                 out = pipe.generate_batch_img2img(ids, neg_ids, src, ctrl, lat[0::2], lat[1::2], s.NUM_INFERENCE_STEPS,
                                                   s.SDEDIT_STRENGTH, s.GUIDANCE_SCALE, s.CONTROLNET_CONDITIONING_SCALE)
+        elif ctrl is None:
+            # ControlNet-free text-to-image (run_aug/run_aug.py:165-169, :235-241): StableDiffusionPipeline, one draw per item.  The
+            # image takes the source's planned size like every other form of this loop (the reference's call passes no size and gets
+            # the UNet's 512 x 512); the source itself only names the files and feeds the filters
+            ids = np.concatenate([tok(it.prompt) for it in batch])
+            out = pipe.generate_batch(ids, neg_ids, lat, s.NUM_INFERENCE_STEPS, s.GUIDANCE_SCALE)
         else:
             ids = np.concatenate([tok(it.prompt) for it in batch])
             out = pipe.generate_batch(ids, neg_ids, ctrl, lat, s.NUM_INFERENCE_STEPS, s.GUIDANCE_SCALE,

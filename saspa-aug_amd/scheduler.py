@@ -24,13 +24,20 @@ SDXL_TURBO_SCHEDULER_CONFIG = dict(
 )
 
 
+# what the fused step kernels serve: epsilon (saspa_cfg_ddim_step, saspa_cfg_unipc_step, ...) and v_prediction (their _v forms, DDIM
+# and UniPC only; the 768-pixel stabilityai/stable-diffusion-2-1 checkpoint).  "sample" prediction is not built.
+PREDICTION_TYPES = ("epsilon", "v_prediction")
+
+
 class DDIMScheduler:
     def __init__(self, **config):
         self.config = dict(SD15_SCHEDULER_CONFIG)
         self.config.update(config)
         c = self.config
-        if c["beta_schedule"] != "scaled_linear" or c["prediction_type"] != "epsilon" or c["clip_sample"]:
-            raise NotImplementedError("only the SD-1.5 DDIM configuration is implemented")
+        if c["beta_schedule"] != "scaled_linear" or c["prediction_type"] not in PREDICTION_TYPES or c["clip_sample"] \
+                or c.get("thresholding"):
+            raise NotImplementedError("only the SD-1.5 / SD-2.1 DDIM configurations (epsilon or v_prediction, no clipping, no "
+                                      "thresholding) are implemented")
         n = c["num_train_timesteps"]
         betas = torch.linspace(c["beta_start"] ** 0.5, c["beta_end"] ** 0.5, n, dtype=torch.float32) ** 2
         self.alphas_cumprod = torch.cumprod(1.0 - betas, dim=0)
@@ -169,8 +176,10 @@ class UniPCMultistepScheduler:
                            final_sigmas_type="zero")
         self.config.update(config)
         c = self.config
-        if c["beta_schedule"] != "scaled_linear" or c["prediction_type"] != "epsilon" or not c["predict_x0"]:
-            raise NotImplementedError("only the SD-1.5 UniPC configuration (epsilon, predict_x0) is implemented")
+        if c["beta_schedule"] != "scaled_linear" or c["prediction_type"] not in PREDICTION_TYPES or not c["predict_x0"] \
+                or c.get("thresholding"):
+            raise NotImplementedError("only the SD-1.5 / SD-2.1 UniPC configurations (epsilon or v_prediction, predict_x0, no "
+                                      "thresholding) are implemented")
         if c["solver_order"] not in (1, 2) or c["solver_type"] not in ("bh1", "bh2") or c["timestep_spacing"] not in ("leading", "trailing"):
             raise NotImplementedError("UniPC: solver_order <= 2, bh1 / bh2, leading / trailing spacing")
         n = c["num_train_timesteps"]
@@ -252,7 +261,8 @@ class UniPCMultistepScheduler:
         return float(c_x), float(c_m0), float(c_m1), float(c_mt)
 
     def plan(self, num_inference_steps=None):
-        """[(t, row)] with row = [1/alpha_t, sigma_t (convert), corr flag, c_last, c_m0, c_m1, c_mt, p_x, p_m0, p_m1, 0, 0]."""
+        """[(t, row)] with row = [1/alpha_t, sigma_t (convert), corr flag, c_last, c_m0, c_m1, c_mt, p_x, p_m0, p_m1, 0, 0];
+        with v_prediction slot 10 carries alpha_t."""
         if num_inference_steps is not None:
             self.set_timesteps(num_inference_steps)
         n_steps = len(self.timesteps)
@@ -261,6 +271,8 @@ class UniPCMultistepScheduler:
         for k, t in enumerate(int(v) for v in self.timesteps):
             a_k, s_k = self._alpha_sigma(sg[k])
             row = [1.0 / a_k, s_k, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0]
+            if self.config["prediction_type"] == "v_prediction":
+                row[10] = a_k                                # x0 = alpha_t x - sigma_t v (saspa_cfg_unipc_step_v reads r10, not r0)
             if k > 0:                                        # corrector of the previous predictor step, at ITS order
                 hist = [sg[k - 2]] if k >= 2 else []
                 cx, cm0, cm1, cmt = self._bh(sg[k], sg[k - 1], hist, this_order, True)

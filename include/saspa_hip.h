@@ -263,6 +263,23 @@ int saspa_flash_attn_bf16(const SaspaAttnParams* p, void* stream);
 int saspa_attn_wide(int dtype, const void* q, int ldq, long long sqb, const void* k, int ldk, long long skb, const void* v, int ldv,
                     long long svb, void* out, int ldo, long long sob, int batch, int nq, int nk, int d, float scale, void* stream);
 
+/* saspa_attn_wide on fp32 STORAGE with x3 products (default library only): ONE WIDE head per batch entry,
+ *   out[b][i][:] = sum_j softmax_j(scale * q[b][i][:] . k[b][j][:]) * v[b][j][:]
+ * the mid-block attention of the fp32 VAE without its n x n score matrix.  The call shape of saspa_attn_wide minus `dtype`: q, k, v and
+ * out point to float, row-major [batch][n][ld], each with its own row pitch (ld*) and batch stride (s*b) in elements -- so q, k and v
+ * may be column slices of one fused Q | K | V buffer.  V is read row-major.  d is a multiple of 64 with 192 <= d <= 512 (narrower
+ * heads: saspa_flash_attn_f32x3).  nq, nk >= 1, otherwise arbitrary; keys >= nk of the last key tile are masked inside the kernel and
+ * their rows are never read.  No workspace, no allocation, no host synchronisation; capturable.
+ * Arithmetic: the contract of saspa_flash_attn_f32x3 below.  Every fp32 operand is split as hi = bf16(x), lo = bf16(x - hi) (round to
+ * nearest) and every product sum -- Q K^T and P V alike -- is lo hi + hi lo + hi hi accumulated in fp32 on bf16 MFMAs; scale * log2(e)
+ * is applied to the fp32 logit; running maximum, exp2, row sum and the online rescale are fp32; P is split from its fp32 value and
+ * NEVER rounded to one bf16; O accumulates in fp32 and is divided by the fp32 row sum.  Every reduction has a fixed order, nothing is
+ * atomic: a batch entry's bytes depend neither on the batch size nor on its position in the batch.
+ * Host-side validation, before any launch: null pointer, batch / nq / nk < 1, batch > 65535, d outside the range above, a pitch shorter
+ * than d -> SASPA_EINVAL; pointers not 16-byte aligned, pitches or batch strides not multiples of 4 -> SASPA_EALIGN. */
+int saspa_attn_wide_f32x3(const void* q, int ldq, long long sqb, const void* k, int ldk, long long skb, const void* v, int ldv,
+                          long long svb, void* out, int ldo, long long sob, int batch, int nq, int nk, int d, float scale, void* stream);
+
 /* Flash attention on fp32 STORAGE with x3 products (the fused form of the fp32 parity path; default library only):
  *   o[b][i][h*D+d] = sum_j softmax_j(scale * q[b][i][h,:] . k[b][j][h,:]) * v[b][j][h,d]
  * Takes SaspaAttnParams as saspa_flash_attn_bf16 does, with q, k, vt and o pointing to float; pitches and batch strides in elements.

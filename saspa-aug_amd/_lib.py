@@ -147,6 +147,7 @@ SYMBOLS = {
     "saspa_flash_attn_f32x3": (_I, [C.POINTER(AttnParams), _P]),
     "saspa_softmax_rows": (_I, [_I, _P, _LL, _I, _I, _F, _I, _I, _P]),
     "saspa_attn_wide": (_I, [_I, _P, _I, _LL, _P, _I, _LL, _P, _I, _LL, _P, _I, _LL, _I, _I, _I, _I, _F, _P]),
+    "saspa_attn_wide_f32x3": (_I, [_P, _I, _LL, _P, _I, _LL, _P, _I, _LL, _P, _I, _LL, _I, _I, _I, _I, _F, _P]),
     "saspa_groupnorm_stats": (_I, [C.POINTER(GroupNormParams), _P]),
     "saspa_groupnorm_apply": (_I, [C.POINTER(GroupNormParams), _P]),
     "saspa_layernorm": (_I, [_I, _P, _I, _P, _I, _LL, _I, _P, _P, _F, _P]),

@@ -17,6 +17,7 @@ Layout decisions (MI355X-first, not a translation of diffusers' NCHW modules):
     epilogue (residual = UNet skip), so the UNet decoder reads the summed tensors.
 
 Semantics follow [upstream] diffusers 0.32.2 as listed in SURVEY.md 3.2 / 8(a7)."""
+import contextlib
 import math
 import os
 
@@ -225,6 +226,17 @@ def vae_attn_fused(dtype):
     if mode not in ("unfused", "fused"):
         raise ValueError(f"SASPA_VAE_ATTN must be 'unfused' or 'fused', got {mode!r}")
     return dtype == torch.float16 or (dtype == torch.bfloat16 and mode == "fused")
+
+
+def vae_attn_f32_fused():
+    """SASPA_VAE_ATTN_F32=fused: an fp32-storage VAE whose mid-block head passes wide_head() runs its attention as the fused x3
+    launch (ops.attn_wide_x3: no n x n fp32 score matrix), under either f32_gemm.  Read when a VAE is packed; unset or 'unfused'
+    (the default): the launches of the unfused path exactly.  vae_attn_fused(torch.float32) stays False: that predicate speaks
+    of SASPA_VAE_ATTN and the 16-bit kernel."""
+    mode = os.environ.get("SASPA_VAE_ATTN_F32", "unfused")
+    if mode not in ("unfused", "fused"):
+        raise ValueError(f"SASPA_VAE_ATTN_F32 must be 'unfused' or 'fused', got {mode!r}")
+    return mode == "fused"
 
 
 def attention_core(q, k, vt, heads, nq, nk, causal=False, prescaled=False, v_rowmajor=False):
@@ -874,10 +886,10 @@ class ControlNet(_Net):
 class VAEDecoder:
     """AutoencoderKL.decode."""
 
-    def __init__(self, sd, cfg, dev, dtype, f32_gemm="exact"):
-        self.cfg, self.dev, self.dtype = cfg, dev, dtype
-        # fp32 VAE only: "exact" = fp32 MFMA (parity path), "x3" = three bf16 MFMAs per product (ops.f32_gemm_mode)
-        self.f32_gemm = f32_gemm if dtype == torch.float32 else "exact"
+    OFFSET_LIMIT = (1 << 31) - 1      # the kernels address an operand with 32-bit byte offsets (tests lower it on an instance)
+
+    def __init__(self, sd, cfg, dev, dtype, f32_gemm="exact", attn_f32=None):
+        self._modes(cfg, dev, dtype, f32_gemm, attn_f32)
         pk = self.pk = _Packed(sd, dev, dtype)
         self.p = pk.p
         pk.conv("post_quant_conv")
@@ -894,6 +906,17 @@ class VAEDecoder:
         pk.sd = None
         if self.f32_gemm == "x3" and os.environ.get("SASPA_X3_PRESPLIT", "1") != "0":
             self._presplit()
+
+    def _modes(self, cfg, dev, dtype, f32_gemm, attn_f32):
+        if f32_gemm not in ("exact", "x3"):
+            raise ValueError(f"f32_gemm must be 'exact' or 'x3', got {f32_gemm!r}")
+        if attn_f32 not in (None, "unfused", "fused"):
+            raise ValueError(f"attn_f32 must be None (SASPA_VAE_ATTN_F32), 'unfused' or 'fused', got {attn_f32!r}")
+        self.cfg, self.dev, self.dtype = cfg, dev, dtype
+        # fp32 VAE only: "exact" = fp32 MFMA (parity path), "x3" = three bf16 MFMAs per product (ops.f32_gemm_mode)
+        self.f32_gemm = f32_gemm if dtype == torch.float32 else "exact"
+        # fp32 VAE only: the mid-block attention as one fused x3 launch; None = the knob, read now
+        self.attn_f32_fused = dtype == torch.float32 and (vae_attn_f32_fused() if attn_f32 is None else attn_f32 == "fused")
 
     def _presplit(self):
         """SASPA_F32X3 (round 6): the conv weights are stored PRE-SPLIT into their bf16 hi | lo halves (weights.presplit_x3,
@@ -918,8 +941,9 @@ class VAEDecoder:
         # The mid block's attention is ONE head as wide as the block (512 channels in the SD / SDXL VAEs).  fp16: always the fused
         # wide-head launch (ops.attn_wide) -- the unfused path stores the UNSCALED q . k in the 16-bit type, which passes 65504 as
         # soon as 512-channel activations are a little above 10, and is not offered.  bf16: SASPA_VAE_ATTN=fused (A/B knob, read
-        # when the weights are packed; default off: the launches of the unfused path exactly).  fp32 storage never.
-        self.fused_attn = vae_attn_fused(self.dtype)
+        # when the weights are packed; default off: the launches of the unfused path exactly).  fp32 storage: SASPA_VAE_ATTN_F32=fused / attn_f32="fused"
+        # (ops.attn_wide_x3, default off likewise) -- the unfused path's score matrix is n x n fp32, 1 GiB per image at 1024 x 1024.
+        self.fused_attn = vae_attn_fused(self.dtype) or self.attn_f32_fused
         if self.fused_attn and wide_head(c):
             # one Q | K | V projection whose column slices are the kernel's operands (V row-major; its bias is in the out bias)
             p = self.p
@@ -951,7 +975,8 @@ class VAEDecoder:
         if (a + ".qkv.w") in p:      # fused wide head (_pack_mid): no [B, 1, n, n] score matrix, no logit rounded to 16 bits
             qkv = ops.linear(h, *_wb(p, a + ".qkv"))
             o = torch.empty((b, n, c), device=x.device, dtype=x.dtype)
-            ops.attn_wide(qkv[:, :, :c], qkv[:, :, c:2 * c], qkv[:, :, 2 * c:], o, n, n, c ** -0.5)
+            wide = ops.attn_wide_x3 if x.dtype == torch.float32 else ops.attn_wide
+            wide(qkv[:, :, :c], qkv[:, :, c:2 * c], qkv[:, :, 2 * c:], o, n, n, c ** -0.5)
             return ops.linear(o, *_wb(p, a + ".o"), residual=x.view(b, n, c)).view(b, hh, ww, c)
         qk = ops.linear(h, *_wb(p, a + ".qk"))
         vt = project_vt(h, p[a + ".v.w"], n)
@@ -965,11 +990,19 @@ class VAEDecoder:
         b, h, w, _ = z.shape
         esz = 2 if _is_half(self.dtype) else 4
         per_img = 64 * h * w * self.cfg["block_out"][min(1, len(self.cfg["block_out"]) - 1)] * esz
-        chunk = max(1, ((1 << 31) - 1) // per_img)
-        with ops.f32_gemm_mode(self.f32_gemm):
+        return self._chunked(self._decode, z, per_img)
+
+    def _gemm_scope(self):
+        return ops.f32_gemm_mode(self.f32_gemm)
+
+    def _chunked(self, run, x, per_img):
+        """run(x) under this VAE's fp32 GEMM mode, at most OFFSET_LIMIT // per_img images per launch sequence."""
+        b = x.shape[0]
+        chunk = max(1, self.OFFSET_LIMIT // per_img)
+        with self._gemm_scope():
             if b <= chunk:
-                return self._decode(z)
-            return torch.cat([self._decode(z[i:i + chunk].contiguous()) for i in range(0, b, chunk)], 0)
+                return run(x)
+            return torch.cat([run(x[i:i + chunk].contiguous()) for i in range(0, b, chunk)], 0)
 
     def _decode(self, z):
         p, cfg = self.p, self.cfg
@@ -993,8 +1026,8 @@ class VAEEncoder(VAEDecoder):
     blocks (2 resnets + a stride-2 conv that zero-pads right / bottom only), mid block (resnet, single-head attention,
     resnet), GroupNorm + SiLU, conv_out, quant_conv -> [B,h,w,8] = mean (channels 0..3) | logvar (4..7)."""
 
-    def __init__(self, sd, cfg, dev, dtype):
-        self.cfg, self.dev, self.dtype = cfg, dev, dtype
+    def __init__(self, sd, cfg, dev, dtype, f32_gemm="exact", attn_f32=None):
+        self._modes(cfg, dev, dtype, f32_gemm, attn_f32)
         pk = self.pk = _Packed(sd, dev, dtype)
         self.p = pk.p
         pk.conv("encoder.conv_in")
@@ -1009,9 +1042,27 @@ class VAEEncoder(VAEDecoder):
         pk.conv("encoder.conv_out")
         pk.conv("quant_conv")
         pk.sd = None
+        if self.f32_gemm == "x3" and os.environ.get("SASPA_X3_PRESPLIT", "1") != "0":
+            self._presplit()
+
+    def _gemm_scope(self):
+        """"exact", the default, enters nothing: the encoder runs in its caller's mode, as it always did."""
+        return ops.f32_gemm_mode("x3") if self.f32_gemm == "x3" else contextlib.nullcontext()
 
     def encode(self, x):
-        """x: [B,H,W,8] pixels in [-1,1] (3 live channels) -> moments [B,H/8,W/8,8]."""
+        """x: [B,H,W,8] pixels in [-1,1] (3 live channels) -> moments [B,H/8,W/8,8].  As in decode, the widest activation -- full
+        resolution x block_out[0] channels, 512 MiB per image at 1024 x 1024 in fp32, or the unfused mid-block attention's score matrix, 1 GiB
+        there -- bounds the images per launch sequence."""
+        b, hh, ww, _ = x.shape
+        esz = 2 if _is_half(self.dtype) else 4
+        per_img = hh * ww * self.cfg["block_out"][0] * esz
+        c, lv = self.cfg["block_out"][-1], len(self.cfg["block_out"]) - 1
+        if "encoder.mid_block.attentions.0.qkv.w" not in self.p and not (_is_half(self.dtype) and c <= 160):
+            n = (hh >> lv) * (ww >> lv)                      # the unfused mid-block attention: an n x n score matrix per image
+            per_img = max(per_img, n * n * esz)
+        return self._chunked(self._encode, x, per_img)
+
+    def _encode(self, x):
         p, cfg = self.p, self.cfg
         h = ops.conv(x, *_wb(p, "encoder.conv_in"), kh=3, kw=3, pad=1)
         n_lvl = len(cfg["block_out"])

@@ -909,6 +909,28 @@ def attn_wide(q, k, v, out, nq, nk, scale):
     return out
 
 
+def attn_wide_x3(q, k, v, out, nq, nk, scale):
+    """attn_wide's operands in fp32 (192 <= d <= 512, d % 64 == 0): q [B, nq, d], k / v [B, nk, d] and out [B, nq, d] views whose last
+    dim is contiguous -- column slices of one fused Q | K | V buffer as they are; V row-major.  One fused launch with x3 products
+    (three bf16 MFMAs per product, counted as one product in the recorder's FLOPs), no score matrix, no workspace.  Anything the
+    library refuses raises with its SASPA_E* code, nothing is launched."""
+    _check_dev(q, k, v, out)
+    _same_dtype("attn_wide_x3", q, k=k, v=v, out=out)
+    if q.dtype != torch.float32:
+        raise TypeError("attn_wide_x3 is the fp32 path; 16-bit tensors use attn_wide")
+    for name, t in (("q", q), ("k", k), ("v", v), ("out", out)):
+        if t.dim() != 3 or t.stride(2) != 1:
+            raise ValueError(f"attn_wide_x3: {name} must be [B, n, d] with a contiguous last dim, got {tuple(t.shape)} / {t.stride()}")
+    b, d = q.shape[0], q.shape[2]
+    lib = _L(q)
+    _launch("attn_wide_x3", 4.0 * b * nq * nk * d,
+            lambda: _lib.check(lib.saspa_attn_wide_f32x3(_ptr(q), q.stride(1), q.stride(0), _ptr(k), k.stride(1), k.stride(0),
+                                                         _ptr(v), v.stride(1), v.stride(0), _ptr(out), out.stride(1), out.stride(0),
+                                                         b, int(nq), int(nk), d, float(scale), _stream()), "saspa_attn_wide_f32x3"),
+            (b, 1, nq, nk, d))
+    return out
+
+
 def _decode_attn_params(q, k, v, out, lens, heads, d, nk, group, scale):
     p = _lib.DecodeAttnParams()
     p.dtype = _dt(q)

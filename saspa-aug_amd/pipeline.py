@@ -1225,6 +1225,20 @@ class StableDiffusionXLControlNetPipeline(StableDiffusionControlNetPipeline):
         b, hh, ww, _ = ctrl.shape
         self._check_sides(ctrl, "control image")
         self._check_latents(latents, self.cfgs["unet"]["in_channels"], ctrl, "control", latents_on_device)
+
+        def start():
+            x = latents if latents_on_device else self.latents_to_device(latents)
+            # (the loop runs in place: not on the caller's tensor; with guidance the doubling below copies)
+            return x.clone(memory_format=torch.contiguous_format) if latents_on_device and not cfg else x
+        return self._denoise_decode(prompt_ids, negative_ids, ctrl, start, num_inference_steps, guidance_scale,
+                                    controlnet_conditioning_scale, return_latents, prompt_ids_2, negative_ids_2)
+
+    def _denoise_decode(self, prompt_ids, negative_ids, ctrl, start, num_inference_steps, guidance_scale, controlnet_conditioning_scale,
+                        return_latents, prompt_ids_2, negative_ids_2, t_start=0):
+        """Text towers, added conditioning, control embedding, `start()` -> the initial latents [B,h,w,8], the steps from index
+        t_start of the schedule, decode: what the text-to-image and the img2img form share."""
+        cfg = guidance_scale > 1.0
+        b, hh, ww, _ = ctrl.shape
         ids1 = np.asarray(prompt_ids.cpu() if torch.is_tensor(prompt_ids) else prompt_ids)
         ids2 = self.pad_ids_2(ids1) if prompt_ids_2 is None else prompt_ids_2
         ctx, pooled = self.encode_prompts_xl(ids1, ids2)
@@ -1242,15 +1256,13 @@ class StableDiffusionXLControlNetPipeline(StableDiffusionControlNetPipeline):
         time_ids = [[hh, ww, 0, 0, hh, ww]] * ctx.shape[0]       # original_size + crops_coords_top_left + target_size
         with self._f32_scope():
             cemb = self.controlnet.cond_embedding(ops.u8_to_act(ctrl, self.dtype))
-        x = latents if latents_on_device else self.latents_to_device(latents)
+        x = start()
         if cfg:
             x = torch.cat([x, x], 0).contiguous()
             cemb = torch.cat([cemb, cemb], 0)
-        elif latents_on_device:
-            x = x.clone(memory_format=torch.contiguous_format)     # (the loop runs in place: not on the caller's tensor)
         # (DDIM, or UniPC: run_aug/run_aug.py:223-226 with sampler = "unipcmultistep")
         self._sample(x, b, (hh // 8) * (ww // 8), ctx, cemb, num_inference_steps, guidance_scale, controlnet_conditioning_scale,
-                     cfg=cfg, added=(pooled, time_ids))
+                     t_start=t_start, cfg=cfg, added=(pooled, time_ids))
         return self._decode(x[:b], return_latents)
 
     def __call__(self, prompt=None, image=None, num_inference_steps=50, generator=None, guidance_scale=5.0,
@@ -1270,3 +1282,128 @@ class StableDiffusionXLControlNetPipeline(StableDiffusionControlNetPipeline):
             n2 = self.pad_ids_2(self.tokenizer_2(str(negative_prompt)))
         return self._output(self.generate_batch(ids1, n1, ctrl[None], lat, num_inference_steps, guidance_scale,
                                                 controlnet_conditioning_scale, prompt_ids_2=ids2, negative_ids_2=n2))
+
+
+def img2img_steps(num_inference_steps, strength):
+    """diffusers' get_timesteps for img2img (SDEdit), on the host: (index of the first kept timestep, number of kept steps).
+    init_timestep = min(int(steps * strength), steps), t_start = max(steps - init_timestep, 0); nothing left to run is a ValueError
+    (RECALLED, as the class below marks it)."""
+    if not 0.0 <= strength <= 1.0:
+        raise ValueError(f"The value of strength should in [0.0, 1.0] but is {strength}")
+    t_start, kept = StableDiffusionControlNetImg2ImgPipeline.kept_steps(num_inference_steps, strength)
+    if kept < 1:
+        raise ValueError(f"After adjusting the num_inference_steps by strength parameter: {strength}, the number of pipeline "
+                         f"steps is {kept} which is < 1 and not appropriate for this pipeline.")
+    return t_start, kept
+
+
+class StableDiffusionXLControlNetImg2ImgPipeline(StableDiffusionXLControlNetPipeline):
+    """Drop-in for diffusers' `StableDiffusionXLControlNetImg2ImgPipeline` as the reference builds it for `BASE_MODEL =
+    "sd_xl-turbo"`, `CONTROLNET = "canny"`, `SDEDIT = 1` (run_aug/run_aug.py:188-193) and calls it (:257-260, :274-276):
+    `pipe(prompt, image=<source PIL>, control_image=<canny PIL>, strength, num_inference_steps, generator, guidance_scale,
+    negative_prompt, controlnet_conditioning_scale)`.  The text-to-image XL form with the SD-1.5 img2img form's start: the source
+    image goes through the VAE encoder, the latent is sampled from the posterior, scaled and noised to the first kept timestep in one
+    kernel (`saspa_vae_sample_noise`), and the kept DDIM steps, the decode and the guards are the parent's.
+
+    diffusers is not installed where this was written, so what is mirrored from it is RECALLED, not verified against its source:
+    - RECALLED: get_timesteps -- init_timestep = min(int(steps * strength), steps), t_start = max(steps - init_timestep, 0); zero
+      remaining steps raise ValueError (here before anything is encoded or launched: img2img_steps);
+    - RECALLED: prepare_latents -- vae.encode(image).latent_dist.sample(generator) * 0.13025, then scheduler.add_noise at the first
+      kept timestep with a second draw from the same generator (posterior sample first, then the step noise);
+    - RECALLED: add_time_ids = (H, W, 0, 0, H, W) from the control image's size; sdxl-turbo's UNet has no aesthetic-score
+      conditioning (requires_aesthetics_score = false), so none is appended;
+    - RECALLED: the scheduler is DDIMScheduler.from_config(pipe.scheduler.config), timestep_spacing "trailing" (the reference,
+      run_aug/run_aug.py:223);
+    - RECALLED: guidance_scale <= 1 -> no classifier-free guidance, as in the text-to-image form.
+
+    The encoder follows the pipeline's VAE mode (set_vae_mode / SASPA_XL_VAE / upcast_vae): it is packed from the retained VAE state
+    dict in the decoder's dtype and fp32 GEMM form and re-packed whenever those change.  In "f16" mode the non-finite guard also
+    covers the encoder's moments: such an item is flagged in `last_nonfinite` exactly as a non-finite decode is.  The fused fp32
+    mid-block attention (ops.attn_wide_x3) is opt-in here as everywhere: SASPA_VAE_ATTN_F32=fused."""
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.vae_encoder = None
+        self._enc_nonfinite = None
+
+    def _sync_encoder(self):
+        if self._vae_sd is None or "encoder.conv_in.weight" not in self._vae_sd:
+            raise KeyError("the VAE checkpoint has no encoder half: img2img (SDEdit) needs vae/encoder.* and quant_conv")
+        v, e = self.vae, self.vae_encoder
+        if e is None or (e.dtype, e.f32_gemm) != (v.dtype, v.f32_gemm):
+            self.vae_encoder = models.VAEEncoder(self._vae_sd, self.cfgs["vae"], self.device, v.dtype, f32_gemm=v.f32_gemm)
+
+    def to(self, device, dtype=None):
+        super().to(device, dtype)
+        self._sync_encoder()
+        return self
+
+    def _apply_vae_mode(self):
+        super()._apply_vae_mode()
+        self._sync_encoder()
+
+    def upcast_vae(self, gemm=None):
+        super().upcast_vae(gemm)
+        if self.vae is not None:
+            self._sync_encoder()
+        return self
+
+    def _encode_image(self, images_u8):
+        """Device u8 [B,H,W,3] -> the VAE posterior's moments [B,H/8,W/8,8] (mean | logvar) in the compute dtype."""
+        enc = self.vae_encoder
+        # VaeImageProcessor: [0,255] -> [-1,1] in the encoder's dtype; the fp16 VAE takes the fp32 pixels rounded once (the
+        # normalising kernel lives in the default library, which has no fp16 stores)
+        f16 = enc.dtype == torch.float16
+        px = imageproc.normalize_u8(images_u8, torch.float32 if f16 else enc.dtype, (0.5, 0.5, 0.5), (0.5, 0.5, 0.5))
+        moments = enc.encode(px.to(enc.dtype))
+        # VAE mode "f16": fp16 stores do not clamp -- the guard of the decoder's output, on all eight moment channels
+        self._enc_nonfinite = ~torch.isfinite(moments).flatten(1).all(1) if self._vae_mode == "f16" else None
+        return moments.to(self.dtype)
+
+    @torch.no_grad()
+    def generate_batch_img2img(self, prompt_ids, negative_ids, source_u8, control_u8, sample_noise, noise, num_inference_steps,
+                               strength, guidance_scale=0.0, controlnet_conditioning_scale=0.75, return_latents=False,
+                               prompt_ids_2=None, negative_ids_2=None):
+        """The contract of StableDiffusionControlNetImg2ImgPipeline.generate_batch_img2img plus the second tokenizer's ids:
+        source_u8 / control_u8 u8 [B,H,W,3] (numpy or device); sample_noise / noise [B,4,H/8,W/8] CPU draws (posterior sample first,
+        then the step noise).  guidance_scale <= 1: no CFG, `negative_ids` ignored, as in generate_batch."""
+        self._need_device()
+        t_start, _ = img2img_steps(num_inference_steps, strength)          # raises before anything is encoded or launched
+        if control_u8 is None:
+            raise ValueError("a control image is required by the ControlNet pipelines")
+        src, ctrl = self._device_u8(source_u8), self._device_u8(control_u8)
+        if tuple(src.shape) != tuple(ctrl.shape):
+            raise ValueError("source and control images must have the same size")
+        self._check_sides(ctrl, "image")
+        for what, t in (("sample_noise", sample_noise), ("noise", noise)):
+            self._check_latents(t, self.cfgs["unet"]["in_channels"], ctrl, what)
+
+        def start():
+            sch = self.scheduler
+            a_t = float(sch.alphas_cumprod[int(list(sch.set_timesteps(num_inference_steps))[t_start])])
+            return ops.vae_sample_noise(self._encode_image(src), self.latents_to_device(sample_noise), self.latents_to_device(noise),
+                                        self.cfgs["vae"]["scaling_factor"], a_t ** 0.5, (1.0 - a_t) ** 0.5)
+        out = self._denoise_decode(prompt_ids, negative_ids, ctrl, start, num_inference_steps, guidance_scale,
+                                   controlnet_conditioning_scale, return_latents, prompt_ids_2, negative_ids_2, t_start=t_start)
+        if self._enc_nonfinite is not None:              # "f16" mode: an item whose moments were not finite fails as a decode does
+            self.last_nonfinite = self._enc_nonfinite if self.last_nonfinite is None else (self.last_nonfinite | self._enc_nonfinite)
+        return out
+
+    def __call__(self, prompt=None, image=None, control_image=None, strength=0.8, num_inference_steps=50, generator=None,
+                 guidance_scale=5.0, negative_prompt=None, controlnet_conditioning_scale=0.8, **unused):
+        self._need_device()
+        if image is None or control_image is None or prompt is None:
+            raise ValueError("`prompt`, `image` (the source image) and `control_image` are required")
+        img2img_steps(num_inference_steps, strength)
+        src, ctrl = _rgb_u8(image), _rgb_u8(control_image)
+        e1 = self._noise(ctrl, generator)                                                # latent_dist.sample(generator)
+        e2 = self._noise(ctrl, generator)                                                # randn_tensor for add_noise
+        ids1 = self.tokenizer(str(prompt))
+        ids2 = self.pad_ids_2(self.tokenizer_2(str(prompt)))
+        n1 = n2 = None
+        if negative_prompt is not None and guidance_scale > 1.0:
+            n1 = self.tokenizer(str(negative_prompt))
+            n2 = self.pad_ids_2(self.tokenizer_2(str(negative_prompt)))
+        return self._output(self.generate_batch_img2img(ids1, n1, src[None], ctrl[None], e1, e2, num_inference_steps, strength,
+                                                        guidance_scale, controlnet_conditioning_scale, prompt_ids_2=ids2,
+                                                        negative_ids_2=n2))

@@ -293,21 +293,25 @@ def init_pipeline(base_model, controlnet, SDEdit, use_compile=False, sampler="dd
         from .scheduler import UniPCMultistepScheduler
         cls = UniPCMultistepScheduler if sampler == "unipcmultistep" else DDIMScheduler
         return cls.from_config(pipe.scheduler.config)
-    if base_model == "sd_xl-turbo" and controlnet == "canny" and not SDEdit:
+    if base_model == "sd_xl-turbo" and controlnet == "canny":
         # run_aug/run_aug.py:185-201: ControlNetModel(diffusers/controlnet-canny-sdxl-1.0) + sdxl-vae-fp16-fix +
-        # StableDiffusionXLControlNetPipeline(stabilityai/sdxl-turbo); :217-228 DDIM from the pipeline's scheduler
-        # config (twice), upcast_vae()
+        # StableDiffusionXLControlNetPipeline(stabilityai/sdxl-turbo), or with SDEDIT = 1 (:188-193)
+        # StableDiffusionXLControlNetImg2ImgPipeline; :217-228 DDIM from the pipeline's scheduler config (twice), upcast_vae()
+        if SDEdit:
+            from .pipeline import StableDiffusionXLControlNetImg2ImgPipeline as _XL
+        else:
+            _XL = StableDiffusionXLControlNetPipeline
         cfgs = cfgs or SDXL_TURBO
         if state_dicts is not None:
-            pipe = StableDiffusionXLControlNetPipeline(state_dicts, cfgs)
+            pipe = _XL(state_dicts, cfgs)
         elif weights_dir:
             vae_dir = os.path.join(weights_dir, "madebyollin/sdxl-vae-fp16-fix")
-            pipe = StableDiffusionXLControlNetPipeline.from_pretrained(
+            pipe = _XL.from_pretrained(
                 os.path.join(weights_dir, BASE_MODEL_DICT[base_model]), os.path.join(weights_dir, CONTROLNET_DICT_SD_XL[controlnet]),
                 vae_dir if os.path.isdir(vae_dir) else None, cfgs)
         else:
             logging.info("no WEIGHTS_DIR given: using architecture-exact SYNTHETIC weights (no checkpoint available offline)")
-            pipe = StableDiffusionXLControlNetPipeline.from_synthetic(cfgs, seed=0)
+            pipe = _XL.from_synthetic(cfgs, seed=0)
         pipe.scheduler = _scheduler_for(pipe)        # DDIM or UniPC, "trailing" spacing inherited from the sdxl-turbo config
         if xl_vae is not None:
             # Settings.XL_VAE: the VAE mode wins over the upcast below ("bf16" / "f16" make it a no-op).  Without it the
@@ -361,7 +365,7 @@ def init_pipeline(base_model, controlnet, SDEdit, use_compile=False, sampler="dd
         raise NotImplementedError(
             f"({base_model}, {controlnet}, SDEdit={SDEdit}): sd_v1.5 (text-to-image and SDEdit img2img, with the canny or HED "
             "ControlNet or without one), sd_v2.1 without a ControlNet (text-to-image and SDEdit img2img), blip_diffusion and "
-            "sd_xl-turbo with the canny ControlNet, and ip2p without a ControlNet are built; blip_diffusion-edit, sd_xl and the "
+            "sd_xl-turbo with the canny ControlNet (text-to-image and SDEdit img2img), and ip2p without a ControlNet are built; blip_diffusion-edit, sd_xl and the "
             "ControlNet-free forms of sd_xl-turbo / blip_diffusion are not")
     cfgs = cfgs or SD15
     if SDEdit:                                  # run_aug/run_aug.py:203-206: StableDiffusionControlNetImg2ImgPipeline
@@ -755,6 +759,12 @@ def hip_batch_generator(pipe, s: Settings, record=None):
             if ctrl is None:                               # Real-Guidance: StableDiffusionImg2ImgPipeline, UNet only
                 out = pipe.generate_batch_img2img(ids, neg_ids, src, lat[0::2], lat[1::2], s.NUM_INFERENCE_STEPS,
                                                   s.SDEDIT_STRENGTH, s.GUIDANCE_SCALE)
+            elif s.BASE_MODEL == "sd_xl-turbo":            # StableDiffusionXLControlNetImg2ImgPipeline: both tokenizers' ids
+                tok2 = pipe.tokenizer_2
+                ids2 = pipe.pad_ids_2(np.concatenate([tok2(it.prompt) for it in batch]))
+                out = pipe.generate_batch_img2img(ids, neg_ids, src, ctrl, lat[0::2], lat[1::2], s.NUM_INFERENCE_STEPS,
+                                                  s.SDEDIT_STRENGTH, s.GUIDANCE_SCALE, s.CONTROLNET_CONDITIONING_SCALE,
+                                                  prompt_ids_2=ids2, negative_ids_2=pipe.pad_ids_2(tok2(NEGATIVE_PROMPT)))
             else:
                 out = pipe.generate_batch_img2img(ids, neg_ids, src, ctrl, lat[0::2], lat[1::2], s.NUM_INFERENCE_STEPS,
                                                   s.SDEDIT_STRENGTH, s.GUIDANCE_SCALE, s.CONTROLNET_CONDITIONING_SCALE)
